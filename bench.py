@@ -14,8 +14,12 @@ gradient all-reduce (N>1), Adam step.  Workloads (BASELINE.json `configs`):
     3  same model, 16384 rays x (64+128), bf16 (the "saturate the GPU" size)
     5  SE3Field warp + axis_aligned_plane (hyper_slice_out_dim = GLO_dim = 8) at config-2 shapes, bf16
     1  legacy nerf_pl render_rays, coarse only, 256 rays x 64 samples, fp32 (the reference's CPU-runnable case)
-The K timed steps are repeated `--repeats` times back to back (each repeat bracketed by barrier + synchronize);
-`value` comes from the MEDIAN repeat, `ms_per_step_repeats` lists all of them.  Prints ONE JSON line (rank 0).
+The timed region is exactly K steps, split into `--repeats` back-to-back windows of (nearly) equal length, each
+bracketed by barrier + synchronize, after untimed replays (SETTLE_RAY_SAMPLES) that bring the step to its steady state;
+`ms_per_step` and `value` come from the MEDIAN window's time per step,
+`ms_per_step_repeats` lists all of them.  Prints ONE JSON line (rank 0).  `--dump-outputs DIR` writes what the last
+timed step computed (the step's outputs, its loss and the updated weights) as DIR/<name>.npy; inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 With N>1 over RCCL the whole step — forward, backward, gradient all-reduce, Adam — is ONE HIP graph (the collective is
 captured with it; `config.dp_step` says which form ran).  The default single-GPU config-2 run appends an `also` block to
 its line: configs 3, 5, 1 and the eval image loop as short child runs (`--no-also` skips it), so that the one command
@@ -24,6 +28,7 @@ the driver runs measures every single-GPU configuration of BASELINE.json.
 import argparse
 import ctypes
 import json
+import math
 import os
 import statistics
 import sys
@@ -54,10 +59,11 @@ CONFIGS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps in all (split into --repeats windows)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
-    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--repeats", type=int, default=5,
+                    help="windows the timed steps are split into; ms_per_step is the median window's time per step")
     ap.add_argument("--rays", type=int, default=None)
     ap.add_argument("--nc", type=int, default=None)
     ap.add_argument("--nf", type=int, default=None)
@@ -86,9 +92,14 @@ def parse():
     ap.add_argument("--no-capture-collective", action="store_true",
                     help="data-parallel runs: keep the gradient all-reduce OUT of the step graph (graph | eager all-reduce "
                          "| graph) instead of capturing it with the step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_BUDGET_BYTES >> 20} MB in all: larger arrays are replaced by a fixed seeded sample)")
     ap.add_argument("--force-dp", action="store_true",
                     help="run the data-parallel code path (process group + all-reduce between two graphs) even with one rank")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[a.config]
     for k in ("rays", "nc", "nf", "precision"):
         if getattr(a, k) is None:
@@ -452,18 +463,32 @@ def main():
         from hypernerf_torch_amd import calibration as CAL
         if rank == 0:
             calibration = CAL.probes(dev)
-        for _ in range(2):                  # back into the step's own thermal / clock state — on EVERY rank: with N > 1
-            step()                          # a step holds collectives, the ranks must run the same number of them
+    # back into the step's own steady state before the clock starts: after a pause (the warm-up's synchronisation, the
+    # calibration probes, zeroing the kernel timeline) and after the power sampler's start (its first reads of every
+    # board's hwmon) the first ~20 config-2 replays run up to 15 % slower.  The step is replayed, untimed, n_settle
+    # times: ~0.15 s of config 2, a count fixed by the arguments (the same on every rank — a step holds collectives —
+    # and from run to run, so that --dump-outputs sees the same number of updates).
+    # The timeline is zeroed BEFORE these replays and read right after them: the timed replays' share is the
+    # difference of two reads, without a second zeroing in front of the timed steps.  The sampler, too, runs from here;
+    # its `timed_region` summary keeps the samples taken during the timed steps (and the one before them, its baseline).
+    n_settle = min(SETTLE_MAX_STEPS, max(8, math.ceil(SETTLE_RAY_SAMPLES / (a.rays * (a.nc + a.nf)))))
     if L.TIMELINE is not None:
         L.timeline_reset()
     sampler = None
     if rank == 0 and not a.no_calibration:
         sampler = CAL.PowerSampler(dev).__enter__()
+    for _ in range(n_settle):
+        step()
+    timeline_before = L.timeline_read() if L.TIMELINE is not None else None       # synchronises
+    first_row = len(sampler.rows) if sampler is not None else 0
+    # exactly a.steps timed steps, in windows of (nearly) equal length; reps = seconds per step of each window
+    n_win = max(1, min(a.repeats, a.steps))
+    windows = [a.steps // n_win + (1 if i < a.steps % n_win else 0) for i in range(n_win)]
     reps = []
-    for _ in range(max(1, a.repeats)):
+    for k in windows:
         barrier()
         t0 = time.perf_counter()
-        for _ in range(a.steps):
+        for _ in range(k):
             out, loss = step()
         barrier()
         dt = time.perf_counter() - t0
@@ -471,16 +496,25 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        reps.append(dt)
-    timeline = L.timeline_read() if L.TIMELINE is not None else None       # the timed replays, nothing else
+        reps.append(dt / k)
+    timeline = None
+    if L.TIMELINE is not None:                  # the timed replays, nothing else
+        timeline = {k: {"ms": v["ms"] - timeline_before.get(k, {}).get("ms", 0.0),
+                        "runs": v["runs"] - timeline_before.get(k, {}).get("runs", 0)}
+                    for k, v in L.timeline_read().items()}
     if sampler is not None:
         sampler.__exit__(None, None, None)
+        sampler.rows = sampler.rows[max(0, first_row - 1):]
         calibration["timed_region"] = sampler.summary()
-        # hwmon's power figure is a running average over roughly a second: the timed region (steps x repeats, often
+        # hwmon's power figure is a running average over roughly a second: the timed region (--steps steps, often
         # < 0.2 s) is too short for it to settle, so the same step is replayed for another second, untimed, and sampled
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # copied now: the untimed steps below replay the same graph into the same output buffers
+        dumped = dump_outputs(a.dump_outputs, out, loss, arena)
     if not a.no_calibration:
         # ... on every rank, the same number of steps (fixed from the max-over-ranks step time: collectives inside)
-        n_soak = max(20, int(CALIB_SOAK_S / max(1e-6, statistics.median(reps) / a.steps)))
+        n_soak = max(20, int(CALIB_SOAK_S / max(1e-6, statistics.median(reps))))
         soak = CAL.PowerSampler(dev).__enter__() if rank == 0 else None
         for _ in range(n_soak):
             step()
@@ -495,23 +529,25 @@ def main():
         cnt = torch.ones(1, device=dev)
         dist.all_reduce(cnt)
         ranks_seen = int(cnt.item())                       # what the collective library itself reports
-    dt = statistics.median(reps)
+    dt = statistics.median(reps)           # seconds per timed step (median window)
     b = a.rays
     samples_step = world * b * (a.nc + a.nf)
-    value = samples_step * a.steps / dt
+    value = samples_step / dt
 
     res = {
         "metric": "ray-samples/sec (fwd+bwd+Adam), whole job; per-GPU = value/n_gpus",
         "value": value, "unit": "ray-samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": 1e3 * dt / a.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": 1e3 * dt, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16 (8-bit stash: e4m3 X, e5m2 dZ; opt-in)" if a.precision == "bf16s8" else a.precision, "data": "synthetic",
         "config": {"workload": workload, "baseline_config": a.config, "rays_per_gpu": b, "n_samples": a.nc,
                    "n_importance": a.nf, "parallelism": f"dp{world}", "hip_graph": use_graph, "wgrad_schedule": wgrad_schedule, "optimizer_launch": "fused with the gradient reduce (hn_mlp_wgrad_reduce_adam)" if opt.fuse_reduce else "hn_adam_step", "dp_code_path": dp, "dp_step": dp_graph, "grad_sync": None if sync is None else ("one all-reduce" if sync.split is None else f"two buckets split at float {sync.split} of {arena.numel}, overlapped"),
                    "ranks_seen_by_collective": ranks_seen},
         "per_gpu": value / world, "final_loss": float(loss.detach()),
-        "repeats": len(reps), "ms_per_step_repeats": [1e3 * r / a.steps for r in reps],
-        "ms_per_step_spread": [1e3 * min(reps) / a.steps, 1e3 * max(reps) / a.steps],
+        "settle_steps": n_settle, "repeats": len(reps), "steps_per_repeat": windows, "ms_per_step_repeats": [1e3 * r for r in reps],
+        "ms_per_step_spread": [1e3 * min(reps), 1e3 * max(reps)],
     }
+    if dumped is not None:
+        res["dump_outputs"] = dumped
 
     res["build"] = L.build_id()
     if calibration is not None:
@@ -520,8 +556,8 @@ def main():
         # per-kernel times of the machine kernels come from the timed region itself (kernel timeline); the eager pass
         # (HIP events around every C-ABI launch) adds the small kernels' list at N = 1 only — with N > 1 every rank
         # goes straight to the final barrier, no rank waits for another's rank-local work
-        n_timed = a.steps * max(1, a.repeats)
-        res.update(roofline(a, L, fwd_bwd, opt, programs(), reference_programs(), dt / a.steps, b, timeline, n_timed,
+        n_timed = a.steps
+        res.update(roofline(a, L, fwd_bwd, opt, programs(), reference_programs(), dt, b, timeline, n_timed,
                             eager=(world == 1 and not dp), calibration=calibration))
         if world > 1 and "roofline" in res:
             res["roofline"]["scope"] = f"rank 0 (1 of {world} GPUs): its own kernels inside the timed region"
@@ -562,16 +598,65 @@ def main():
         print(json.dumps(res), flush=True)
 
 
+DUMP_BUDGET_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_SEED = 20250101              # the fixed sample of an array too large for its share of the budget
+
+
+def dump_outputs(dirname, out, loss, arena):
+    """--dump-outputs: the arrays a caller of the timed step receives — every tensor of the model's output dict, the
+    loss, and the weights the optimizer left (the flat parameter arena) — as <dirname>/<name>.npy, floating point as
+    float32 (float64 stays float64), integers and flags as float64 (exact).  If they add up to more than
+    DUMP_BUDGET_BYTES, each array larger than an equal share of it is replaced by a fixed, seeded sample of its
+    elements (the same indices in every run of the same shapes).  Returns {name: {shape, dtype, sampled}}."""
+    import numpy as np
+    arrays = {}
+
+    def walk(prefix, x):
+        if isinstance(x, torch.Tensor):
+            arrays[prefix] = x
+        elif isinstance(x, dict):
+            for k, v in x.items():
+                walk(f"{prefix}_{k}" if prefix else str(k), v)
+        elif isinstance(x, (list, tuple)):
+            for i, v in enumerate(x):
+                walk(f"{prefix}_{i}", v)
+    walk("", out)
+    arrays["loss"] = loss
+    arrays["params_after_step"] = arena.data
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32
+        safe = "".join(c if c.isalnum() or c in "_.-" else "_" for c in name)
+        host[safe] = t.to(dt).cpu().numpy()
+    total = sum(v.nbytes for v in host.values())
+    share = DUMP_BUDGET_BYTES // max(1, len(host))
+    os.makedirs(dirname, exist_ok=True)
+    info = {}
+    for name, v in host.items():
+        sampled = None
+        if total > DUMP_BUDGET_BYTES and v.nbytes > share:
+            n = share // v.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, size=n, replace=False))
+            sampled = n
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+        info[name] = {"shape": list(host[name].shape), "dtype": str(v.dtype), "sampled": sampled}
+    return {"dir": os.path.abspath(dirname), "arrays": info}
+
+
 CHECK_BOUND = {"fp32": 1e-4, "bf16": 1e-2, "bf16s8": 1e-2}      # cpu_baseline.check against the fp32 oracle, see its note
 CHECK_BOUND_BF16_CONTRACT = 1e-3      # bf16 modes against the oracle under the same arithmetic contract (O.bf16_operands)
 CALIB_SOAK_S = 1.2
+SETTLE_RAY_SAMPLES = 12e6   # untimed replays between warm-up / calibration and the timed steps: ~0.15 s of config 2
+SETTLE_MAX_STEPS = 200
 ALSO_BUDGET_S = 60.0        # the whole block; a child that would start later is recorded as skipped
 
 
 def also_block():
     """The driver runs ONE command (`python bench.py`, BASELINE config 2).  Four of the five BASELINE configurations and
     the evaluation loop would otherwise only ever be builder-run lines under profiles/: the default run therefore
-    appends short measurements of configs 3, 5, 1 (<= 10 steps x 3 repeats, HIP-graph replay, no CPU baseline) and of
+    appends short measurements of configs 3, 5, 1 (<= 30 timed steps in 3 windows, HIP-graph replay, no CPU baseline) and of
     `inference.render_image` (tools/eval_bench.py) — each its own child process, started after the headline has been
     measured (its ~10 GB of device memory stay allocated next to the children's; ordinary children, never an exec),
     each with value, ms/step, the dominant kernel's fractions and the kernel build it ran.  Bounded: ALSO_BUDGET_S for
@@ -580,9 +665,9 @@ def also_block():
     t0 = time.perf_counter()
     out = {"note": "short runs appended to the config-2 headline; same metric, same definitions (bench.py --config N); "
                    "not part of `value`"}
-    jobs = [("config3", ["--config", "3", "--steps", "5", "--warmup", "2", "--repeats", "3"]),
-            ("config5", ["--config", "5", "--steps", "10", "--warmup", "3", "--repeats", "3"]),
-            ("config1", ["--config", "1", "--steps", "10", "--warmup", "3", "--repeats", "3"]),
+    jobs = [("config3", ["--config", "3", "--steps", "15", "--warmup", "2", "--repeats", "3"]),
+            ("config5", ["--config", "5", "--steps", "30", "--warmup", "3", "--repeats", "3"]),
+            ("config1", ["--config", "1", "--steps", "30", "--warmup", "3", "--repeats", "3"]),
             ("render_image", None)]
     for name, argv in jobs:
         left = ALSO_BUDGET_S - (time.perf_counter() - t0)

@@ -12,8 +12,9 @@
 3. the same for the legacy nerf_pl `NeRF` (models/nerf.py) under the prefix eval.py uses.
 Import shims: the ones of make_golden.py plus import-only stubs for `torchvision.transforms`, `cv2` and `PIL`
 (the reference's `utils/__init__.py` pulls in its visualisation helpers; none of them is on the loader's path).
-Prints one JSON line with what was compared; tests/test_host_api.py::test_ckpt_round_trip_through_the_reference_loader
-runs it whenever /root/reference is present (it never is on the GPU box)."""
+Prints one JSON line with what was compared.  tests/test_host_api.py::test_ckpt_round_trip_through_the_reference_loader
+checks the same round trips without the reference: against its model's key / shape lists recorded in the g11 / g12
+fixtures and its loader's rule restated."""
 import json
 import os
 import sys

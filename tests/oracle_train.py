@@ -38,6 +38,21 @@ def usable_cores() -> int:
     return max(1, n)
 
 
+# worker processes of the CPU oracle beside the process that holds the GPU.  A shared GPU node may stop a job that has
+# more than six processes per card: with one worker per two cores (eight on a 16-CPU node) the GPU suite was stopped
+# that way while this pool ran, so the pool stays this small whatever the core count (the cores are shared out as
+# threads instead)
+MAX_CPU_WORKERS = 4
+
+
+def cpu_workers(n_runs: int):
+    """(worker processes, threads per worker) for n_runs oracle runs beside a GPU process: at most MAX_CPU_WORKERS
+    processes, the usable cores shared out between them, at least 2 threads each."""
+    cores = usable_cores()
+    procs = max(1, min(n_runs, MAX_CPU_WORKERS, cores // 2))
+    return procs, max(2, cores // procs)
+
+
 SCENE_FREQ = 1.0        # spatial frequency scale of the analytic scene (lower = easier)
 
 

@@ -30,12 +30,10 @@ def main():
     freq = float(a[8]) if len(a) > 8 else 1.0
     seed0 = int(a[9]) if len(a) > 9 else 0      # seeds first_seed .. first_seed + seeds - 1 (a second, independent sample)
     noise = 0.5
-    cores = OT.usable_cores()
     # the oracle's small-batch steps are op-overhead bound (0.09 s per step at 8 threads, 0.12 at 2): few threads per run,
-    # one process per seed — and never more threads than the affinity mask admits (an over-subscribed OpenMP pool on a
-    # quota-limited box is orders of magnitude slower)
-    procs = max(1, min(n_seeds, cores // 2))
-    threads = 2
+    # a small pool of worker processes — and never more threads than the affinity mask admits (an over-subscribed
+    # OpenMP pool on a quota-limited box is orders of magnitude slower)
+    procs, threads = OT.cpu_workers(n_seeds)
     t0 = time.perf_counter()
     ctx = mp.get_context("spawn")
     pool = ctx.Pool(procs)

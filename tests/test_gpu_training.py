@@ -192,11 +192,11 @@ def test_bf16_training_psnr_vs_cpu_oracle():
     import torch.multiprocessing as mp
     import oracle_train as OT
     steps, b, nc, nf, n_seeds, lr, lr_end, freq, noise = 400, 128, 16, 16, 8, 1e-3, 1e-4, 0.5, 0.5
-    procs = max(1, min(n_seeds, OT.usable_cores() // 2))
+    procs, threads = OT.cpu_workers(n_seeds)
     ctx = mp.get_context("spawn")
     pool = ctx.Pool(procs)
     try:
-        fut = pool.map_async(OT.cpu_run, [(s_, steps, b, nc, nf, lr, noise, 2, lr_end, freq) for s_ in range(n_seeds)])
+        fut = pool.map_async(OT.cpu_run, [(s_, steps, b, nc, nf, lr, noise, threads, lr_end, freq) for s_ in range(n_seeds)])
         gpu = [OT.gpu_run(s_, steps, b, nc, nf, lr, noise, "bf16", lr_end=lr_end, freq=freq) for s_ in range(n_seeds)]
         cpu = sorted(fut.get(timeout=900))
     finally:

@@ -427,6 +427,42 @@ def test_bench_also_block_host_logic(monkeypatch):
     assert not calls and all("skipped" in out[k] for k in ("config3", "config5", "config1", "render_image"))
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every tensor of the step's output dict, the loss and the weights as <name>.npy in
+    float32 (float64 kept, integers exact in float64); over the byte budget, each array larger than its share is a
+    fixed seeded sample — the same elements in every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Arena:
+        data = torch.arange(10, dtype=torch.float32)
+    out = {"coarse": {"rgb": torch.rand(4, 3, dtype=torch.float64), "idx": torch.tensor([1, 2 ** 40])},
+           "fine": {"rgb": torch.rand(4, 3).bfloat16(), "missing": None}}
+    loss = torch.tensor(0.25)
+    info = bench.dump_outputs(str(tmp_path / "a"), out, loss, Arena)
+    names = {"coarse_rgb", "coarse_idx", "fine_rgb", "loss", "params_after_step"}
+    assert set(info["arrays"]) == names and sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["coarse_rgb"].dtype == np.float64 and np.array_equal(got["coarse_rgb"], out["coarse"]["rgb"].numpy())
+    assert got["coarse_idx"].dtype == np.float64 and got["coarse_idx"].tolist() == [1.0, float(2 ** 40)]
+    assert got["fine_rgb"].dtype == np.float32 and np.array_equal(got["fine_rgb"], out["fine"]["rgb"].float().numpy())
+    assert got["loss"] == np.float32(0.25) and np.array_equal(got["params_after_step"], np.arange(10, dtype=np.float32))
+    assert all(v["sampled"] is None for v in info["arrays"].values())
+    # over budget: the large array is sampled, the small ones are not, and the sample is the same run to run
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    big = {"fine": {"rgb": torch.arange(3000, dtype=torch.float32)}}
+    sizes = []
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), big, loss, Arena)
+        assert info["arrays"]["fine_rgb"]["sampled"] == 4 * 1000 // 3 // 4 and info["arrays"]["loss"]["sampled"] is None
+        sizes.append(sum(os.path.getsize(tmp_path / d / f) - 128 for f in os.listdir(tmp_path / d)))
+    a, c = np.load(tmp_path / "b" / "fine_rgb.npy"), np.load(tmp_path / "c" / "fine_rgb.npy")
+    assert np.array_equal(a, c) and len(np.unique(a)) == a.size and np.all(np.diff(a) > 0)
+    assert max(sizes) <= 4 * 1000
+
+
 def test_pmc_traffic_is_tied_to_the_build(tmp_path, monkeypatch):
     """bench.py quotes a profiles/rNN_traffic_configC.json only when it was collected on the running kernels."""
     import importlib.util
@@ -461,20 +497,88 @@ def test_pmc_traffic_is_tied_to_the_build(tmp_path, monkeypatch):
     assert bench._pmc_traffic(A)[0] is None
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/utils"), reason="build container only: needs /root/reference")
-def test_ckpt_round_trip_through_the_reference_loader():
-    """SURVEY.md §8 f3, executed rather than argued: tests/golden/check_ckpt_with_reference.py imports the reference's
-    own `load_ckpt` / `extract_model_state_dict` (utils/__init__.py:66-88) and round-trips checkpoints between the
-    reference's modules and this package's (arena-backed) ones, both directions, NerfModel and legacy NeRF."""
-    import json
-    import subprocess
-    import sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "check_ckpt_with_reference.py")],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-3000:]
-    rep = json.loads(out.stdout.strip().splitlines()[-1])
-    assert rep["ours_to_reference_tensors"] == rep["reference_to_ours_tensors"] == 94
-    assert rep["legacy_ours_to_reference_tensors"] == rep["legacy_reference_to_ours_tensors"] == 24
+def _reference_strict_load(layout, picked, what):
+    """What the reference's `load_ckpt` does with the entries its `extract_model_state_dict` picked (utils/__init__.py:
+    66-88: model.state_dict().update(picked), then a strict load_state_dict), against the reference model's own key and
+    shape list recorded in the golden fixtures: no unknown key, no shape mismatch, and every parameter replaced."""
+    keys, shapes = layout["keys"].tolist(), layout["shapes"].tolist()
+    assert set(picked) <= set(keys), (what, set(picked) - set(keys))
+    for k, shp in zip(keys, shapes):
+        if k in picked:
+            assert str(tuple(picked[k].shape)) == shp, (what, k, tuple(picked[k].shape), shp)
+    return {k: picked[k] for k in keys if k in picked}
+
+
+def _layout_shapes(layout):
+    """{name: shape} of a recorded key / shape list (shapes stored as their tuple's text, e.g. '(256, 63)')."""
+    return {k: tuple(int(x) for x in s.strip("()").split(",") if x.strip())
+            for k, s in zip(layout["keys"].tolist(), layout["shapes"].tolist())}
+
+
+def test_ckpt_round_trip_through_the_reference_loader(tmp_path, golden_dir):
+    """checkpoints cross between this package and the reference both ways, NerfModel and legacy NeRF.
+    The reference's side is its model's key and shape list (recorded from the reference itself: g11 / g12 fixtures)
+    and its loader's rule (strip '<model_name>.', update, strict load — restated in _reference_strict_load).
+    1. ours -> reference: save_ckpt of an arena-backed model fills every parameter of the reference's model, with
+    prefixes_to_ignore honoured; 2. reference -> ours: a Lightning-layout file (`nerf.` prefix, train.py:48, plus a
+    foreign entry) with the reference's keys and shapes loads into an arena-backed model; 3. the same for the legacy
+    NeRF under the prefix eval.py uses."""
+    import hashprng as H
+    from hypernerf_torch_amd.utils import extract_model_state_dict, load_ckpt, save_ckpt
+    kw = dict(hyper_slice_method="bendy_sheet", use_nerf_embed=True, use_alpha_cond=True, view_fourier_dim=6)
+    g11 = np.load(os.path.join(golden_dir, "g11_model_bendy_cond_8_8.npz"))
+    g12 = np.load(os.path.join(golden_dir, "g12_legacy_c_only.npz"))
+    report = {}
+
+    def same(a, b, what):
+        assert set(a) == set(b), (what, set(a) ^ set(b))
+        for k in a:
+            assert a[k].shape == b[k].shape and torch.equal(a[k].detach().cpu().float(), b[k].detach().cpu().float()), (what, k)
+        return len(a)
+
+    # 1. ours -> reference loader
+    torch.manual_seed(11)
+    mine = models.NerfModel(EMB, **kw)
+    arena = HN.ParamArena(mine.parameters())
+    with torch.no_grad():
+        arena.data.add_(torch.randn_like(arena.data) * 0.01)    # not the initial weights of anyone
+    path = save_ckpt(mine, os.path.join(tmp_path, "epoch=3.ckpt"), model_name="nerf", epoch=3, global_step=77)
+    picked = extract_model_state_dict(path, model_name="nerf")
+    assert set(picked) == set(g11["keys"].tolist()) == set(mine.state_dict())
+    theirs = _reference_strict_load(g11, picked, "ours -> reference")
+    report["ours_to_reference_tensors"] = same(theirs, mine.state_dict(), "ours -> reference")
+    kept = _reference_strict_load(g11, extract_model_state_dict(path, model_name="nerf", prefixes_to_ignore=["warp_field"]),
+                                  "prefixes_to_ignore")
+    assert not any(k.startswith("warp_field") for k in kept)
+    assert any(k.startswith("warp_field") for k in g11["keys"].tolist())
+    assert torch.equal(kept["hyper_sheet_mlp.mlp.linears.0.weight"],
+                       mine.hyper_sheet_mlp.mlp.linears[0].weight.detach().float())
+
+    # 2. reference -> ours (Lightning layout)
+    src = H.fill_state_dict(_layout_shapes(g11), 12)
+    lightning = {"epoch": 5, "global_step": 9, "state_dict": {"nerf." + k: v.clone() for k, v in src.items()}}
+    lightning["state_dict"]["loss.dummy"] = torch.zeros(1)
+    p2 = os.path.join(tmp_path, "epoch=5.ckpt")
+    torch.save(lightning, p2)
+    dst = models.NerfModel(EMB, **kw)
+    arena2 = HN.ParamArena(dst.parameters())
+    load_ckpt(dst, p2, "nerf")
+    report["reference_to_ours_tensors"] = same(dst.state_dict(), src, "reference -> ours")
+    assert arena2.attached(dst.warp_field.mlp.linears[0].weight) is not None
+
+    # 3. legacy nerf_pl NeRF both ways (eval.py loads 'nerf_coarse' / 'nerf_fine' prefixes in nerf_pl; any prefix works)
+    torch.manual_seed(13)
+    lm = legacy_nerf.NeRF()
+    p3 = save_ckpt(lm, os.path.join(tmp_path, "legacy.ckpt"), model_name="nerf_coarse")
+    lr = _reference_strict_load(g12, extract_model_state_dict(p3, model_name="nerf_coarse"), "legacy ours -> reference")
+    report["legacy_ours_to_reference_tensors"] = same(lr, lm.state_dict(), "legacy ours -> reference")
+    lsrc = H.fill_state_dict(_layout_shapes(g12), 13)
+    torch.save({"state_dict": {"nerf_coarse." + k: v for k, v in lsrc.items()}}, p3)
+    load_ckpt(lm, p3, "nerf_coarse")
+    report["legacy_reference_to_ours_tensors"] = same(lm.state_dict(), lsrc, "legacy reference -> ours")
+
+    assert report["ours_to_reference_tensors"] == report["reference_to_ours_tensors"] == 94
+    assert report["legacy_ours_to_reference_tensors"] == report["legacy_reference_to_ours_tensors"] == 24
 
 
 def test_lr_schedules_match_the_reference(golden_dir):
