@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("HN_LIB_PATH") or PRODUCT_LIB_PATH
 SOURCES = ["hn_mlp.hip", "hn_render.hip", "hn_calib.hip"]
 CSRC_HEADERS = ["hn_common.h", "hn_pack.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hn_kernels.h")
-BUILD_MACROS = ("HN_WGRAD_PERSIST", "HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_EXP", "HN_WGRAD_BIAS_MFMA", "HN_WGRAD_BLOCK", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT", "HN_WSTREAM_ASYM")     # build-time tuning knobs (A/B experiments)
+BUILD_MACROS = ("HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT")     # build-time tuning knobs (A/B experiments)
 
 HN_MODE_F32, HN_MODE_BF16, HN_MODE_BF16_S8 = 0, 1, 2
 BUILD_CONFIG_KEYS = ("WGRAD_STAGES", "WGRAD_MAXSLOT", "WGRAD_BIAS_MFMA", "CHUNK_UNITS", "WGRAD_BLOCK", "WSTREAM_ASYM",
@@ -47,7 +47,7 @@ def _read_build_config(path: str):
     return {k: v for k, v in zip(BUILD_CONFIG_KEYS, vals)}
 
 
-# hn_wgrad_kernel's LDS ring, the weight-stream chunk and the bias path of the build: host-side mirrors of build-time
+# hn_wgrad_kernel's LDS ring and the weight-stream chunk of the build: host-side mirrors of build-time
 # macros in csrc/hn_mlp.hip.  They come from the LIBRARY (hn_build_config) whenever one exists — a library prebuilt
 # with other knobs carries its own values; the environment variables (which also drive build()) only stand in before the
 # first build, and load() refuses a library that disagrees with the mirrors in use.
@@ -55,7 +55,6 @@ BUILD_CONFIG = _read_build_config(LIB_PATH)
 _cfg = BUILD_CONFIG or {}
 WGRAD_STAGES = _cfg.get("WGRAD_STAGES", int(os.environ.get("HN_WGRAD_STAGES") or 2))
 WGRAD_MAXSLOT = _cfg.get("WGRAD_MAXSLOT", int(os.environ.get("HN_WGRAD_MAXSLOT") or 8))
-WGRAD_BIAS_MFMA = bool(_cfg.get("WGRAD_BIAS_MFMA", os.environ.get("HN_WGRAD_BIAS_MFMA", "0") not in ("", "0")))
 WGRAD_MAX_STAGE_KB = min(8 * WGRAD_MAXSLOT, 160 // WGRAD_STAGES)
 HN_MAX_SRC, HN_MAX_DST, HN_MAX_SLOTS = 8, 4, 128
 HN_OP_WORDS, HN_CHUNK_UNITS, HN_DSRC_COMPS = 8, _cfg.get("CHUNK_UNITS", int(os.environ.get("HN_CHUNK_UNITS", 32))), 32
@@ -256,12 +255,11 @@ def load():
             raise HnError(f"{LIB_PATH} does not export {name}")
         getattr(lib, name).restype = C.c_int
     # the host tables in use were cut for the mirrors above: a library built with other knobs must not run under them
-    # (e.g. bias records whose slab tiles a bias-by-MFMA build never writes: garbage gradients, no error)
+    # (e.g. job stages cut for another ring depth or LDS-DMA slot count: garbage gradients, no error)
     buf = (C.c_int32 * len(BUILD_CONFIG_KEYS))()
     n_cfg = lib.hn_build_config(buf, len(BUILD_CONFIG_KEYS))
     now = {k: int(buf[i]) for i, k in enumerate(BUILD_CONFIG_KEYS[:n_cfg])}
-    mine = {"WGRAD_STAGES": WGRAD_STAGES, "WGRAD_MAXSLOT": WGRAD_MAXSLOT, "WGRAD_BIAS_MFMA": int(WGRAD_BIAS_MFMA),
-            "CHUNK_UNITS": HN_CHUNK_UNITS}
+    mine = {"WGRAD_STAGES": WGRAD_STAGES, "WGRAD_MAXSLOT": WGRAD_MAXSLOT, "CHUNK_UNITS": HN_CHUNK_UNITS}
     bad = {k: (v, now.get(k)) for k, v in mine.items() if now.get(k) != v}
     if bad:
         raise HnError(f"{LIB_PATH} was built with other tuning knobs than the host tables assume (mirror, library): {bad}; "

@@ -35,10 +35,7 @@ struct WStream {
   HN_DEV void issue(int c) {
     const char* src = g + (size_t)c * (HN_CHUNK_UNITS * 1024);
     char* dst = lds + (c & 1) * (HN_CHUNK_UNITS * 1024);
-#ifndef HN_WSTREAM_ASYM
-#define HN_WSTREAM_ASYM 1      /* 0: rounds 1-5a, every wave issues its eighth of a chunk's DMA (A/B knob) */
-#endif
-    if constexpr (WAVES == 8 && HN_WSTREAM_ASYM != 0) {
+    if constexpr (WAVES == 8) {
       // Waves w and w + 4 share a SIMD.  A wave sits ~100-200 cycles on every 1-KiB LDS-DMA instruction it issues (the
       // memory pipe's back-pressure, measured in hn_wgrad_kernel); with all eight waves issuing four pieces each behind
       // the chunk barrier, every SIMD's matrix pipe idled that long once per chunk.  Now the SECOND wave of every SIMD
@@ -1127,31 +1124,13 @@ HN_DEV void hn_dw_tr_offsets(int lane, int& o0, int& o1) {
   o1 = u * 1024 + hn_stash_slot(8 * hh + 4 + q, h, u) * 16 + 8 * g;
 }
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-// The four transposed reads of one tile + the wait for them, as ONE asm statement.  (The compiler builtin of
-// ds_read_b64_tr_b16 carries no memory operand, so next to LDS-DMA in flight hipcc guards every one of them with
-// s_waitcnt vmcnt(0) — which drains the whole stage ring: measured 0.70 -> 1.00 ms on the weight-gradient launch.  The
-// asm form is invisible to that rule; the data dependence of the MFMAs on its outputs orders them behind the wait.)
-// a0 / a1: LDS byte addresses of the lane's reads jh = 0 / 1 in tile 0; OFF: byte offset of the tile.
-template <int OFF>
-HN_DEV void hn_tr_tile(bf16x8* v, unsigned a0, unsigned a1) {
-  u32x2 l0, h0, l1, h1;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %4 offset:%6\n\t"
-      "ds_read_b64_tr_b16 %1, %5 offset:%6\n\t"
-      "ds_read_b64_tr_b16 %2, %4 offset:%7\n\t"
-      "ds_read_b64_tr_b16 %3, %5 offset:%7\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1)
-      : "v"(a0), "v"(a1), "n"(OFF), "n"(OFF + 256)
-      : "memory");
-  const u32x4 w0 = {l0[0], l0[1], h0[0], h0[1]}, w1 = {l1[0], l1[1], h1[0], h1[1]};
-  v[0] = __builtin_bit_cast(bf16x8, w0);
-  v[1] = __builtin_bit_cast(bf16x8, w1);
-}
 // All operand tiles of one 32-point block of a wave's rectangle (2 X tiles, NZ dZ tiles of 2 KiB) under ONE wait: 8 + 4 NZ
 // transposed reads in flight together instead of a read-wait-multiply round trip per tile (an LDS round trip next to the
 // ring's DMA writes is ~300 cycles; six of them per block were the critical path of a stage).  Tiles the wave does not own
-// are read all the same (never used; reads past the end of LDS return zero).
+// are read all the same (never used; reads past the end of LDS return zero).  The reads and their wait are ONE asm statement:
+// the compiler builtin of ds_read_b64_tr_b16 carries no memory operand, so next to LDS-DMA in flight hipcc guards every one
+// of them with s_waitcnt vmcnt(0) — which drains the whole stage ring (measured 0.70 -> 1.00 ms on the weight-gradient
+// launch).  The asm form is invisible to that rule; the data dependence of the MFMAs on its outputs orders them behind the wait.
 template <int NZ>
 HN_DEV void hn_tr_block(bf16x8 (*x)[2], bf16x8 (*z)[2], unsigned ax0, unsigned ax1, unsigned az0, unsigned az1) {
   u32x2 r[8 + 4 * NZ];
@@ -1224,19 +1203,9 @@ HN_DEV void hn_tr_block(bf16x8 (*x)[2], bf16x8 (*z)[2], unsigned ax0, unsigned a
 template <>
 struct DwFrag<true> {
   bf16x8 v[2];
-  template <int OFF>
-  HN_DEV void load_tr(unsigned a0, unsigned a1) { hn_tr_tile<OFF>(v, a0, a1); }
-  HN_DEV void load(const char*, int, int, int) {}
   HN_DEV static void mma(f32x16& acc, const DwFrag& a, const DwFrag& b) {
     acc = hn_mfma_bf16(a.v[0], b.v[0], acc);
     acc = hn_mfma_bf16(a.v[1], b.v[1], acc);
-  }
-  HN_DEV static void mma_ones(f32x16& acc, const DwFrag& a, int, int) {      // one accumulator per tile, every column
-    bf16x8 one;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) one[j] = (__bf16)1.0f;
-    acc = hn_mfma_bf16(a.v[0], one, acc);
-    acc = hn_mfma_bf16(a.v[1], one, acc);
   }
   // bias gradient on the vector pipe (round 5): s + the sum of this lane's 16 values — feature (lane & 31) of the dZ
   // tile at the 16 points of the lane's half — as eight v_dot2c_f32_bf16 with a (1, 1) operand.  The all-ones MFMAs it
@@ -1255,23 +1224,15 @@ struct DwFrag<true> {
 template <>
 struct DwFrag<false> {
   f32x4 v[4];
-  HN_DEV void load(const char* tile, int lane, int, int) {
+  HN_DEV void load(const char* tile, int lane) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) v[g] = *reinterpret_cast<const f32x4*>(tile + g * 1024 + lane * 16);
   }
-  template <int OFF>
-  HN_DEV void load_tr(unsigned, unsigned) {}
   HN_DEV static void mma(f32x16& acc, const DwFrag& a, const DwFrag& b) {
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc = hn_mfma_f32(a.v[g][e], b.v[g][e], acc);
-  }
-  HN_DEV static void mma_ones(f32x16& acc, const DwFrag& a, int, int) {     // fp32: one accumulator per tile, every column
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = hn_mfma_f32(a.v[g][e], 1.0f, acc);
   }
   HN_DEV float add_point_sum(float s) const {       // the lane's 16 points of feature (lane & 31)
 #pragma unroll
@@ -1294,20 +1255,6 @@ HN_DEV int hn_dw8_offset(int lane) {
 HN_DEV int hn_dw8_feature(int c) { return hn_rho(8 * (c >> 4) + (c & 7), (c >> 3) & 1); }
 struct DwFrag8 {
   long v[2];
-  template <int OFF>
-  HN_DEV void load_tr(unsigned a0, unsigned) {
-    u32x2 l0, l1;
-    asm volatile(
-        "ds_read_b64_tr_b8 %0, %2 offset:%3\n\t"
-        "ds_read_b64_tr_b8 %1, %2 offset:%4\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(l0), "=&v"(l1)
-        : "v"(a0), "n"(OFF), "n"(OFF + 512)
-        : "memory");
-    v[0] = __builtin_bit_cast(long, l0);
-    v[1] = __builtin_bit_cast(long, l1);
-  }
-  HN_DEV void load(const char*, int, int, int) {}
   // a: dZ (e5m2), b: X (e4m3)
   HN_DEV static void mma(f32x16& acc, const DwFrag8& a, const DwFrag8& b) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf8_fp8(a.v[0], b.v[0], acc, 0, 0, 0);
@@ -1315,7 +1262,6 @@ struct DwFrag8 {
   }
   // bias gradient of tile `col` (0..3) into COLUMN `col` of the one shared accumulator: the B operand is all ones on the
   // lanes of that column and zero elsewhere, so four tiles' row sums live side by side in 16 registers instead of 64
-  HN_DEV float add_point_sum(float s) const { return s; }      // (the 8-bit stash keeps the all-ones MFMA)
   HN_DEV static void mma_ones(f32x16& acc, const DwFrag8& a, int col, int lane) {
     const long one = ((lane & 31) == col) ? 0x3838383838383838L : 0L;       // e4m3 1.0 in every byte of column `col`
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf8_fp8(a.v[0], one, acc, 0, 0, 0);
@@ -1467,18 +1413,13 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
   f32x16 acc[4][2];
   // bias gradient db[n] = sum_p dZ[p][n].  bf16 / fp32: a running sum per dZ tile on the vector pipe (bsum[i]: this
   // lane's feature over the points of its half, DwFrag::add_point_sum).  8-bit stash: ONE all-ones MFMA accumulator,
-  // tile i in its column i (DwFrag8::mma_ones).
-#ifndef HN_WGRAD_BIAS_MFMA
-#define HN_WGRAD_BIAS_MFMA 0      /* 1: rounds 1-4, an all-ones MFMA accumulator per dZ tile (A/B knob) */
-#endif
-  constexpr bool BM = S8 || (HN_WGRAD_BIAS_MFMA != 0);
-  constexpr int NB = S8 ? 1 : (BM ? 4 : 1);
-  f32x16 accb[NB];
+  // tile i in its column i (accb, DwFrag8::mma_ones).
+  f32x16 accb;
   float bsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  for (int e = 0; e < 16; ++e) accb[e] = 0.0f;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) accb[i % NB][e] = 0.0f;
+  for (int i = 0; i < 4; ++i) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -1612,15 +1553,10 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
 #pragma unroll
             for (int j = 0; j < 2; ++j)
               if (j < my_k) DwFrag8::mma(acc[i][j], za8[i], xb[j]);
-            if (bias_mask & (1u << i)) DwFrag8::mma_ones(accb[0], za8[i], i, lane);
+            if (bias_mask & (1u << i)) DwFrag8::mma_ones(accb, za8[i], i, lane);
           }
         });
-        continue;
-      }
-#ifndef HN_WGRAD_BLOCK
-#define HN_WGRAD_BLOCK 1      /* 0: rounds 1-5a, one read-wait-multiply round trip per operand tile (A/B knob) */
-#endif
-      if constexpr (BF16 && !S8 && HN_WGRAD_BLOCK != 0) {
+      } else if constexpr (BF16) {
         // every operand tile of the block under one LDS wait (hn_tr_block), then the products back to back
         DwFrag<true> za[4];
         bf16x8 xv[2][2], zv[4][2];      // (a wave with <= 2 dZ tiles reads two; tiles 2, 3 are then never multiplied: i < my_n below)
@@ -1636,37 +1572,25 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
 #pragma unroll
             for (int j = 0; j < 2; ++j)
               if (j < my_k) Fr::mma(acc[i][j], za[i], xb[j]);
-            if (bias_mask & (1u << i)) {
-              if constexpr (BM) Fr::mma_ones(accb[i % NB], za[i], i, lane);
-              else bsum[i] = za[i].add_point_sum(bsum[i]);
-            }
+            if (bias_mask & (1u << i)) bsum[i] = za[i].add_point_sum(bsum[i]);
           }
         });
-        continue;
-      }
-      if constexpr (BF16) {
-        if (0 < my_k) xb[0].template load_tr<0>(ax + tro0, ax + tro1);
-        if (1 < my_k) xb[1].template load_tr<TBc>(ax + tro0, ax + tro1);
       } else {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          if (j < my_k) xb[j].load(sb + (size_t)(jb.n_nt + k0 + j) * TB, lane, 0, 0);
-      }
-      static_for4([&](auto I) __attribute__((always_inline)) {
-        constexpr int i = decltype(I)::value;
-        if (i < my_n) {
-          Fr za;
-          if constexpr (BF16) za.template load_tr<TBc * i>(az + tro0, az + tro1);
-          else za.load(sb + (size_t)(n0 + i) * TB, lane, 0, 0);
+          if (j < my_k) xb[j].load(sb + (size_t)(jb.n_nt + k0 + j) * TB, lane);
+        static_for4([&](auto I) __attribute__((always_inline)) {
+          constexpr int i = decltype(I)::value;
+          if (i < my_n) {
+            Fr za;
+            za.load(sb + (size_t)(n0 + i) * TB, lane);
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
-            if (j < my_k) Fr::mma(acc[i][j], za, xb[j]);
-          if (bias_mask & (1u << i)) {
-            if constexpr (BM) Fr::mma_ones(accb[i % NB], za, i, lane);
-            else bsum[i] = za.add_point_sum(bsum[i]);
+            for (int j = 0; j < 2; ++j)
+              if (j < my_k) Fr::mma(acc[i][j], za, xb[j]);
+            if (bias_mask & (1u << i)) bsum[i] = za.add_point_sum(bsum[i]);
           }
-        }
-      });
+        });
+      }
     }
 #ifdef HN_PROF
     if (prof_on) { HN_TS(t4_); tw += t1_ - t0_; tb += t2_ - t1_; ti += t3_ - t2_; tc += t4_ - t3_; }
@@ -1682,34 +1606,8 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
     o[5] = jb.n_nt * 16 + jb.n_kt; o[6] = bps; o[7] = blockIdx.x;
   }
 #endif
-#if defined(HN_WGRAD_EXP) && (HN_WGRAD_EXP == 1 || HN_WGRAD_EXP == 3)   // timing-only experiments (results are WRONG):
-  {                                                                     // 1 = no flush at all, 3 = no dW flush
-    float z = 0.0f;                                                     // (every accumulator stays live)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) z += acc[i][j][q];
-#if HN_WGRAD_EXP == 1
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) z += accb[i][q] + bsum[q & 3];
-#endif
-    if (z == 123.456f) grads[0] = z;
-  }
-#if HN_WGRAD_EXP == 1
-  hn_timeline_end(tab.timeline);
-  return;
-#endif
-#endif
   // D[n][k]: lane = column k (c), register q -> row rho(q,h)
-#if defined(HN_WGRAD_EXP) && HN_WGRAD_EXP == 3      // timing-only experiment: no dW flush (weight gradients are WRONG)
-  if (false) {
-#else
   if (jb.w_off >= 0 && partials != nullptr) {
-#endif
     // the rectangle leaves as raw accumulator tiles, 16 coalesced 256-B stores per tile (hn_mlp_wgrad_reduce sums the
     // jobs' slabs and adds every element to the gradient once): a CU retires float atomics at ~5 GB/s, plain stores
     // at its full store rate — the atomic flush was 100 us of a 650-us launch at config 2
@@ -1729,11 +1627,7 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
               *reinterpret_cast<f32x4*>(T + q4 * 256) = v;
             }
           }
-#if defined(HN_WGRAD_EXP) && HN_WGRAD_EXP == 3
-  } else if (false) {
-#else
   } else if (jb.w_off >= 0) {
-#endif
     float* G = grads + jb.w_off;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -1749,10 +1643,7 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
                 atomicAdd(G + (size_t)row * jb.ld + col, S8 ? acc[i][j][q] * tab.unscale : acc[i][j][q]);
             }
   }
-#if defined(HN_WGRAD_EXP) && HN_WGRAD_EXP == 2      // timing-only experiment: no bias flush (bias gradients are WRONG)
-  bias_mask = 0;
-#endif
-  if (!BM && bias_mask != 0) {
+  if (!S8 && bias_mask != 0) {
     // the two halves of the wave hold the sums over the two halves of every block's points: add them, lanes 0-31 hold
     // db of row (lane) of each dZ tile
     float* Bp = partials != nullptr ? partials + (size_t)(jb.p_tile + jb.n_nt * jb.n_kt) * 1024 : nullptr;
@@ -1768,15 +1659,15 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
           else if (row >= 0 && row < jb.r_end) atomicAdd(gb + row, v);
         }
       }
-  } else if (bias_mask != 0 && c < 4) {
+  } else if (bias_mask != 0 && c < 4) {      // 8-bit stash: column i of accb holds the sums of dZ tile i
     float* gb = grads + jb.b_off;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if ((bias_mask & (1u << i)) && c == (S8 ? i : 0))
+      if ((bias_mask & (1u << i)) && c == i)
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const int row = jb.r0 + 32 * (n0 + i) + (S8 ? hn_dw8_feature(hn_rho(q, h)) : hn_rho(q, h));
-          if (row >= 0 && row < jb.r_end) atomicAdd(gb + row, S8 ? accb[i % NB][q] * tab.unscale : accb[i % NB][q]);
+          const int row = jb.r0 + 32 * (n0 + i) + hn_dw8_feature(hn_rho(q, h));
+          if (row >= 0 && row < jb.r_end) atomicAdd(gb + row, accb[q] * tab.unscale);
         }
   }
 #ifdef HN_WGRAD_JOBTIMES
@@ -1793,290 +1684,6 @@ __global__ __launch_bounds__(512, 2) void hn_wgrad_kernel(const HnDwBatchTable t
 #endif
   hn_timeline_end(tab.timeline);
 }
-
-#ifdef HN_WGRAD_PERSIST
-// ------------------------------------------------------------------------------------------------
-// EXPERIMENT BUILD ONLY (-DHN_WGRAD_PERSIST=1; round 6, verdict item 3 — measured and CLOSED, profiles/r06_wgrad_persistent.md):
-// a persistent form of the weight-gradient launch.  It does what it was built for — per job, ramp 4.1 -> 1.5 us, workgroup
-// turnover 12.8 -> 0 us, 5.8 % of launch x CUs of idle time gone (tools/wg_jobtimes.py) — and the launch is no faster
-// (0.575 against 0.550 ms, same box, alternating): the stream is bound by the AGGREGATE HBM rate, a CU that pauses between
-// two jobs leaves its share to the others, and hiding the pause only stretches every job's own streaming time (0.855 ->
-// 0.907 of launch x CUs).  What is really lost is the idle tail behind each CU's last job (7-8 %), which this form does
-// not touch.  Not compiled into the product library.
-// The same weight-gradient jobs, PERSISTENT form (round 6; bf16 stash, 2-stage ring, block reads): one workgroup per CU
-// walks the host-ordered job list through a device ticket.  tools/wg_jobtimes.py (profiles/r06_wgrad_jobtimes.log) had put
-// numbers on what one-workgroup-per-job leaves on the table at config 2: 4.1 us of ramp per job (entry -> first stage
-// landed), 1.1 us of flush, and 12.8 us between a job's exit and the next workgroup's entry on the same CU (dispatch of a
-// 512-thread / 128-KiB workgroup + two dependent descriptor loads) = 7.2 % of launch x CUs.  Here the ring runs ACROSS
-// jobs: while the last stage of job j is being multiplied, the first stage of job j + 1 — claimed and its descriptor
-// loaded one job ahead — is already on its way into the other buffer (the slot tables of job j are dead once its last
-// stage has been issued, so they are re-decoded in place: no second set of registers), and the slab stores of job j drain
-// under it.  Same products, same slabs, same reduce: results bit-identical to hn_wgrad_kernel<true>.
-// ------------------------------------------------------------------------------------------------
-struct HnDwCur {           // what a job's stages and flush need of its descriptor + geometry: wave-uniform, 27 scalar registers
-  int bps, n0, k0, my_n, my_k, UB, nb, nstage, blk0, blk1, n_nt, n_kt;
-  int w_off, p_tile, b_off, r0, c0, r_end, c_end, ld;
-  unsigned zstride, xstride, x2stride, bias_mask;
-  const char* stash; float* grads; float* partials;
-};
-__global__ __launch_bounds__(512, 2) void hn_wgrad_persist_kernel(const HnDwBatchTable tab, unsigned* __restrict__ ticket,
-                                                                  int total) {
-  hn_timeline_begin(tab.timeline);
-  using Fr = DwFrag<true>;
-  constexpr int TU = ModeT<true>::TILE_UNITS;
-  constexpr int TBc = TU * 1024;
-  constexpr size_t TB = TBc;
-  constexpr int MAXSLOT = HN_WGRAD_MAXSLOT;
-  constexpr unsigned BUF = 8u * MAXSLOT * 1024u;      // bytes per ring buffer: fixed (jobs differ in their stage size)
-  constexpr unsigned TK = (unsigned)(TBc / 1024);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* s_next = reinterpret_cast<int*>(smem + 2 * BUF);      // two words behind the ring (dynamic LDS: 2 x BUF + 64)
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int c = lane & 31, h = lane >> 5;
-  const int G = (int)gridDim.x;
-  int tro0 = 0, tro1 = 0;
-  hn_dw_tr_offsets(lane, tro0, tro1);
-
-  // per-wave LDS-DMA slots of one stage (hn_wgrad_kernel's tables)
-  unsigned sbase[MAXSLOT];
-  int sinfo[MAXSLOT];
-  // job `g` of the launch's global order: its descriptor is read, boiled down to `q` (geometry of this wave, flush
-  // destination, batch pointers) and to the slot tables — the descriptor itself is dead afterwards
-  auto prepare = [&](int g, HnDwCur& q) __attribute__((always_inline)) {
-    int job_id = g, which = 0;
-    if (tab.order != nullptr) {
-      const int o = __builtin_amdgcn_readfirstlane(tab.order[g]);
-      which = o >> 24;
-      job_id = o & 0xffffff;
-    } else {
-#pragma unroll
-      for (int i = 0; i < HN_MAX_WGRAD_BATCH - 1; ++i)
-        if (which == i && i + 1 < tab.n && job_id >= tab.b[i].n_jobs) { job_id -= tab.b[i].n_jobs; which = i + 1; }
-    }
-    const HnDwJob* jobs = tab.b[0].jobs;
-    q.stash = reinterpret_cast<const char*>(tab.b[0].stash); q.grads = tab.b[0].grads; q.partials = tab.b[0].partials;
-#pragma unroll
-    for (int i = 1; i < HN_MAX_WGRAD_BATCH; ++i)
-      if (which == i) { jobs = tab.b[i].jobs; q.stash = reinterpret_cast<const char*>(tab.b[i].stash); q.grads = tab.b[i].grads; q.partials = tab.b[i].partials; }
-    const HnDwJob jd = jobs[job_id];
-    const int gn = jd.pad & 255, gk = (jd.pad >> 8) & 255;
-    q.bps = (jd.pad >> 16) & 255;
-    const int tn = (jd.n_nt + gn - 1) / gn, tk = (jd.n_kt + gk - 1) / gk;
-    const int wn = wave / gk, wk = wave % gk;
-    q.n0 = wn * tn; q.k0 = wk * tk;
-    q.my_n = wn < gn ? min(tn, jd.n_nt - q.n0) : 0;
-    q.my_k = min(tk, jd.n_kt - q.k0);
-    q.UB = TU * (jd.n_nt + jd.n_kt);
-    q.nb = jd.blk1 - jd.blk0;
-    q.nstage = (q.nb + q.bps - 1) / q.bps;
-    q.blk0 = jd.blk0; q.blk1 = jd.blk1; q.n_nt = jd.n_nt; q.n_kt = jd.n_kt;
-    q.w_off = jd.w_off; q.p_tile = jd.p_tile; q.b_off = jd.b_off; q.r0 = jd.r0; q.c0 = jd.c0; q.r_end = jd.r_end;
-    q.c_end = jd.c_end; q.ld = jd.ld;
-    q.zstride = (unsigned)jd.z_nt * TK; q.xstride = (unsigned)jd.x_nt * TK; q.x2stride = (unsigned)jd.x2_nt * TK;
-    q.bias_mask = 0;
-    if (jd.b_off >= 0 && q.my_n > 0)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < q.my_n && (i % gk) == wk) q.bias_mask |= 1u << i;
-#pragma unroll
-    for (int i = 0; i < MAXSLOT; ++i) {
-      const int qq = wave + 8 * i;
-      sinfo[i] = 1 << 30;
-      sbase[i] = 0;
-      if (qq < q.bps * q.UB) {
-        const int bi = qq / q.UB, r = qq % q.UB;
-        const int tile = r / TU, u = r % TU;
-        const bool isz = tile < jd.n_nt;
-        const int kt = tile - jd.n_nt;
-        const bool isx2 = !isz && kt >= jd.n_kt1;
-        const unsigned rel = isz ? ((unsigned)bi * jd.z_nt + jd.z_t0 + tile) * TK
-                           : isx2 ? ((unsigned)bi * jd.x2_nt + jd.x2_t0 + (kt - jd.n_kt1)) * TK
-                                  : ((unsigned)bi * jd.x_nt + jd.x_t0 + kt) * TK;
-        sbase[i] = (unsigned)((isz ? jd.z_off : (isx2 ? jd.x2_off : jd.x_off)) >> 10) + rel + (unsigned)u;
-        sinfo[i] = bi << 2 | (isz ? 1 : (isx2 ? 2 : 0));
-      }
-    }
-  };
-  // stage `s` of job `q` (whose tables are the decoded ones) into ring buffer `buf`
-  auto issue = [&](const HnDwCur& q, int s, int buf) __attribute__((always_inline)) {
-    char* dst = smem + (size_t)buf * BUF;
-    const int b0 = q.blk0 + s * q.bps;
-    const int nblk_s = min(q.bps, q.blk1 - b0);
-#pragma unroll
-    for (int i = 0; i < MAXSLOT; ++i) {
-      if ((sinfo[i] >> 2) < nblk_s) {
-        const unsigned kind = sinfo[i] & 3;
-        const char* src = q.stash + ((unsigned long long)(sbase[i] + (unsigned)b0 * (kind == 1 ? q.zstride : (kind == 2 ? q.x2stride : q.xstride))) << 10);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane * 16),
-                                         (__attribute__((address_space(3))) void*)(dst + (wave + 8 * i) * 1024), 16, 0,
-                                         HN_WGRAD_AUX);
-      }
-    }
-  };
-
-  if ((int)blockIdx.x >= total) {       // (the host never launches more workgroups than jobs)
-    hn_timeline_end(tab.timeline);
-    return;
-  }
-  HnDwCur cj, nj;                       // current job, next job
-  prepare((int)blockIdx.x, cj);         // this workgroup's first job: one per workgroup, the tickets hand out the rest
-  int rb = 0;                           // ring buffer of the current job's stage 0
-  issue(cj, 0, rb);
-  int parity = 0;
-#ifdef HN_WGRAD_JOBTIMES
-  long long* jt_buf = (long long*)tab.b[HN_MAX_WGRAD_BATCH - 1].jobs;
-  const bool jt_on = jt_buf != nullptr && tab.n < HN_MAX_WGRAD_BATCH && threadIdx.x == 0;
-  int jt_idx = (int)blockIdx.x;
-  unsigned long long jt_prev_end = wall_clock64();
-#endif
-  for (;;) {
-#ifdef HN_WGRAD_JOBTIMES
-    unsigned long long jt0 = jt_prev_end, jt1 = 0, jt2 = 0;
-#endif
-    // The job after this one is claimed LATE — one stage before its descriptor is needed (stage nstage - 3's products hide
-    // the atomic, stage nstage - 2 publishes it through LDS) —: a claim at the start of the job turned the ticket into a
-    // round-robin assignment (every workgroup holds two jobs, a third of the list is handed out blind) and the launch ran
-    // 12 % LONGER than one workgroup per job (profiles/r06_wgrad_persist_ab.log).
-    const int s_pub = max(0, cj.nstage - 2);
-    unsigned tk_raw = 0;
-    if (s_pub == 0 && threadIdx.x == 0) tk_raw = atomicAdd(ticket, 1u);
-    int nxt = total;
-    bool prepared = false;
-    f32x16 acc[4][2];
-    float bsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-    for (int s = 0; s < cj.nstage; ++s) {
-      // stage s has landed: everything this wave issued is older than it or it (2-stage ring: nothing younger in flight)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (s == s_pub && threadIdx.x == 0) s_next[parity] = G + (int)tk_raw;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_sched_barrier(0);
-#ifdef HN_WGRAD_JOBTIMES
-      if (jt_on && s == 0) jt1 = wall_clock64();
-#endif
-      if (s == s_pub) nxt = __builtin_amdgcn_readfirstlane(s_next[parity]);
-      if (s + 1 == s_pub && threadIdx.x == 0) tk_raw = atomicAdd(ticket, 1u);
-      if (s + 1 < cj.nstage) {
-        issue(cj, s + 1, (rb + s + 1) & 1);
-      }
-      if (s + 2 >= cj.nstage && !prepared && nxt < total) {
-        // the current job's slot tables are dead — its last stage has been issued (or is the one in LDS): the next job's
-        // descriptor is read and decoded in place, one stage before it is needed where the job has two or more
-        prepare(nxt, nj);
-        prepared = true;
-      }
-      if (s + 1 >= cj.nstage && prepared) issue(nj, 0, (rb + s + 1) & 1);      // into the buffer stage s - 1 has just released
-      const char* st = smem + (size_t)((rb + s) & 1) * BUF;
-      const int nblk_s = min(cj.bps, cj.nb - s * cj.bps);
-      for (int bi = 0; bi < nblk_s; ++bi) {
-        const char* sb = st + (size_t)bi * cj.UB * 1024;
-        const unsigned a_blk = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)sb;
-        const unsigned ax = a_blk + (unsigned)((cj.n_nt + cj.k0) * TB), az = a_blk + (unsigned)(cj.n0 * TB);
-        Fr xb[2], za[4];
-        bf16x8 xv[2][2], zv[4][2];
-        if (cj.my_n > 2) hn_tr_block<4>(xv, zv, ax + tro0, ax + tro1, az + tro0, az + tro1);
-        else hn_tr_block<2>(xv, zv, ax + tro0, ax + tro1, az + tro0, az + tro1);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) { xb[j].v[0] = xv[j][0]; xb[j].v[1] = xv[j][1]; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { za[i].v[0] = zv[i][0]; za[i].v[1] = zv[i][1]; }
-        static_for4([&](auto I) __attribute__((always_inline)) {
-          constexpr int i = decltype(I)::value;
-          if (i < cj.my_n) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-              if (j < cj.my_k) Fr::mma(acc[i][j], za[i], xb[j]);
-            if (cj.bias_mask & (1u << i)) bsum[i] = za[i].add_point_sum(bsum[i]);
-          }
-        });
-      }
-    }
-#ifdef HN_WGRAD_JOBTIMES
-    if (jt_on) jt2 = wall_clock64();
-#endif
-    // ---- flush of the current job (hn_wgrad_kernel's: partial slabs or float atomics) ----
-    if (cj.w_off >= 0 && cj.partials != nullptr) {
-      float* P = cj.partials + (size_t)cj.p_tile * 1024;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < cj.my_n)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            if (j < cj.my_k) {
-              float* T = P + (size_t)((cj.n0 + i) * cj.n_kt + (cj.k0 + j)) * 1024 + lane * 4;
-#pragma unroll
-              for (int q4 = 0; q4 < 4; ++q4) {
-                const f32x4 v = {acc[i][j][4 * q4], acc[i][j][4 * q4 + 1], acc[i][j][4 * q4 + 2], acc[i][j][4 * q4 + 3]};
-                *reinterpret_cast<f32x4*>(T + q4 * 256) = v;
-              }
-            }
-    } else if (cj.w_off >= 0) {
-      float* Gw = cj.grads + cj.w_off;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < cj.my_n)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            if (j < cj.my_k)
-#pragma unroll
-              for (int q = 0; q < 16; ++q) {
-                const int row = cj.r0 + 32 * (cj.n0 + i) + hn_rho(q, h);
-                const int col = cj.c0 + 32 * (cj.k0 + j) + c;
-                if (row >= 0 && col >= 0 && row < cj.r_end && col < cj.c_end) atomicAdd(Gw + (size_t)row * cj.ld + col, acc[i][j][q]);
-              }
-    }
-    if (cj.bias_mask != 0) {
-      float* Bp = cj.partials != nullptr ? cj.partials + (size_t)(cj.p_tile + cj.n_nt * cj.n_kt) * 1024 : nullptr;
-      float* gb = cj.grads + cj.b_off;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (cj.bias_mask & (1u << i)) {
-          const float v = bsum[i] + __shfl_xor(bsum[i], 32, 64);
-          const int row = cj.r0 + 32 * (cj.n0 + i) + c;
-          if (h == 0) {
-            if (Bp != nullptr) Bp[(cj.n0 + i) * 32 + c] = v;
-            else if (row >= 0 && row < cj.r_end) atomicAdd(gb + row, v);
-          }
-        }
-    }
-#ifdef HN_WGRAD_JOBTIMES
-    if (jt_on) {
-      unsigned hw = 0, xcc = 0;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      long long* o = jt_buf + (size_t)jt_idx * 8;
-      jt_prev_end = wall_clock64();
-      o[0] = (long long)hw | ((long long)(xcc & 15u) << 32);
-      o[1] = (long long)jt0; o[2] = (long long)jt1; o[3] = (long long)jt2; o[4] = (long long)jt_prev_end;
-      o[5] = (long long)cj.nb * cj.UB * 1024; o[6] = cj.n_nt * 16 + cj.n_kt; o[7] = 1;
-    }
-    jt_idx = nxt;
-#endif
-    if (!prepared) break;
-    rb = (rb + cj.nstage) & 1;
-    cj = nj;
-    parity ^= 1;
-  }
-  // the workgroup that leaves last re-arms the tickets for the next launch
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(ticket + 1, 1u) == (unsigned)G - 1) {
-      ticket[0] = 0u;
-      ticket[1] = 0u;
-    }
-  }
-  hn_timeline_end(tab.timeline);
-}
-
-#endif  // HN_WGRAD_PERSIST
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -2107,11 +1714,11 @@ extern "C" int hn_abi_sizes(int32_t* out, int n) {
 // the same values as text inside the binary: a host that must know them BEFORE it may dlopen the library (Python's import
 // of the package, which a rebuild can follow) finds them by scanning the file for the marker
 extern "C" __attribute__((used)) const char hn_build_config_text[] =
-    "HN_BUILD_CONFIG:" HN_STR(HN_WGRAD_STAGES) "," HN_STR(HN_WGRAD_MAXSLOT) "," HN_STR(HN_WGRAD_BIAS_MFMA) "," HN_STR(HN_CHUNK_UNITS) ","
-    HN_STR(HN_WGRAD_BLOCK) "," HN_STR(HN_WSTREAM_ASYM) "," HN_STR(HN_BF16_WAVES) "," HN_STR(HN_WGRAD_AUX) ";";
+    "HN_BUILD_CONFIG:" HN_STR(HN_WGRAD_STAGES) "," HN_STR(HN_WGRAD_MAXSLOT) ",0," HN_STR(HN_CHUNK_UNITS) ",1,1,"
+    HN_STR(HN_BF16_WAVES) "," HN_STR(HN_WGRAD_AUX) ";";
 extern "C" int hn_build_config(int32_t* out, int n) {
-  const int32_t v[HN_BUILD_CONFIG_N] = {HN_WGRAD_STAGES, HN_WGRAD_MAXSLOT, HN_WGRAD_BIAS_MFMA, HN_CHUNK_UNITS,
-                                        HN_WGRAD_BLOCK,  HN_WSTREAM_ASYM,  HN_BF16_WAVES,      HN_WGRAD_AUX};
+  const int32_t v[HN_BUILD_CONFIG_N] = {HN_WGRAD_STAGES, HN_WGRAD_MAXSLOT, 0, HN_CHUNK_UNITS,
+                                        1,               1,                HN_BF16_WAVES, HN_WGRAD_AUX};
   for (int i = 0; i < n && i < HN_BUILD_CONFIG_N; ++i) out[i] = v[i];
   return HN_BUILD_CONFIG_N;
 }
@@ -2126,9 +1733,6 @@ static void hn_allow_big_lds() {
   done[dev] = true;
   const int big = 160 * 1024;
 #define HN_BIG(k) (void)hipFuncSetAttribute((const void*)(k), hipFuncAttributeMaxDynamicSharedMemorySize, big)
-#ifdef HN_WGRAD_PERSIST
-  HN_BIG(hn_wgrad_persist_kernel);
-#endif
   HN_BIG((hn_mlp_fwd_kernel<true, 2, false, true>)); HN_BIG((hn_mlp_fwd_kernel<true, 2, false, false>));
   HN_BIG((hn_mlp_fwd_kernel<true, 2, true, true>)); HN_BIG((hn_mlp_fwd_kernel<true, 2, true, false>));
   HN_BIG((hn_mlp_fwd_kernel<true, 3, false, true>)); HN_BIG((hn_mlp_fwd_kernel<true, 3, false, false>));
@@ -2353,11 +1957,7 @@ __global__ __launch_bounds__(256 * HN_REDUCE_SPLIT) void hn_wgrad_reduce_kernel(
       hn_adam_update(K, A.p[i], g, A.m[i], A.v[i]);
       *Gp = A.zero_grad ? 0.0f : g;
     } else {
-#if defined(HN_REDUCE_ATOMIC) && HN_REDUCE_ATOMIC
-      atomicAdd(Gp, add);
-#else
       *Gp += add;      // one writer per element in this launch, every other launch is ordered before or behind it
-#endif
     }
   };
   // (with HN_REDUCE_SPLIT > 1 the table-row, bias and rest paths run on the first 256 threads; every barrier below is
@@ -2382,11 +1982,7 @@ __global__ __launch_bounds__(256 * HN_REDUCE_SPLIT) void hn_wgrad_reduce_kernel(
     const int lane = threadIdx.x & 63, wave = (threadIdx.x >> 6) & 3;
     float colsum = 0.0f;          // lanes c < dim: column c of this wave's programs
     int* mlist = s_match[wave];
-#ifdef HN_REDUCE_EXP_NOEMBED      /* timing-only experiment: the table rows do no work (their gradient is WRONG) */
-    for (int sIdx = wave; first256 && sIdx < 0; sIdx += 4) {
-#else
     for (int sIdx = wave; first256 && sIdx < em.n_src; sIdx += 4) {
-#endif
       const float* __restrict__ P = em.partial[sIdx];
       const int64_t* __restrict__ idx = em.idx[sIdx];
       const int nb = em.n_blocks[sIdx], spr = em.samples_per_ray[sIdx];
@@ -2572,11 +2168,7 @@ __global__ __launch_bounds__(256 * HN_REDUCE_SPLIT) void hn_wgrad_reduce_kernel(
           g4[j] += tot[j];
           hn_adam_update(K, p4[j], g4[j], m4[j], v4[j]);
         } else {
-#if defined(HN_REDUCE_ATOMIC) && HN_REDUCE_ATOMIC
-          atomicAdd(gp[j], tot[j]);
-#else
           *gp[j] += tot[j];
-#endif
         }
       }
       if (ADAM) {
@@ -2711,36 +2303,8 @@ extern "C" int hn_mlp_wgrad_batched(int mode, const HnDwBatch* batches, int n_ba
   return hn_mlp_wgrad_batched_t(mode, batches, n_batches, order_dev, nullptr, stream);
 }
 
-static int hn_cu_count() {
-  static int cus[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
-
-static int hn_wgrad_batched_impl(int mode, const HnDwBatch* batches, int n_batches, const int32_t* order_dev,
-                                 uint64_t* timeline_dev, uint32_t* ticket_dev, hnStream_t stream);
-
 extern "C" int hn_mlp_wgrad_batched_t(int mode, const HnDwBatch* batches, int n_batches, const int32_t* order_dev,
                                       uint64_t* timeline_dev, hnStream_t stream) {
-  return hn_wgrad_batched_impl(mode, batches, n_batches, order_dev, timeline_dev, nullptr, stream);
-}
-
-#ifdef HN_WGRAD_PERSIST
-extern "C" int hn_mlp_wgrad_batched_p(int mode, const HnDwBatch* batches, int n_batches, const int32_t* order_dev,
-                                      uint64_t* timeline_dev, uint32_t* ticket_dev, hnStream_t stream) {
-  if (ticket_dev == nullptr) return -3;
-  return hn_wgrad_batched_impl(mode, batches, n_batches, order_dev, timeline_dev, ticket_dev, stream);
-}
-#endif
-
-static int hn_wgrad_batched_impl(int mode, const HnDwBatch* batches, int n_batches, const int32_t* order_dev,
-                                 uint64_t* timeline_dev, uint32_t* ticket_dev, hnStream_t stream) {
   if (hn_wgrad_stage_check(mode) != 0) return -8;
   if (n_batches < 0 || n_batches > HN_MAX_WGRAD_BATCH) return -1;
   if (n_batches > 0 && batches == nullptr) return -3;
@@ -2763,19 +2327,5 @@ static int hn_wgrad_batched_impl(int mode, const HnDwBatch* batches, int n_batch
 #endif
   if (total == 0) return 0;
   if (total > 0x7fffffffLL) return -2;
-#ifdef HN_WGRAD_PERSIST
-  // the persistent form exists for the bf16 stash on the 2-stage ring with block reads (the product's build)
-  if (ticket_dev != nullptr && (mode & 255) == HN_MODE_BF16 && HN_WGRAD_STAGES == 2 && HN_WGRAD_BLOCK != 0 && !HN_WGRAD_BIAS_MFMA) {
-    hn_allow_big_lds();
-    const size_t lds = (size_t)2 * 8 * HN_WGRAD_MAXSLOT * 1024 + 64;
-    if (lds > 160 * 1024) return -8;
-    const int cus = hn_cu_count();
-    const int grid = total < cus ? (int)total : cus;      // one workgroup per CU (128 KiB of LDS each)
-    hipLaunchKernelGGL(hn_wgrad_persist_kernel, dim3(grid), dim3(512), lds, (hipStream_t)stream, tab, ticket_dev, (int)total);
-    HN_CHECK_LAUNCH();
-    return 0;
-  }
-#endif
-  (void)ticket_dev;
   return hn_launch_wgrad(mode, tab, (int)total, stream);
 }

@@ -30,7 +30,6 @@ import torch
 from . import _lib as L
 
 CHUNK = L.HN_CHUNK_UNITS
-_FORCE_WIDE = os.environ.get("HN_FORCE_WIDE", "0") == "1"
 
 
 def pow2ceil(n: int) -> int:
@@ -423,9 +422,9 @@ class Program:
         word = 0
         for tt in range(2):
             fts = [f for f in ly.aux.feats[64 * g + 32 * tt:64 * g + 32 * tt + 32] if f.need_grad]
-            if fts or not AUX_TILE_SKIP:
+            if fts:
                 word |= 1 << tt
-            if any(f.kind not in (L.HN_FEAT_ID, L.HN_FEAT_ZERO) for f in fts) or AUX_TILE_SKIP < 2:
+            if any(f.kind not in (L.HN_FEAT_ID, L.HN_FEAT_ZERO) for f in fts):
                 word |= 256 << tt
         return word
 
@@ -669,12 +668,13 @@ class Program:
 
     @staticmethod
     def _wave_grid(n_nt: int, n_kt: int, one_row: bool = False) -> Tuple[int, int]:
-        """(gn, gk), gn*gk <= 8 waves, every wave's rectangle <= 4x2 tiles.  `one_row`: the grids of rounds 1-3."""
-        if WGRAD_GRID == 0 or one_row:   # one row of waves for <= 4 dZ tiles (a 4x4 job runs on 4 of its 8 waves)
+        """(gn, gk), gn*gk <= 8 waves, every wave's rectangle <= 4x2 tiles.  `one_row`: fewer, larger rectangles (fp32
+        at full batch sizes, see wgrad_jobs)."""
+        if one_row:   # one row of waves for <= 4 dZ tiles (a 4x4 job runs on 4 of its 8 waves)
             if n_nt <= 4:
                 return 1, min(8, max(1, n_kt)) if n_kt <= 8 else 8
             return 2, 4
-        # round 4: as many ACTIVE waves as the rectangle admits (a wave without a tile only issues DMA; with one
+        # as many ACTIVE waves as the rectangle admits (a wave without a tile only issues DMA; with one
         # active wave per SIMD nothing hides its LDS read latencies), then the smallest rectangle per wave, then the
         # fewest operand tiles read per block over all waves
         best = None
@@ -709,7 +709,7 @@ class Program:
             # with two X slots when it fits a job (<= 8 k-tiles): its dZ tiles are then read once, not once per
             # segment (round 4: the launch is HBM-bound, every byte counts — 3.6 % of its reads at config 2)
             x2 = None
-            if (WGRAD_FUSE_SEGS and bf16_like(mode) and len(segs) == 2 and segs[0][2] == 0 and segs[0][3] % 32 == 0
+            if (bf16_like(mode) and len(segs) == 2 and segs[0][2] == 0 and segs[0][3] % 32 == 0
                     and segs[1][2] == segs[0][3] and segs[0][3] // 32 + (segs[1][3] + 31) // 32 <= tmax):
                 x2 = (segs[1][0], segs[1][1], segs[0][3] // 32)          # (offset, tiles per block, k-tiles of slot 1)
                 segs = [(segs[0][0], segs[0][1], 0, segs[0][3] + segs[1][3])]
@@ -768,15 +768,13 @@ class Program:
                 # Jobs of big rectangles therefore stream as much as one CU's share of the whole launch allows (ONE
                 # flush per CU and rectangle; measured at config 2, same box: 12.5-15 MiB jobs 0.661-0.668 ms against
                 # 0.717-0.725 ms with 5 MiB, 20 MiB 0.835 ms: one job longer than the launch), jobs of small ones
-                # fewer (they fill the tail of the launch): WGRAD_JOB_SCALE / `launch_bytes`
+                # fewer (they fill the tail of the launch): `launch_bytes`
                 big, small = n_nt * n_kt >= 48, n_nt * n_kt < 12
                 share_cu = (launch_bytes if launch_bytes else total_tiles * nblk * tile_bytes) / N_CUS
                 # round 5: the base size grows with the launch — a CU never gets more than ~WGRAD_JOBS_PER_CU (16) mid-sized
                 # jobs (config 3 streams 266 MB per CU: 5-MiB jobs were 50 flushes per CU, and 0.5 ms of slab reduction)
-                base = max(job_bytes, share_cu / WGRAD_JOBS_PER_CU) if WGRAD_JOBS_PER_CU > 0 else job_bytes
-                if WGRAD_JOB_SCALE is not None:
-                    jb = job_bytes * WGRAD_JOB_SCALE[0 if big else (2 if small else 1)]
-                elif big:
+                base = max(job_bytes, share_cu / WGRAD_JOBS_PER_CU)
+                if big:
                     jb = min(max(0.85 * share_cu, base), WGRAD_BIG_CAP * base)
                 else:
                     jb = base * (0.5 if small else 1.0)
@@ -832,20 +830,11 @@ def wgrad_mode_word(mode: int) -> int:
     return mode | (DZ_SCALE_LOG2 << 8) if mode == L.HN_MODE_BF16_S8 else mode | (WGRAD_STAGE_KB << 8)
 
 
-# job size relative to WGRAD_JOB_BYTES for rectangles of >= 48 / >= 12 / fewer tiles (see wgrad_jobs)
-# HN_WGRAD_JOB_SCALE="a,b,c" pins them (A/B runs: "1,1,1" = rounds 1-3); default: sized from the launch's bytes
-WGRAD_JOB_SCALE = (tuple(float(x) for x in os.environ["HN_WGRAD_JOB_SCALE"].split(","))
-                   if os.environ.get("HN_WGRAD_JOB_SCALE") else None)
 N_CUS = 256                      # MI355X
-# backward feature-gradient ops: 2 = only tiles with a differentiable feature, no chain-rule factor on identity-only tiles;
-# 1 = only the tile skip; 0 = every tile of a group with a gradient (rounds 1-3)
-AUX_TILE_SKIP = int(os.environ.get("HN_AUX_TILE_SKIP", 2))
 # LDS stage of hn_wgrad_kernel's ring (bf16 / fp32 builds), KiB: as large as the build's ring allows (2 x 64 KiB; A/B knob)
 WGRAD_STAGE_KB = min(int(os.environ.get("HN_WGRAD_STAGE_KB") or L.WGRAD_MAX_STAGE_KB), L.WGRAD_MAX_STAGE_KB)
-WGRAD_JOBS_PER_CU = float(os.environ.get("HN_WGRAD_JOBS_PER_CU", 16.0))   # 0: the base job size never grows with the launch (round 4)
+WGRAD_JOBS_PER_CU = 16            # mid-sized jobs per CU at most: the base job size grows with the launch (wgrad_jobs)
 WGRAD_BIG_CAP = float(os.environ.get("HN_WGRAD_BIG_CAP", 8.0))     # largest job of a big rectangle, in units of WGRAD_JOB_BYTES
-WGRAD_FUSE_SEGS = int(os.environ.get("HN_WGRAD_FUSE_SEGS", 1))     # 0: one job per input segment of a skip layer (rounds 1-3)
-WGRAD_GRID = int(os.environ.get("HN_WGRAD_GRID", 1))       # 0: the wave grids of rounds 1-3 (Program._wave_grid)
 WGRAD_TAIL_FRAC = float(os.environ.get("HN_WGRAD_TAIL_FRAC", 0.4))   # lightest 40 % of the jobs are halved: -1.8 % step time at config 2
 WGRAD_TAIL_PARTS = int(os.environ.get("HN_WGRAD_TAIL_PARTS", 2))
 WGRAD_JOB_BYTES = int(float(os.environ.get("HN_WGRAD_JOB_MB", 5)) * (1 << 20))     # stash bytes one job of a batched weight-gradient launch streams (~3 jobs per CU
@@ -893,7 +882,6 @@ class ResolvedWgrad:
 # (HnDwBatch.partials) and ONE more launch (hn_mlp_wgrad_reduce, a workgroup per destination tile) sums the slabs and adds
 # every gradient element once: 1/12 of the atomics, and sums whose order no longer depends on which job finished first.
 WGRAD_PARTIALS = int(os.environ.get("HN_WGRAD_PARTIALS", 1))
-BIAS_MFMA_BUILD = L.WGRAD_BIAS_MFMA      # A/B build: bias by all-ones MFMAs + atomics (asked of the library: hn_build_config)
 _UID = itertools.count(1)
 _ORPHAN_GROUP_CACHE: Dict[tuple, tuple] = {}      # shares built without an owner (tests that assemble ResolvedWgrad by hand)
 
@@ -950,7 +938,7 @@ def _reduce_tables(grp: Sequence["ResolvedWgrad"], device):
         for ji in range(len(jb)):
             j = jb[ji]
             n_nt, n_kt = int(j["n_nt"]), int(j["n_kt"])
-            if j["b_off"] >= 0 and p.mode != L.HN_MODE_BF16_S8 and not BIAS_MFMA_BUILD:     # bias record (ld = 0): the job's extra slab tile
+            if j["b_off"] >= 0 and p.mode != L.HN_MODE_BF16_S8:     # bias record (ld = 0): the job's extra slab tile
                 key = (gptr, int(j["b_off"]), 0, int(j["r0"]), n_nt, int(j["r_end"]), 0)
                 dest.setdefault(key, [k]).append((k << 28) | (int(j["p_tile"]) + n_nt * n_kt))
             if j["w_off"] < 0:
@@ -1112,27 +1100,6 @@ WGRAD_SPLIT_OFFSET: Optional[int] = None
 HELD_JOB_DIV = int(os.environ.get("HN_HELD_JOB_DIV", 6))
 
 
-# EXPERIMENT builds only (-DHN_WGRAD_PERSIST=1 exports hn_mlp_wgrad_batched_p): the persistent weight-gradient launch of
-# round 6 — measured, no gain, closed (profiles/r06_wgrad_persistent.md); the product library does not carry it
-WGRAD_PERSISTENT = os.environ.get("HN_WGRAD_PERSISTENT", "0") != "0"
-_TICKETS: Dict[tuple, torch.Tensor] = {}
-
-
-def _wgrad_tickets(device) -> torch.Tensor:
-    """The persistent weight-gradient launch's job ticket + exit counter: two zeroed uint32 per (device, stream) — the
-    kernel re-arms them itself, launches that share a pair must be stream-ordered."""
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-    t = _TICKETS.get(key)
-    if t is None:
-        if torch.cuda.is_current_stream_capturing():
-            key0 = next((k for k in _TICKETS if k[0] == str(device)), None)
-            if key0 is None:
-                raise L.HnError("persistent weight gradient: tickets first needed inside a stream capture (run a warm-up step)")
-            return _TICKETS[key0]      # a capture on a side stream: it replays in the order of its warm-up, one launch at a time
-        t = _TICKETS[key] = torch.zeros(2, dtype=torch.int32, device=device)
-    return t
-
-
 def resolve_pending(pending: Sequence[PendingWgrad]) -> List[ResolvedWgrad]:
     """Cut the shares of ONE launch into jobs.  The launch's bytes — the sum over the programs queued for it, first
     bucket only when the pass is split — size the jobs of big rectangles (one flush of a dW rectangle per CU);
@@ -1195,16 +1162,9 @@ def launch_resolved_wgrads(shares: Sequence[ResolvedWgrad]):
                         raise L.HnError("weight-gradient reduce tables: first use of this set of programs inside a stream "
                                         "capture (run one warm-up step of the same shapes first)")
                     red = cache[rkey] = _reduce_tables(grp, grp[0].stash.device)
-            if WGRAD_PERSISTENT and mode == L.HN_MODE_BF16 and hasattr(L.load(), "hn_mlp_wgrad_batched_p"):
-                # one workgroup per CU walking the job list (hn_wgrad_persist_kernel): the next job's first stage in flight
-                # under the current job's last products and flush
-                L.launch("hn_mlp_wgrad_batched_p", C.c_int(wgrad_mode_word(mode)), arr, C.c_int(len(grp)), L.ptr(order),
-                         C.c_void_p(L.timeline_slot("hn_mlp_wgrad_batched", grp[0].stash.device)),
-                         L.ptr(_wgrad_tickets(grp[0].stash.device)), L.stream_handle(), tag="batched")
-            else:
-                L.launch("hn_mlp_wgrad_batched_t", C.c_int(wgrad_mode_word(mode)), arr, C.c_int(len(grp)), L.ptr(order),
-                         C.c_void_p(L.timeline_slot("hn_mlp_wgrad_batched", grp[0].stash.device)), L.stream_handle(),
-                         tag="batched")
+            L.launch("hn_mlp_wgrad_batched_t", C.c_int(wgrad_mode_word(mode)), arr, C.c_int(len(grp)), L.ptr(order),
+                     C.c_void_p(L.timeline_slot("hn_mlp_wgrad_batched", grp[0].stash.device)), L.stream_handle(),
+                     tag="batched")
             embeds = [p.embed for p in grp if p.embed is not None]
             by_table: Dict[int, list] = {}
             for e in embeds:
@@ -1384,10 +1344,9 @@ class MlpRunner:
         a.prof = L.PROF_BUFFER.data_ptr() if L.PROF_BUFFER is not None else 0
         a.timeline = L.timeline_slot(f"{kind}[{self.prog.name}]", d.bias.device)
         a.comps, a.n_comps = d.comps.data_ptr(), len(self.prog.comp_map)
-        # (HN_FORCE_WIDE=1: A/B knob — take the kernel build that carries the wide ops although the program has none)
-        wide = any(ly.out is not None and ly.out.wide for ly in self.prog.layers) or _FORCE_WIDE
+        wide = any(ly.out is not None and ly.out.wide for ly in self.prog.layers)
         direct = any(f.kind != L.HN_FEAT_ZERO and (f.src, f.comp) not in self.prog.comp_map for f in self.prog.feat_table)
-        a.wide_ops = (1 if wide else 0) | (2 if (direct or _FORCE_WIDE) else 0)
+        a.wide_ops = (1 if wide else 0) | (2 if direct else 0)
         a.dz_scale_log2 = DZ_SCALE_LOG2 if mode == L.HN_MODE_BF16_S8 else 0
         a.n_trig_comps = min(len(self.prog.comp_map), max(1, self.prog.n_trig_comps))
         # hi + lo planes of x / 2pi for the encoded components when the forward's LDS budget allows (158 KiB: ring +
@@ -1449,7 +1408,7 @@ class MlpRunner:
         """HN_MODE_BF16_S8 exists in the render-level kernel builds only: a program with stand-alone-module paths (wide
         outputs, directly read identity features) runs, stash included, in plain HN_MODE_BF16."""
         if mode == L.HN_MODE_BF16_S8:
-            wide = any(ly.out is not None and ly.out.wide for ly in self.prog.layers) or _FORCE_WIDE
+            wide = any(ly.out is not None and ly.out.wide for ly in self.prog.layers)
             direct = any(f.kind != L.HN_FEAT_ZERO and (f.src, f.comp) not in self.prog.comp_map
                          for f in self.prog.feat_table)
             if wide or direct:

@@ -252,10 +252,11 @@ int hn_version(void);
  * HnCompositeArgs, HnFeat, HnSlot, HnSrc — lets a foreign-language binding verify its mirror. */
 int hn_abi_sizes(int32_t* out, int n);
 /* The build-time tuning knobs of THIS library (ABI 340): out[0..] = ring depth and LDS-DMA pieces per wave and stage of
- * hn_wgrad_kernel, bias-by-MFMA build (0/1), weight-stream chunk in units, block-read build (0/1), asymmetric weight-stream
- * issue (0/1), waves per workgroup of the bf16 machines, cache policy of the stash stream.  Returns the number of
- * entries.  A binding derives its host-side mirrors (job stage cuts, chunk alignment, reduce tables) from these instead of
- * assuming the defaults. */
+ * hn_wgrad_kernel, bias-by-MFMA build, weight-stream chunk in units, block-read build, asymmetric weight-stream issue,
+ * waves per workgroup of the bf16 machines, cache policy of the stash stream.  Entries 2, 4 and 5 are fixed at 0, 1 and 1
+ * (those alternatives are no longer built); they keep their slots so that the layout stays the same.  Returns the number
+ * of entries.  A binding derives its host-side mirrors (job stage cuts, chunk alignment, reduce tables) from these
+ * instead of assuming the defaults. */
 #define HN_BUILD_CONFIG_N 8
 int hn_build_config(int32_t* out, int n);
 
