@@ -62,7 +62,7 @@ HN_AUXG_MAX = 3
 HN_MAX_COMPS = 32
 
 HN_OP_LAYER, HN_OP_OUT, HN_OP_OUT_WIDE = 1, 4, 5
-HN_ACT_NONE, HN_ACT_RELU = 0, 1
+HN_ACT_NONE, HN_ACT_RELU, HN_ACT_LEAKY_RELU, HN_ACT_ELU, HN_ACT_SOFTPLUS = 0, 1, 2, 3, 4
 HN_LAYER_NO_COMMIT, HN_LAYER_DIRECT = 1, 2
 HN_BOP_LOAD, HN_BOP_LOAD_WIDE, HN_BOP_LAYER, HN_BOP_AUX = 1, 2, 3, 4
 HN_FEAT_ZERO, HN_FEAT_ID, HN_FEAT_SIN, HN_FEAT_COS, HN_FEAT_SINP, HN_FEAT_ID_DIRECT = 0, 1, 2, 3, 4, 5

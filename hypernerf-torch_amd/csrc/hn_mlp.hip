@@ -469,6 +469,74 @@ HN_DEV unsigned hn_push_mask(unsigned bits, float x) {
 // all-ones where element (q, i) of the mask word is kept, zero where it is dropped
 HN_DEV int hn_keep_mask(unsigned nbits, int q, int i) { return (int)(nbits << (16 * q + i)) >> 31; }
 
+// The activations beyond ReLU (HN_ACT_LEAKY_RELU / ELU / SOFTPLUS), applied to the fp32 accumulator of one tile.
+// p0 / p1: the layer's parameters (op words, include/hn_kernels.h).  LeakyReLU pushes mask bits as ReLU does, with the
+// exact predicate !(z > 0) in both modes (torch's leaky_relu_backward tests z > 0, also at z = 0).  fp32 (parity) mode
+// takes the accurate expm1f / log1pf / expf; bf16 mode the hardware v_exp_f32 / v_log_f32 (__expf / __logf).
+template <bool BF16>
+HN_DEV void hn_act_tile(f32x16& acc, int act, float p0, float p1, unsigned& bits) {
+  if (act == HN_ACT_LEAKY_RELU) {
+#pragma unroll 1
+    for (int i = 0; i < 16; ++i) {
+      bits = hn_push_mask<false>(bits, acc[i]);
+      acc[i] = acc[i] > 0.0f ? acc[i] : p0 * acc[i];
+    }
+  } else if (act == HN_ACT_ELU) {
+#pragma unroll 1
+    for (int i = 0; i < 16; ++i) {
+      const float z = acc[i];
+      const float em1 = BF16 ? __expf(z) - 1.0f : expm1f(z);
+      acc[i] = z > 0.0f ? z : p0 * em1;
+    }
+  } else if (act == HN_ACT_SOFTPLUS) {
+    const float inv = 1.0f / p0;
+#pragma unroll 1
+    for (int i = 0; i < 16; ++i) {
+      const float z = acc[i], u = z * p0;
+      const float sp = BF16 ? __logf(1.0f + __expf(u)) : log1pf(expf(u));
+      acc[i] = u > p1 ? z : (BF16 ? sp * inv : sp / p0);
+    }
+  }
+}
+// f'(z) from the layer output y (ELU, SOFTPLUS), times the incoming gradient in acc
+template <bool BF16>
+HN_DEV float hn_dact_y(int act, float y, float p0, float p1) {
+  if (act == HN_ACT_ELU) return y > 0.0f ? 1.0f : y + p0;
+  const float u = p0 * y;                                   // HN_ACT_SOFTPLUS: sigmoid(p0 z) = 1 - exp(-p0 y)
+  return u > p1 ? 1.0f : (BF16 ? 1.0f - __expf(-u) : -expm1f(-u));
+}
+// Read back tile t of a stash slot as an accumulator tile (element i of lane (r, h) = feature rho(i, h) of point r):
+// the inverse of hn_stash.  bf16: the two fragments this lane stored (hn_acc_to_frags is lane-local: fragment element
+// 8u + j is accumulator element 8u + j), widened; fp32: the transposed tile, transposed back through the matrix core.
+template <bool BF16>
+HN_DEV f32x16 hn_unstash(const char* slot_base, int t, int lane) {
+  using M = ModeT<BF16>;
+  const char* src = slot_base + (size_t)t * (M::TILE_UNITS * 1024);
+  f32x16 y;
+  if constexpr (BF16) {
+    const int off0 = hn_stash_slot(lane & 31, lane >> 5, 0) * 16;
+    const u32x4 f0 = *reinterpret_cast<const u32x4*>(src + off0);
+    const u32x4 f1 = *reinterpret_cast<const u32x4*>(src + 1024 + (off0 ^ 128));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      y[2 * k] = __uint_as_float(f0[k] << 16);
+      y[2 * k + 1] = __uint_as_float(f0[k] & 0xffff0000u);
+      y[8 + 2 * k] = __uint_as_float(f1[k] << 16);
+      y[8 + 2 * k + 1] = __uint_as_float(f1[k] & 0xffff0000u);
+    }
+  } else {
+    float z[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(src + g * 1024 + lane * 16);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) z[4 * g + e] = v[e];
+    }
+    y = hn_transpose_tile(z, lane);
+  }
+  return y;
+}
+
 // Op words are read through the constant address space: scalar loads (s_load_dwordx8 through the scalar cache), and
 // the compiler knows no store of the kernel can change them (a plain pointer made it re-load a word with a vector
 // load + vmcnt(0) after every stash store).
@@ -645,7 +713,7 @@ __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_
         const int K32 = w[1] & 255, nG = (w[1] >> 8) & 255, NT = (w[1] >> 16) & 255;
         const int act = (w[1] >> 24) & 15, flags = (w[1] >> 28) & 15;
         const float* bias = bias_lds + w[2];
-        const bool do_mask = TRAIN && w[4] >= 0 && wave_valid;
+        const bool do_mask = TRAIN && w[4] >= 0 && wave_valid && act != HN_ACT_SOFTPLUS;   // (softplus: w4 = p1)
         const bool do_stash = TRAIN && w[5] >= 0 && wave_valid;
         char* out_base = do_stash ? hn_slot_base<BF16, SX>(a, w[5], NT, blk) : nullptr;
         char* aux_base = (TRAIN && wave_valid) ? hn_slot_base<BF16, SX>(a, w[6], 2 * nG, blk) : nullptr;
@@ -697,6 +765,8 @@ __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_
                 bits = hn_push_mask<BF16>(bits, acc[i]);
                 acc[i] = __int_as_float(max(__float_as_int(acc[i]), 0));  // relu on the bit pattern: one v_max_i32
               }
+            } else if (act != HN_ACT_NONE) {
+              hn_act_tile<BF16>(acc, act, __int_as_float(w[7]), __int_as_float(w[4]), bits);
             }
             if (has_out && t == 0 && h == 0 && valid) {
               // the OUT op that follows a head layer: <= 4 fp32 columns straight from the accumulator
@@ -933,22 +1003,40 @@ __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_
           else cur[s] = tmp[s];
         }
       } else if (WIDE && code == HN_BOP_LOAD_WIDE) {
-        const int n = w[3], NT = w[4];
+        const int n = w[3] & 0xffff, NT = w[4], dact = (w[3] >> 16) & 15;
         const HnSrc s = a.src[w[1]];
         unsigned nbits = 0xffffffffu;  // complement of the mask word: set = keep
         char* dz_base = (a.training && wave_valid) ? hn_slot_base<BF16>(a, w[7], NT, blk) : nullptr;
+        const bool has_mask = w[5] >= 0 && dact != HN_ACT_SOFTPLUS;              // (softplus: w5 = p1)
+        const bool from_y = (dact == HN_ACT_ELU || dact == HN_ACT_SOFTPLUS) && wave_valid;
+        const char* y_base = from_y ? hn_slot_base<BF16>(a, w[7], NT, blk) : nullptr;  // y, stashed by the forward
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
           if (t < NT) {
-            if (w[5] >= 0 && !(t & 1)) {  // output activation was relu: dZ = dY * relu'
+            if (has_mask && !(t & 1)) {  // output activation was relu / leaky relu: dZ = dY * f'(mask)
               nbits = wave_valid ? ~hn_mask_base(a, w[5], (NT + 1) >> 1, blk, lane)[(t >> 1) * 64 + lane] : 0u;
             }
             f32x16 v;
+            if (dact == 0) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-              const int row = 32 * t + hn_rho(i, h);
-              const bool keep = hn_keep_mask(nbits, t & 1, i) != 0;
-              v[i] = (valid && keep && row < n) ? s.ptr[(size_t)p * s.ld + w[2] + row] : 0.0f;
+              for (int i = 0; i < 16; ++i) {
+                const int row = 32 * t + hn_rho(i, h);
+                const bool keep = hn_keep_mask(nbits, t & 1, i) != 0;
+                v[i] = (valid && keep && row < n) ? s.ptr[(size_t)p * s.ld + w[2] + row] : 0.0f;
+              }
+            } else {
+              const float p0 = __int_as_float(w[6]), p1 = __int_as_float(w[5]);
+              f32x16 y = {0};
+              if (y_base != nullptr) y = hn_unstash<BF16>(y_base, t, lane);
+#pragma unroll
+              for (int i = 0; i < 16; ++i) {
+                const int row = 32 * t + hn_rho(i, h);
+                const float g = (valid && row < n) ? s.ptr[(size_t)p * s.ld + w[2] + row] : 0.0f;
+                float d = 1.0f;
+                if (dact == HN_ACT_LEAKY_RELU) d = hn_keep_mask(nbits, t & 1, i) != 0 ? 1.0f : p0;
+                else d = hn_dact_y<BF16>(dact, y[i], p0, p1);
+                v[i] = g * d;
+              }
             }
             hn_acc_to_frags(v, cur + t * M::STEPS32);
             if (dz_base != nullptr) hn_stash<BF16>(cur + t * M::STEPS32, dz_base, t, lane);
@@ -959,6 +1047,9 @@ __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_
         const bool has_mask = w[4] >= 0;
         const bool do_stash = a.training && w[5] >= 0 && wave_valid;
         char* dz_base = do_stash ? hn_slot_base<BF16, SZ>(a, w[5], NT, blk) : nullptr;
+        const int dact = w[2];      // 0: relu' from the mask (or nothing); else HN_ACT_LEAKY_RELU / ELU / SOFTPLUS
+        const char* y_base = (!S8 && (dact == HN_ACT_ELU || dact == HN_ACT_SOFTPLUS) && wave_valid)
+                                 ? hn_slot_base<BF16>(a, w[6], NT, blk) : nullptr;
         unsigned nbits = 0xffffffffu;
         unsigned mbits[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // complemented words: set = keep
         if (has_mask) {
@@ -987,9 +1078,21 @@ __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_
             HN_STAMP(2);
             if (!(t & 1)) nbits = mbits[t >> 1];
             // dZ of padded points is zero from the LOAD ops on and stays zero: no `valid` select here
+            if (dact == 0) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i)
-              acc[i] = __int_as_float(__float_as_int(acc[i]) & hn_keep_mask(nbits, t & 1, i));
+              for (int i = 0; i < 16; ++i)
+                acc[i] = __int_as_float(__float_as_int(acc[i]) & hn_keep_mask(nbits, t & 1, i));
+            } else if (dact == HN_ACT_LEAKY_RELU) {
+              const float p0 = __int_as_float(w[3]);
+#pragma unroll
+              for (int i = 0; i < 16; ++i)
+                if (hn_keep_mask(nbits, t & 1, i) == 0) acc[i] *= p0;
+            } else if (y_base != nullptr) {
+              const f32x16 y = hn_unstash<BF16>(y_base, t, lane);
+              const float p0 = __int_as_float(w[3]), p1 = __int_as_float(w[7]);
+#pragma unroll
+              for (int i = 0; i < 16; ++i) acc[i] *= hn_dact_y<BF16>(dact, y[i], p0, p1);
+            }
             hn_acc_to_frags(acc, nxt + t * M::STEPS32);
             if (do_stash) {
               if constexpr (SZ != 0) hn_stash8_acc<SZ>(acc, dz_base, t, lane);
@@ -1817,8 +1920,8 @@ extern "C" int hn_mlp_workspace_bytes(const int32_t* ops_host, int n_ops, int ba
     const int32_t* w = ops_host + (size_t)i * HN_OP_WORDS;
     if (!backward) {
       if (w[0] == HN_OP_LAYER) {
-        const int nG = (w[1] >> 8) & 255, NT = (w[1] >> 16) & 255;
-        mask(w[4], NT);
+        const int nG = (w[1] >> 8) & 255, NT = (w[1] >> 16) & 255, act = (w[1] >> 24) & 15;
+        if (act != HN_ACT_SOFTPLUS) mask(w[4], NT);      // (softplus: w4 = p1)
         stash(w[5], NT);
         stash(w[6], 2 * nG);
       } else if (w[0] != HN_OP_OUT && w[0] != HN_OP_OUT_WIDE) {
@@ -1828,12 +1931,13 @@ extern "C" int hn_mlp_workspace_bytes(const int32_t* ops_host, int n_ops, int ba
       if (w[0] == HN_BOP_LOAD) {
         stash(w[7], 1);
       } else if (w[0] == HN_BOP_LOAD_WIDE) {
-        mask(w[5], w[4]);
+        if (((w[3] >> 16) & 15) != HN_ACT_SOFTPLUS) mask(w[5], w[4]);      // (softplus: w5 = p1)
         stash(w[7], w[4]);
       } else if (w[0] == HN_BOP_LAYER) {
         const int NT = (w[1] >> 16) & 255;
         mask(w[4], NT);
         stash(w[5], NT);
+        if (w[2] == HN_ACT_ELU || w[2] == HN_ACT_SOFTPLUS) stash(w[6], NT);   // the derivative source (y)
       } else if (w[0] != HN_BOP_AUX) {
         return -7;
       }

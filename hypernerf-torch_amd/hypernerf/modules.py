@@ -20,15 +20,58 @@ from ..machine import AuxSpec, Feature, GradIn, Layer, OutSpec, Program, copy_fe
 from . import model_utils
 
 
-def _act_name(act, what: str) -> str:
-    if act is None or isinstance(act, nn.Identity):
-        return "none"
+def _smooth_act(act):
+    """(machine name, (p0, p1)) of the activations the MLP machine applies in its layer epilogue beyond ReLU, with every
+    constructor parameter of the torch module (include/hn_kernels.h HN_ACT_*), or None."""
+    if isinstance(act, nn.LeakyReLU):
+        return "leaky_relu", (float(act.negative_slope), 0.0)
+    if isinstance(act, nn.ELU):
+        return "elu", (float(act.alpha), 0.0)
+    if isinstance(act, nn.Softplus):
+        return "softplus", (float(act.beta), float(act.threshold))
+    return None
+
+
+def _hidden_act(act, what: str):
+    """(machine name, params) of a HIDDEN activation: ReLU, LeakyReLU, ELU, Softplus."""
     if isinstance(act, nn.ReLU):
-        return "relu"
+        return "relu", (0.0, 0.0)
+    spec = _smooth_act(act)
+    if spec is not None:
+        return spec
+    name = type(act).__name__
+    if isinstance(act, (nn.SiLU, nn.GELU)):
+        raise NotImplementedError(f"{what}: hidden_activation {name}: its derivative is not a function of the layer "
+                                  "output, so the backward would need the pre-activation stashed as well; the HIP MLP "
+                                  "machine takes f' from the ReLU mask or from the stashed output only (ReLU, LeakyReLU, "
+                                  "ELU, Softplus)")
+    raise NotImplementedError(f"{what}: hidden_activation {name} is not implemented in the HIP MLP machine (hidden "
+                              "layers: ReLU, LeakyReLU, ELU, Softplus)")
+
+
+def _out_act(act, what: str):
+    """(machine name, params) of an OUTPUT activation: Identity, Sigmoid (narrow heads), ReLU / LeakyReLU / ELU / Softplus
+    (wide outputs: the hidden-layer epilogue)."""
+    if act is None or isinstance(act, nn.Identity):
+        return "none", (0.0, 0.0)
+    if isinstance(act, nn.ReLU):
+        return "relu", (0.0, 0.0)
     if isinstance(act, nn.Sigmoid):
-        return "sigmoid"
+        return "sigmoid", (0.0, 0.0)
+    spec = _smooth_act(act)
+    if spec is not None:
+        return spec
     raise NotImplementedError(f"{what}: activation {type(act).__name__} is not implemented in the HIP MLP machine "
-                              "(reference path uses ReLU / Sigmoid / Identity only)")
+                              "(outputs: Identity / Sigmoid / ReLU / LeakyReLU / ELU / Softplus)")
+
+
+def _act_name(act, what: str) -> str:
+    return _out_act(act, what)[0]
+
+
+# output activations that only a wide output (the hidden-layer epilogue) applies; a narrow head (<= 4 columns, the
+# head epilogue) has Identity / Sigmoid only
+WIDE_ONLY_ACTS = ("relu", "leaky_relu", "elu", "softplus")
 
 
 def mlp_layers(mlp: "MLP", prefix: str, input_aux: Optional[AuxSpec], main_in: Optional[int],
@@ -38,9 +81,8 @@ def mlp_layers(mlp: "MLP", prefix: str, input_aux: Optional[AuxSpec], main_in: O
     The MLP input is [running activation (main_in features, may be None) | generated features
     (input_aux, may be None)]; skip layers re-append the same input after `linears[i]`, i in skips.
     """
-    if _act_name(mlp.hidden_activation, prefix) != "relu":
-        raise NotImplementedError(f"{prefix}: hidden activation must be ReLU")
-    out_act = _act_name(mlp.output_activation, prefix)
+    act, act_params = _hidden_act(mlp.hidden_activation, prefix)
+    out_act, out_params = _out_act(mlp.output_activation, prefix)
     if main_in is not None and any(i in mlp.skips for i in range(len(mlp.linears) - 1)):
         # a skip would have to re-append the running activation, which no longer exists
         raise NotImplementedError(f"{prefix}: skip connections need generated (aux) inputs only")
@@ -56,17 +98,18 @@ def mlp_layers(mlp: "MLP", prefix: str, input_aux: Optional[AuxSpec], main_in: O
         if i == 0:
             ly = Layer(f"{prefix}.linears.0", lin.weight, lin.bias,
                        main=(0, main_in) if main_in is not None else None,
-                       aux=input_aux, aux_c0=main_in or 0, act="relu")
+                       aux=input_aux, aux_c0=main_in or 0, act=act, act_params=act_params)
         elif (i - 1) in mlp.skips:
             ly = Layer(f"{prefix}.linears.{i}", lin.weight, lin.bias, main=(0, mlp.width), aux=input_aux,
-                       aux_c0=mlp.width, act="relu")
+                       aux_c0=mlp.width, act=act, act_params=act_params)
         else:
-            ly = Layer(f"{prefix}.linears.{i}", lin.weight, lin.bias, main=(0, mlp.width), act="relu")
+            ly = Layer(f"{prefix}.linears.{i}", lin.weight, lin.bias, main=(0, mlp.width), act=act,
+                       act_params=act_params)
         layers.append(ly)
     lg = mlp.logit_layer
     if out is not None and not out.wide:
-        if out_act == "relu":
-            raise NotImplementedError(f"{prefix}: ReLU on a narrow output head")
+        if out_act in WIDE_ONLY_ACTS:
+            raise NotImplementedError(f"{prefix}: {type(mlp.output_activation).__name__} on a narrow output head")
         out = OutSpec(out.dst, out.col, out_act, out.residual, False, out.publish)
         layers.append(Layer(f"{prefix}.logit_layer", lg.weight, lg.bias, main=(0, mlp.width), act="none",
                             commit=False, out=out, grad_in=grad_in))
@@ -74,7 +117,7 @@ def mlp_layers(mlp: "MLP", prefix: str, input_aux: Optional[AuxSpec], main_in: O
         if out_act == "sigmoid":
             raise NotImplementedError(f"{prefix}: sigmoid on a wide output")
         layers.append(Layer(f"{prefix}.logit_layer", lg.weight, lg.bias, main=(0, mlp.width), act=out_act,
-                            commit=True, out=out, grad_in=grad_in))
+                            act_params=out_params, commit=True, out=out, grad_in=grad_in))
     return layers
 
 
@@ -110,12 +153,11 @@ class MLP(nn.Module):
     def _check_machine_limits(self):
         """What the HIP MLP machine does not run is refused HERE, at construction — before a mis-configured model reaches
         the GPU (round 6; the first forward raised before).  The reference's own configurations all pass (ReLU hidden
-        layers, Identity / Sigmoid heads, width <= 256: modules.py:62-114, models.py:139-166).  INTEGRATION.md lists these."""
+        layers, Identity / Sigmoid heads, width <= 256: modules.py:62-114, models.py:139-166), and so do LeakyReLU / ELU /
+        Softplus hidden layers and wide outputs.  INTEGRATION.md lists these."""
         name = type(self).__name__
-        if _act_name(self.hidden_activation, name) != "relu":
-            raise NotImplementedError(f"{name}: hidden_activation {type(self.hidden_activation).__name__}: the hidden layers "
-                                      "of the HIP MLP machine are ReLU (mask bit + v_max on the bit pattern)")
-        out_act = _act_name(self.output_activation, name)           # raises for anything but Identity / ReLU / Sigmoid
+        _hidden_act(self.hidden_activation, name)                   # raises for anything but ReLU / LeakyReLU / ELU / Softplus
+        out_act = _act_name(self.output_activation, name)           # raises for anything else but Identity / Sigmoid
         if self.width > 256:
             raise NotImplementedError(f"{name}: width {self.width} > 256 — a wave carries one hidden vector of <= 256 "
                                       "features (64 VGPRs in bf16) through the layers in registers; not a host-side limit")
@@ -134,7 +176,7 @@ class MLP(nn.Module):
         if call is None:
             aux = AuxSpec(copy_features(0, range(self.in_ch), need_input_grad))
             out_act = _act_name(self.output_activation, "mlp")
-            narrow = self.out_ch <= 4 and out_act != "relu"
+            narrow = self.out_ch <= 4 and out_act not in WIDE_ONLY_ACTS
             grad_in = GradIn(4, 0, (5, 0) if (narrow and out_act == "sigmoid") else None)
             layers = mlp_layers(self, "mlp", aux, None, OutSpec(0, 0, "none", None, wide=not narrow), grad_in)
             call = F.ProgramCall(Program(layers, name="MLP"), [False], [self.out_ch], [("g", 0), ("y", 0)])
@@ -223,9 +265,10 @@ class NerfMLP(nn.Module):
         self._calls = {}
         # refused at construction (round 6), not at the first forward: the rgb head is a narrow (<= 4 column) head of the
         # machine — Identity or Sigmoid (models.py:164, 288) —, the trunk feeds the bottleneck at trunk_width // 2
-        if _act_name(self.rgb_mlp.output_activation, "NerfMLP.rgb_mlp") == "relu":
-            raise NotImplementedError("NerfMLP: rgb_activation ReLU (a ReLU on a <= 4-column head is not implemented in "
-                                      "the HIP MLP machine; the reference uses Sigmoid / Identity)")
+        if _act_name(self.rgb_mlp.output_activation, "NerfMLP.rgb_mlp") in WIDE_ONLY_ACTS:
+            raise NotImplementedError(f"NerfMLP: rgb_activation {type(self.rgb_mlp.output_activation).__name__} (only "
+                                      "Identity / Sigmoid on a <= 4-column head are implemented in the HIP MLP machine; "
+                                      "the reference uses Sigmoid / Identity)")
         if rgb_channels > 4 or alpha_channels > 4:
             raise NotImplementedError("NerfMLP: rgb_channels / alpha_channels > 4 (narrow heads of the HIP MLP machine)")
 

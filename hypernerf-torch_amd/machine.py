@@ -60,6 +60,18 @@ DZ_SCALE_LOG2 = int(os.environ.get("HN_DZ_SCALE_LOG2", 16))
 # --------------------------------------------------------------------------------------------
 # network description
 # --------------------------------------------------------------------------------------------
+# hidden / wide-output activations of a Layer: name -> HN_ACT_* code (include/hn_kernels.h)
+ACT_CODES = {"none": L.HN_ACT_NONE, "relu": L.HN_ACT_RELU, "leaky_relu": L.HN_ACT_LEAKY_RELU, "elu": L.HN_ACT_ELU,
+             "softplus": L.HN_ACT_SOFTPLUS}
+MASK_ACTS = ("relu", "leaky_relu")      # f' from the mask word
+Y_ACTS = ("elu", "softplus")            # f' from the stashed layer output y
+
+
+def f32_bits(x: float) -> int:
+    """The int32 op word that carries float32 `x` (activation parameters travel bit-cast in op words)."""
+    return int(np.array([x], dtype=np.float32).view(np.int32)[0])
+
+
 @dataclass
 class Feature:
     src: int            # source array index (0..3)
@@ -143,7 +155,8 @@ class Layer:
                                                 # column -k0 makes the layer read cur[k0:] only (block-sparse window)
     aux: Optional[AuxSpec] = None
     aux_c0: int = 0
-    act: str = "none"                           # 'none' | 'relu'
+    act: str = "none"                           # a key of ACT_CODES
+    act_params: Tuple[float, float] = (0.0, 0.0)   # (p0, p1): leaky_relu (slope, -), elu (alpha, -), softplus (beta, threshold)
     commit: bool = True
     out: Optional[OutSpec] = None
     grad_in: Optional[GradIn] = None
@@ -320,8 +333,17 @@ class Program:
             ly.dz_slot = self._new_slot("stash", ly.nt)
             if id(ly) in consumers:
                 ly.out_slot = self._new_slot("stash", ly.nt)
-            if ly.act == "relu" and (id(ly) in consumers or (ly.out is not None and ly.out.wide)):
+            if ly.act not in ACT_CODES:
+                raise NotImplementedError(f"{ly.name}: activation {ly.act!r} is not implemented in the MLP machine")
+            wide_out = ly.out is not None and ly.out.wide
+            if ly.act != "none" and ly.out is not None and not wide_out:
+                raise NotImplementedError(f"{ly.name}: activation {ly.act!r} on a narrow output head")
+            if ly.act in MASK_ACTS and (id(ly) in consumers or wide_out):
                 ly.mask_slot = self._new_slot("mask", (ly.nt + 1) // 2)
+            if ly.act in Y_ACTS and wide_out:
+                # the backward takes f' from y: a wide output has no consumer stashing it, so the forward stashes y into
+                # the layer's dZ slot, which the backward's HN_BOP_LOAD_WIDE reads and overwrites with dZ in place
+                ly.out_slot = ly.dz_slot
         last = self.layers[-1]
         if last.out is None:
             raise ValueError("the last layer of a program must produce an output")
@@ -384,7 +406,8 @@ class Program:
         for ly in self.layers:
             k32 = ly.prev.nt if ly.main is not None else 0
             ng = ly.aux.groups if ly.aux is not None else 0
-            act = L.HN_ACT_RELU if ly.act == "relu" else L.HN_ACT_NONE
+            act = ACT_CODES[ly.act]
+            p0, p1 = (f32_bits(v) for v in ly.act_params) if ly.act not in ("none", "relu") else (0, 0)
             flags = 0 if ly.commit else L.HN_LAYER_NO_COMMIT
             if ly.aux is not None and any(f.kind != L.HN_FEAT_ZERO and (f.src, f.comp) not in self.comp_map
                                           for f in ly.aux.feats):
@@ -394,7 +417,8 @@ class Program:
                 aux_slot = ly.aux.slot
                 stashed_aux.add(id(ly.aux))
             ops.append([L.HN_OP_LAYER, k32 | ng << 8 | ly.nt << 16 | act << 24 | flags << 28, ly.bias_off,
-                        ly.aux.feat_off if ly.aux is not None else 0, ly.mask_slot, ly.out_slot, aux_slot, 0])
+                        ly.aux.feat_off if ly.aux is not None else 0,
+                        p1 if ly.act == "softplus" else ly.mask_slot, ly.out_slot, aux_slot, p0])
             if ly.out is not None:
                 o = ly.out
                 if o.wide:
@@ -408,6 +432,19 @@ class Program:
         return np.asarray(ops, dtype=np.int32)
 
     # ---- backward ops -------------------------------------------------------------------------
+    @staticmethod
+    def _dact(ly: Layer) -> Tuple[int, int, int]:
+        """(dact, p0 word, p1 word) of a backward op: HN_ACT_* when f' is more than the relu mask AND, else all 0 (ReLU
+        and linear layers encode exactly as before the smooth activations existed)."""
+        if ly.act in ("none", "relu"):
+            return 0, 0, 0
+        return ACT_CODES[ly.act], f32_bits(ly.act_params[0]), f32_bits(ly.act_params[1])
+
+    @property
+    def y_acts(self) -> bool:
+        """Some layer takes f' from its stashed output (ELU / Softplus)."""
+        return any(ly.act in Y_ACTS for ly in self.layers)
+
     def _aux_grad_groups(self, ly: Layer) -> List[int]:
         if ly.aux is None:
             return []
@@ -438,7 +475,9 @@ class Program:
             if gi is None:
                 raise ValueError(f"{ly.name}: output layer without a gradient source")
             if ly.out.wide:
-                ops.append([L.HN_BOP_LOAD_WIDE, gi.src, gi.col, ly.n_out, ly.nt, ly.mask_slot, 0, ly.dz_slot])
+                dact, p0, p1 = self._dact(ly)
+                ops.append([L.HN_BOP_LOAD_WIDE, gi.src, gi.col, ly.n_out | dact << 16, ly.nt,
+                            p1 if ly.act == "softplus" else ly.mask_slot, p0, ly.dz_slot])
             else:
                 sy = gi.sigmoid_y
                 w3 = ly.n_out | (256 if to2 else 0)
@@ -471,9 +510,10 @@ class Program:
                 if head is not None:
                     emit_load(head, True)
                     emit_aux(head, True)
-                mask = P.mask_slot if P.act == "relu" else -1
-                ops.append([L.HN_BOP_LAYER, consumer.nt | (1 if head else 0) << 8 | P.nt << 16, 0, 0, mask, P.dz_slot,
-                            0, 0])
+                mask = P.mask_slot if P.act in MASK_ACTS else -1
+                dact, p0, p1 = self._dact(P)
+                ops.append([L.HN_BOP_LAYER, consumer.nt | (1 if head else 0) << 8 | P.nt << 16, dact, p0, mask,
+                            P.dz_slot, P.out_slot if P.act in Y_ACTS else 0, p1])
                 plan.append(("layer", consumer, head, P))
                 consumer = P
                 emit_aux(P, False)
@@ -648,15 +688,21 @@ class Program:
         fwd = self.fwd_ops.copy()
         for w in fwd:
             if w[0] == L.HN_OP_LAYER:
-                w[4], w[5], w[6] = res(int(w[4])), res(int(w[5])), res(int(w[6]))
+                if (int(w[1]) >> 24) & 15 != L.HN_ACT_SOFTPLUS:     # softplus: w4 = p1
+                    w[4] = res(int(w[4]))
+                w[5], w[6] = res(int(w[5])), res(int(w[6]))
         bwd = self.bwd_ops.copy()
         for w in bwd:
             if w[0] == L.HN_BOP_LOAD:
                 w[7] = res(int(w[7]))
             elif w[0] == L.HN_BOP_LOAD_WIDE:
-                w[5], w[7] = res(int(w[5])), res(int(w[7]))
+                if (int(w[3]) >> 16) & 15 != L.HN_ACT_SOFTPLUS:     # softplus: w5 = p1
+                    w[5] = res(int(w[5]))
+                w[7] = res(int(w[7]))
             elif w[0] == L.HN_BOP_LAYER:
                 w[4], w[5] = res(int(w[4])), res(int(w[5]))
+                if int(w[2]) in (L.HN_ACT_ELU, L.HN_ACT_SOFTPLUS):   # the derivative source (y)
+                    w[6] = res(int(w[6]))
         return fwd, bwd
 
     def grad_offsets(self) -> Tuple[List[int], int]:
@@ -1418,6 +1464,11 @@ class MlpRunner:
     def forward(self, mode, n_points, samples_per_ray, srcs, dsts, training: bool):
         """Launch the forward machine.  Returns (stash, masks) (None, None when not training)."""
         mode = self.effective_mode(mode)
+        if mode == L.HN_MODE_BF16_S8 and training and self.prog.y_acts:
+            raise NotImplementedError(
+                f"{self.prog.name}: precision 'bf16s8' keeps the training stash in 8 bits, too coarse to take the "
+                "derivative of an ELU / Softplus layer from its output; use 'bf16' or 'fp32' (LeakyReLU works: it needs "
+                "only the mask)")
         device = dsts[0].device if dsts and dsts[0] is not None else srcs[0][0].device
         d = self.pack(device, mode, force=training)
         stash = masks = None

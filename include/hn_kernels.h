@@ -32,7 +32,9 @@ typedef void* hnStream_t; /* hipStream_t */
 #define HN_VERSION 340   /* 320: HnDwJob carries a second X slot; 321: HN_BOP_AUX w2 = tile word; 330: a level composited
                             from two parts through a merge permutation (HnCompositeArgs.perm, hn_sample_pdf_split); 331: weight-gradient
                             jobs flush to partial slabs + hn_mlp_wgrad_reduce (HnDwBatch.partials, HnDwJob.p_tile); 340: hn_build_config,
-                            hn_mlp_wgrad_reduce_adam (the reduce launch applies the optimizer) */
+                            hn_mlp_wgrad_reduce_adam (the reduce launch applies the optimizer).  The activations
+                            HN_ACT_LEAKY_RELU / ELU / SOFTPLUS extend the op-word vocabulary only: no struct and
+                            no existing encoding changed */
 
 /* numeric modes of the MLP machine */
 #define HN_MODE_F32 0  /* v_mfma_f32_32x32x2_f32: exact fp32 products, parity mode (<=1e-4 vs oracle) */
@@ -69,9 +71,18 @@ typedef void* hnStream_t; /* hipStream_t */
 #define HN_OP_LAYER 1    /* w1 = K32 | nG<<8 | NT<<16 | act<<24 | flags<<28 ; w2=bias_off w3=feat_off
                             w4=mask|-1 w5=stash_out|-1 w6=stash_aux|-1 — RESOLVED for the launch: the byte offset
                             of block 0 of that stash region in KiB (masks: in units of 256 B); a region holds, per
-                            32-point block, NT tiles (out), 2*nG tiles (aux) or (NT+1)/2 mask words per lane     */
+                            32-point block, NT tiles (out), 2*nG tiles (aux) or (NT+1)/2 mask words per lane;
+                            w7 = first activation parameter p0 (bit-cast float, 0 for NONE / RELU).
+                            HN_ACT_SOFTPLUS keeps no mask: its w4 is the second parameter p1 (bit-cast float)     */
+/* act(z), z = the fp32 accumulator (pre-activation).  The backward takes f' from what it has: the mask word (RELU,
+ * LEAKY_RELU) or the layer output y read back from the stash slot the forward wrote (ELU, SOFTPLUS).  Activations whose
+ * derivative is not a function of y (SiLU, GELU) would need the pre-activation stashed and are not provided. */
 #define HN_ACT_NONE 0
 #define HN_ACT_RELU 1
+#define HN_ACT_LEAKY_RELU 2 /* z > 0 ? z : p0*z (p0 = negative_slope); mask word as RELU; f' = keep ? 1 : p0           */
+#define HN_ACT_ELU 3        /* z > 0 ? z : p0*expm1(z) (p0 = alpha); f' = y > 0 ? 1 : y + p0                           */
+#define HN_ACT_SOFTPLUS 4   /* p0*z > p1 ? z : log1p(exp(p0*z))/p0 (p0 = beta, p1 = threshold); f' = p0*y > p1 ? 1 :
+                               1 - exp(-p0*y)                                                                           */
 #define HN_LAYER_NO_COMMIT 1 /* flags bit0: leave cur untouched (head layers read by an OUT op)      */
 #define HN_LAYER_DIRECT 2    /* flags bit1: the layer's feature groups hold HN_FEAT_ID_DIRECT entries       */
 /* dst[w1][p*ld + w2 + i] = act(accL row i) (+ residual src[w5][.. + w6 + i]), i < w3 <= 4           */
@@ -84,14 +95,21 @@ typedef void* hnStream_t; /* hipStream_t */
  * State: `cur` = dZ of the layer being differentiated, `cur2` = a second, 32-feature dZ (heads).
  * HN_BOP_LAYER: dH = W^T . dZ for every 32-feature tile t < NT of the layer INPUT, one at a time:
  *     acc = W[:, 32t..]^T . cur (32*K32 dZ features) + W2[:, 32t..]^T . cur2 (if K32b) ;
- *     nxt[t] = acc * relu'(mask) ; then cur <- nxt.  Stream order per tile: K32 blocks, K32b blocks. */
+ *     nxt[t] = acc * f'(mask | y) ; then cur <- nxt.  Stream order per tile: K32 blocks, K32b blocks. */
 #define HN_BOP_LOAD 1      /* w1=src w2=col w3=n(<=4) w4=act'(1 sigmoid: y from src w5 col w6)
                               w7=stash|-1 ; w3 bit 8 set: destination cur2 instead of cur ;
                               w3 bit 9 set: ADD the source-gradient accumulators of slots 8*((w3>>10)&3) + i — the
                               gradient that later ops of this program (earlier in forward order) left for the
                               components this head published (a NULL src then contributes nothing)         */
-#define HN_BOP_LOAD_WIDE 2 /* w1=src  w2=col  w3=n  w4=NT  w5=relu mask|-1  w7=dZ stash|-1 (resolved offsets)   */
-#define HN_BOP_LAYER 3     /* w1 = K32 | K32b<<8 | NT<<16 ; w4=mask|-1 w5=dZ stash|-1 (resolved offsets)   */
+#define HN_BOP_LOAD_WIDE 2 /* w1=src  w2=col  w3=n | dact<<16  w4=NT  w5=relu mask|-1  w6=p0  w7=dZ stash|-1
+                              (resolved offsets).  dact = HN_ACT_* of the output when f' is more than the mask AND
+                              (LEAKY_RELU, ELU, SOFTPLUS), else 0.  ELU / SOFTPLUS: the derivative source is the dZ
+                              slot itself — the forward layer stashed y there (its stash_out) and this op overwrites
+                              it, tile by tile and lane by lane, with dZ; SOFTPLUS has no mask, w5 = p1              */
+#define HN_BOP_LAYER 3     /* w1 = K32 | K32b<<8 | NT<<16 ; w4=mask|-1 w5=dZ stash|-1 (resolved offsets) ;
+                              w2 = dact of the layer's activation (as HN_BOP_LOAD_WIDE; 0 = the mask AND / none),
+                              w3 = p0, w7 = p1 (bit-cast floats), w6 = derivative source: the stash slot of the layer
+                              output y (its stash_out, resolved offset; ELU / SOFTPLUS, else unused)                 */
 /* gradient w.r.t. GENERATED input features: per 32-feature tile of nG*64 features,
  * tmp = W_aux^T . (cur | cur2), then the chain rule through the feature table into the per-point
  * source-gradient accumulators (LDS), written to `dsrc` at the end of the program.               */
