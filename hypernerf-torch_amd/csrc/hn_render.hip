@@ -610,7 +610,10 @@ HN_DEV void hn_pdf_ray(const HnPdfArgs& q, int ray, int lane, const float* wr, f
   // (binary search) and the new samples below it or equal with a smaller index — then scatters them to that position in
   // LDS.  The same sequence, bit for bit, as the (depth, position) bitonic sort below — which stays for any other input —
   // in 2 LDS passes instead of log2(n)(log2(n)+1)/2 = 28 rounds of compare-exchange at 128 entries (16 -> 10 us a launch).
-  bool fast = true;
+  // Each lane holds 4 of the level's own depths (xs[0..3]), so the rank merge covers nmerge <= 256 only; longer levels
+  // (the fused form admits nc = 257, the bins form nc up to 512 - nf) take the bitonic sort.  The 8 slots for new
+  // samples (xs[4..11]) always suffice: hn_pdf_check admits nf <= 512 - nmerge (<= 510 with a merge, nc >= 2).
+  bool fast = nmerge <= 256;             // wave-uniform: the ballot below is all-false or all-true on it
   for (int i = lane; i < total; i += 64) {
     const float x = srt[i];
     fast = fast && (x == x) && !(i + 1 < nmerge && !(x <= srt[i + 1]));

@@ -504,6 +504,24 @@ def sample_along_rays(origins, directions, lower, upper, t_rand, scale: float = 
     return z, pts
 
 
+MAX_SAMPLES = 512       # samples per ray and level: hn_composite_* (8 segments of 64), the sampler's merge buffer
+MAX_PDF_COARSE = 257    # coarse samples the fused inverse-CDF form takes: nc - 2 = 255 bins, 256 cdf entries
+
+
+def check_sample_counts(n_coarse: int, n_fine: int, what: str):
+    """NotImplementedError for per-ray sample counts the render kernels refuse (hn_check_comp, hn_pdf_check) — raised
+    where a model is built or a render starts, instead of an HnError from the first launch that sees them."""
+    if n_coarse > MAX_SAMPLES:
+        raise NotImplementedError(f"{what}: {n_coarse} coarse samples per ray; the compositing kernel takes at most "
+                                  f"{MAX_SAMPLES}")
+    if n_fine > 0 and n_coarse + n_fine > MAX_SAMPLES:
+        raise NotImplementedError(f"{what}: {n_coarse} + {n_fine} samples per ray; the fine level takes at most "
+                                  f"{MAX_SAMPLES} (coarse + fine)")
+    if n_fine > 0 and n_coarse > MAX_PDF_COARSE:
+        raise NotImplementedError(f"{what}: {n_coarse} coarse samples per ray; the inverse-CDF sampler takes at most "
+                                  f"{MAX_PDF_COARSE} ({MAX_PDF_COARSE - 2} bins)")
+
+
 def sample_pdf(weights, z, u, origins=None, directions=None, want_points=True, bins=None, merge=True, split=False):
     """Inverse-CDF sampling at draws u (B,Nf).
 

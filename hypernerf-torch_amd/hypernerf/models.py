@@ -137,6 +137,7 @@ class NerfModel(nn.Module):
             raise UnboundLocalError("n_samples_fine=0 is not constructible in the reference (models.py:292-309): "
                                     "local variable 'nerf_mlps_fine' referenced before assignment; use the legacy "
                                     "render_rays(N_importance=0) path for coarse-only rendering")
+        F.check_sample_counts(self.num_coarse_samples, self.num_fine_samples, "NerfModel")
         self.nerf_mlps_coarse = nerf_mlps_coarse
         self.nerf_mlps_fine = nerf_mlps_fine
         self._template_calls: Dict[Any, F.ProgramCall] = {}

@@ -46,6 +46,7 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
     compatibility; the fused kernels need no point chunking.  `rng` optionally supplies the draws
     ('perturb_rand' (B,N), 'noise_coarse' (B,N), 'u' (B,Nimp), 'noise_fine' (B,N+Nimp), N(0,1) unscaled)."""
     rng = rng or {}
+    F.check_sample_counts(N_samples, N_importance, "render_rays")
     L.require_gpu(rays)
     model_coarse = models[0]
     emb_xyz, emb_dir = embeddings[0], embeddings[1]

@@ -798,3 +798,66 @@ def test_ray_metadata_is_a_dict_that_converts_on_first_use():
     assert type(rd["metadata"]) is dict and rd["metadata"]["warp"].tolist() == [3, 7, 0, 99]
     sub = extract_rays_batch({"origins": rays[:, :3], "directions": rays[:, 3:6], "viewdirs": None, "metadata": RayMetadata(col)}, 1, 3)
     assert sub["metadata"]["camera"].tolist() == [7, 0]
+
+
+def test_per_ray_kernels_refuse_sizes_past_their_limits_before_any_launch():
+    """The first size each per-ray entry point refuses returns -2 with every pointer non-null (dummies: a launch would
+    fault, so -2 means nothing was launched); the last admitted size, called with one input missing, gets past the size
+    check to the pointer check (-3) — the boundary sits exactly there.  Limits: compositing S <= 512; inverse-CDF
+    sampling nb <= 255 bins and nc + nf <= 512 (the fused form nb = nc - 2: S <= 257 for hn_composite_sample_pdf)."""
+    lib = L.load()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    i = ctypes.c_int
+
+    def comp(s, missing=None):
+        a = L.HnCompositeArgs()
+        a.n_rays, a.n_samples, a.ray_ld = 1, s, 3
+        for f in ("rgb", "raw", "z", "dirs", "out_rgb", "out_depth", "out_acc", "out_weights", "d_rgb", "d_raw"):
+            setattr(a, f, None if f == missing else p.value)
+        return a
+
+    for fn in (lib.hn_composite_forward, lib.hn_composite_backward):
+        assert fn(ctypes.byref(comp(513)), None) == -2
+        assert fn(ctypes.byref(comp(512, missing="rgb")), None) == -3
+
+    def pdf(fn, nb, nc, nf, bins=True, u=p, split=False):
+        args = [p, i(nb), p if bins else None, i(nb), p, i(nc), u, p, p, i(3), i(1), i(nf), p, p, p, p]
+        if split:
+            args += [p, p]
+        return fn(*args, None)
+
+    for split, fn in ((False, lib.hn_sample_pdf), (True, lib.hn_sample_pdf_split)):
+        assert pdf(fn, 256, 300, 64, split=split) == -2                      # 256 bins
+        assert pdf(fn, 255, 300, 64, u=None, split=split) == -3
+        assert pdf(fn, 100, 300, 213, split=split) == -2                     # nc + nf = 513
+        assert pdf(fn, 100, 300, 212, u=None, split=split) == -3
+        assert pdf(fn, 256, 258, 64, bins=False, split=split) == -2          # fused form, nc = 258
+        assert pdf(fn, 255, 257, 255, bins=False, u=None, split=split) == -3
+        assert pdf(fn, 255, 257, 256, bins=False, split=split) == -2         # fused form, nc + nf = 513
+
+    def comp_pdf(s, nf, u=p):
+        return lib.hn_composite_sample_pdf(ctypes.byref(comp(s)), u, p, p, i(3), i(nf), p, p, p, p, p, p, None)
+
+    assert comp_pdf(258, 64) == -2
+    assert comp_pdf(257, 256) == -2
+    assert comp_pdf(257, 255, u=None) == -3
+
+
+def test_sample_counts_past_the_kernel_limits_are_refused_up_front():
+    """NerfModel refuses, at construction and naming the limit, what its render kernels would refuse at the first
+    forward: more than 257 coarse samples with a fine level (255 pdf bins), more than 512 samples per ray in a level.
+    Legacy render_rays refuses the same before its first launch (here: before it even asks for a GPU tensor)."""
+    for nc, nf, limit in ((258, 1, "257"), (300, 100, "257"), (200, 313, "512"), (257, 256, "512"), (513, 1, "512")):
+        with pytest.raises(NotImplementedError, match=limit):
+            models.NerfModel(EMB, n_samples_coarse=nc, n_samples_fine=nf)
+    for nc, nf in ((257, 255), (256, 256), (64, 448), (3, 509)):
+        m = models.NerfModel(EMB, n_samples_coarse=nc, n_samples_fine=nf)
+        assert (m.num_coarse_samples, m.num_fine_samples) == (nc, nf)
+    rays = torch.zeros(4, 8)
+    for nc, nf, limit in ((513, 0, "512"), (258, 1, "257"), (200, 313, "512")):
+        with pytest.raises(NotImplementedError, match=limit):
+            legacy_rendering.render_rays([None, None], [None, None], rays, N_samples=nc, N_importance=nf)
+    with pytest.raises(Exception) as e:         # admitted: gets as far as the GPU check
+        legacy_rendering.render_rays([None, None], [None, None], rays, N_samples=512, N_importance=0)
+    assert not isinstance(e.value, NotImplementedError)

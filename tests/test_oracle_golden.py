@@ -218,6 +218,11 @@ def sum_mode(request):
 def test_g11_model(golden_dir, fixture, sum_mode):
     g = load(golden_dir, fixture)
     case = [c for c in sorted(CASES, key=len, reverse=True) if fixture.startswith("g11_model_" + c + "_")][0]
+    check_model_fixture(g, case, sum_mode)
+
+
+def check_model_fixture(g, case, sum_mode):
+    """The oracle's NerfModel forward, loss and gradients against a g11-layout model fixture."""
     nc, nf, b, seed = int(g["nc"]), int(g["nf"]), int(g["b"]), int(g["seed"])
     kw = dict(CASES[case])
     cfg = O.ModelCfg(n_samples_coarse=nc, n_samples_fine=nf, view_fourier_dim=6,
@@ -350,3 +355,46 @@ def test_g16_filter_sigma(golden_dir):
         r = O.volumetric_rendering(T(g["rgb"]), f, T(g["z"]), T(g["d"]), white_bg=False, sample_at_infinity=True)
         for k, v in r.items():
             close(v, g[f"{k}_{tag}"], rtol=1e-6, atol=1e-6)
+
+
+# ---- G19: long rays (tests/golden/make_long_rays_golden.py) ---------------------------------------------------------
+def test_g19_long_rays_compositing(golden_dir):
+    """volumetric_rendering and the median index at 256, 257, 384 and 512 samples per ray."""
+    g = load(golden_dir, "g19_long_rays")
+    for s in (256, 257, 384, 512):
+        pre = f"comp/S{s}/"
+        for inf in (True, False):
+            for wb in (True, False):
+                tag = f"{pre}inf{int(inf)}_wb{int(wb)}/"
+                r = O.volumetric_rendering(T(g[pre + "rgb"]), T(g[pre + "sigma"]), T(g[pre + "z"]), T(g[pre + "d"]),
+                                           white_bg=wb, sample_at_infinity=inf)
+                for k, v in r.items():
+                    close(v, g[tag + k], rtol=1e-6, atol=1e-6)
+                _, di = O.median_depth_index(r["weights"])
+                assert np.array_equal(di.numpy(), g[tag + "dindex"]), tag
+
+
+def test_g19_long_rays_sampler(golden_dir, sum_mode):
+    """Inverse-CDF sampling + merge in the fused shape at nc = 256 / 257 coarse and 512 - nc fine samples: indices
+    bit-exact in both normaliser modes (every u lies > 1e-5 from every cdf entry).  Depths 1e-6 under refsum; 5e-5
+    under fp64sum, where a 1-ulp normaliser change moves a sample by up to (b1 - b0) ulp / (cdf1 - cdf0) — 8e-6 at
+    the narrowest cdf step of these rays (weights w^3)."""
+    g = load(golden_dir, "g19_long_rays")
+    tol = 1e-6 if sum_mode == "refsum" else 5e-5
+    for nc in (256, 257):
+        pre = f"pdf/nc{nc}/"
+        z, w, u = T(g[pre + "z"]), T(g[pre + "w"]), T(g[pre + "u"])
+        mid = 0.5 * (z[:, 1:] + z[:, :-1])
+        zs, inds = O.piecewise_constant_pdf(mid, w[:, 1:-1], u)
+        assert np.array_equal(inds.numpy(), g[pre + "inds"]), f"nc {nc} ({sum_mode}): indices"
+        close(zs, g[pre + "z_samples"], rtol=tol, atol=tol)
+        z_all, pts, inds2 = O.sample_pdf(mid, w[:, 1:-1], T(g[pre + "o"]), T(g[pre + "d"]), z, u)
+        assert torch.equal(inds2, inds)
+        close(z_all, g[pre + "z_all"], rtol=tol, atol=tol)
+        close(pts, g[pre + "pts"], rtol=tol, atol=tol)
+
+
+def test_g19_long_rays_model(golden_dir, sum_mode):
+    """A bendy_cond NerfModel at 257 + 255 samples per ray (4 rays), as the g11 fixtures."""
+    g = load(golden_dir, "g19_long_rays")
+    check_model_fixture({k[len("model/"):]: v for k, v in g.items() if k.startswith("model/")}, "bendy_cond", sum_mode)
