@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the HyperNeRF render hot path on MI355X (BASELINE.json metric: ray-samples/s, forward + backward).
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,5}] [--full]
 N>1: one rank per GPU over RCCL.  Under `torch.distributed.run` (WORLD_SIZE set) this process IS a rank; started
 plainly, `--gpus N` makes it the LAUNCHER (the reference's Lightning Trainer spawns `devices=num_gpus` ranks itself,
 train.py:224-229): it starts N child rank processes BEFORE any GPU call of its own, relays rank 0's JSON line and
@@ -21,9 +21,13 @@ bracketed by barrier + synchronize, after untimed replays (SETTLE_RAY_SAMPLES) t
 timed step computed (the step's outputs, its loss and the updated weights) as DIR/<name>.npy; inputs and weights are
 seeded, so two builds run with the same arguments can be compared output for output.
 With N>1 over RCCL the whole step — forward, backward, gradient all-reduce, Adam — is ONE HIP graph (the collective is
-captured with it; `config.dp_step` says which form ran).  The default single-GPU config-2 run appends an `also` block to
-its line: configs 3, 5, 1 and the eval image loop as short child runs (`--no-also` skips it), so that the one command
-the driver runs measures every single-GPU configuration of BASELINE.json.
+captured with it; `config.dp_step` says which form ran).
+A plain run does only what the headline needs: set-up, warm-up, the settle replays, the timed steps, the dump, the line.
+`--full` adds everything else this file measures, each part behind its own switch: the box calibration
+(`--no-calibration`), the per-kernel roofline with its eager pass (`--no-roofline`), the CPU oracle baseline and its
+check (`--no-cpu-baseline`) and, on the default single-GPU config-2 run, the `also` block: configs 3, 5, 1 and the eval
+image loop as short child runs (`--no-also`), so that one command measures every single-GPU configuration of
+BASELINE.json.  The timed steps are the same either way.
 """
 import argparse
 import ctypes
@@ -70,11 +74,15 @@ def parse():
     ap.add_argument("--precision", default=None, choices=["bf16", "fp32", "bf16s8"],
                     help="bf16s8: OPT-IN variant of bf16 with the training stash in 8 bits (HN_MODE_BF16_S8) — never the default, "
                          "reported as dtype 'bf16 (8-bit stash: e4m3 X, e5m2 dZ)'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure the box calibration, the per-kernel roofline, the CPU baseline and "
+                         "(default config-2 run) the `also` block; each can still be skipped with its --no-* switch")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline and its check")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="skip the roofline (--full) and keep the machine kernels' self-timing out of the timed steps")
     ap.add_argument("--no-calibration", action="store_true",
-                    help="skip the box calibration (MFMA / HBM-stream probes before the timed region, hwmon power and "
-                         "clock during it)")
+                    help="--full: skip the box calibration (MFMA / HBM-stream probes before the timed region, hwmon power "
+                         "and clock during it)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying a HIP graph")
     ap.add_argument("--overlap", action="store_true",
                     help="data-parallel runs: all-reduce the gradient buffer in two buckets, the first in flight while the "
@@ -87,8 +95,8 @@ def parse():
     ap.add_argument("--launch-plan", action="store_true",
                     help="print the rank launch plan of --gpus N (commands + per-rank environment) as JSON and exit")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the `also` block (short lines for BASELINE configs 3, 5, 1 and the eval image loop that the "
-                         "default config-2 run appends to its JSON line)")
+                    help="--full: skip the `also` block (short lines for BASELINE configs 3, 5, 1 and the eval image loop "
+                         "that the default config-2 run appends to its JSON line)")
     ap.add_argument("--no-capture-collective", action="store_true",
                     help="data-parallel runs: keep the gradient all-reduce OUT of the step graph (graph | eager all-reduce "
                          "| graph) instead of capturing it with the step")
@@ -348,7 +356,11 @@ def main():
     HN.set_precision(a.precision)
     # the three machine kernels time themselves (HnMlpArgs.timeline): per-kernel durations of the TIMED graph replays,
     # not of a second, eager pass.  Enabled before the step is captured (the slots' addresses are baked into the graph).
+    # A plain run reports no per-kernel figures but keeps the timeline on: its timed kernels are those of a --full run.
     L.TIMELINE = {} if not a.no_roofline else None
+    # what a --full run adds to the headline (the module docstring)
+    calibrate = a.full and not a.no_calibration
+    cpu_check = a.full and not a.no_cpu_baseline and rank == 0 and world == 1
     from hypernerf_torch_amd import functional as HF0
     if a.fork_wgrad:
         HF0.set_wgrad_overlap(True)
@@ -363,7 +375,7 @@ def main():
         dist.broadcast(arena.data, src=0)
     # the weights BEFORE any training step: what cpu_baseline.check renders with (the check measures the kernels'
     # arithmetic against the oracle's, not how far ~130 bf16 training steps have carried two trajectories apart)
-    init_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    init_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if cpu_check else None
     from hypernerf_torch_amd import optim as HO
     # one GPU: the launch that completes the gradient also applies Adam (hn_mlp_wgrad_reduce_adam); with an all-reduce
     # between backward and the optimizer the two launches stay
@@ -459,7 +471,7 @@ def main():
         except OSError:
             pass
     calibration = None
-    if not a.no_calibration:
+    if calibrate:
         from hypernerf_torch_amd import calibration as CAL
         if rank == 0:
             calibration = CAL.probes(dev)
@@ -475,7 +487,7 @@ def main():
     if L.TIMELINE is not None:
         L.timeline_reset()
     sampler = None
-    if rank == 0 and not a.no_calibration:
+    if rank == 0 and calibrate:
         sampler = CAL.PowerSampler(dev).__enter__()
     for _ in range(n_settle):
         step()
@@ -512,7 +524,7 @@ def main():
     if a.dump_outputs and rank == 0:
         # copied now: the untimed steps below replay the same graph into the same output buffers
         dumped = dump_outputs(a.dump_outputs, out, loss, arena)
-    if not a.no_calibration:
+    if calibrate:
         # ... on every rank, the same number of steps (fixed from the max-over-ranks step time: collectives inside)
         n_soak = max(20, int(CALIB_SOAK_S / max(1e-6, statistics.median(reps))))
         soak = CAL.PowerSampler(dev).__enter__() if rank == 0 else None
@@ -552,7 +564,7 @@ def main():
     res["build"] = L.build_id()
     if calibration is not None:
         res["calibration"] = calibration
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         # per-kernel times of the machine kernels come from the timed region itself (kernel timeline); the eager pass
         # (HIP events around every C-ABI launch) adds the small kernels' list at N = 1 only — with N > 1 every rank
         # goes straight to the final barrier, no rank waits for another's rank-local work
@@ -563,9 +575,9 @@ def main():
             res["roofline"]["scope"] = f"rank 0 (1 of {world} GPUs): its own kernels inside the timed region"
             if "hbm" in res:
                 res["hbm"]["scope"] = res["roofline"]["scope"]
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if cpu_check:
         res["cpu_baseline"] = cpu_baseline(a, model, data, dev, init_state, arena)
-    if (rank == 0 and world == 1 and not dp and not a.no_also and a.config == 2 and a.precision == "bf16"
+    if (a.full and rank == 0 and world == 1 and not dp and not a.no_also and a.config == 2 and a.precision == "bf16"
             and a.rays == CONFIGS[2]["rays"] and use_graph):
         # the headline run is over; its ~10 GB stay allocated beside the children's (config 3: a 60 GB stash of 288).
         # The headline must survive whatever happens to the extras: if this process is told to stop while the children
@@ -654,8 +666,8 @@ ALSO_BUDGET_S = 60.0        # the whole block; a child that would start later is
 
 
 def also_block():
-    """The driver runs ONE command (`python bench.py`, BASELINE config 2).  Four of the five BASELINE configurations and
-    the evaluation loop would otherwise only ever be builder-run lines under profiles/: the default run therefore
+    """`python bench.py --full` at BASELINE config 2 measures every single-GPU configuration in one command: four of the
+    five BASELINE configurations and the evaluation loop would otherwise only ever be lines under profiles/, so the run
     appends short measurements of configs 3, 5, 1 (<= 30 timed steps in 3 windows, HIP-graph replay, no CPU baseline) and of
     `inference.render_image` (tools/eval_bench.py) — each its own child process, started after the headline has been
     measured (its ~10 GB of device memory stay allocated next to the children's; ordinary children, never an exec),
@@ -677,7 +689,8 @@ def also_block():
         if argv is None:
             cmd = [sys.executable, os.path.join(ROOT, "tools", "eval_bench.py"), "32768", "3"]
         else:
-            cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--no-also", "--no-calibration"]
+            cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--full", "--no-cpu-baseline", "--no-also",
+                                                                        "--no-calibration"]      # --full: the roofline
         try:
             t1 = time.perf_counter()
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=min(40.0, left))

@@ -795,6 +795,28 @@ def test_bench_launches_its_own_ranks():
     assert line["value"] > 0 and np.isfinite(line["final_loss"])
 
 
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain `bench.py` run carries the headline and nothing that needs work of its own; `--full` adds the box
+    calibration and the per-kernel roofline (the CPU baseline and the `also` block are skipped here for time)."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+
+    def line_of(*extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup",
+                              "2", "--repeats", "2", *extra], capture_output=True, text=True, env=env, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.strip().splitlines()[-1])
+    plain = line_of()
+    assert plain["metric"].startswith("ray-samples/sec") and plain["unit"] == "ray-samples/s"
+    assert plain["higher_is_better"] is True and plain["dtype"] == "bf16" and plain["steps"] == 4
+    assert plain["ms_per_step"] > 0 and plain["value"] == pytest.approx(1024 * 128 / (plain["ms_per_step"] * 1e-3))
+    assert not {"roofline", "calibration", "cpu_baseline", "also", "step_mfma_frac"} & set(plain)
+    full = line_of("--full", "--no-cpu-baseline", "--no-also")
+    assert full["ms_per_step"] > 0 and full["roofline"]["bound"] == "mfma" and full["step_mfma_frac"] > 0
+    assert full["calibration"]["mfma_probe_tflops"] > 0 and "soak" in full["calibration"]
+    assert not {"cpu_baseline", "also"} & set(full)
+
+
 def test_checkpoint_into_the_hip_model_renders_like_the_oracle(tmp_path):
     """SURVEY.md §8 f3 on the GPU: a Lightning-layout checkpoint ({'state_dict': {'nerf.<name>': ...}}, train.py:48,
     200-204) holding hash weights -> utils.load_ckpt into an ARENA-backed NerfModel already on the device -> the HIP

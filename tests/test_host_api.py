@@ -380,7 +380,7 @@ def test_bench_launch_plan():
 
 
 def test_bench_also_block_host_logic(monkeypatch):
-    """The `also` block the default `python bench.py` appends to its line (configs 3, 5, 1 + the eval image loop as child
+    """The `also` block `python bench.py --full` appends to its line (configs 3, 5, 1 + the eval image loop as child
     processes): entries are built from the children's own JSON lines, a child that fails or times out becomes an
     `error` / `skipped` entry instead of costing the headline, the flags every child gets keep it from recursing or
     timing the CPU oracle, and the block stops starting children when its time budget is spent."""
@@ -425,6 +425,30 @@ def test_bench_also_block_host_logic(monkeypatch):
     monkeypatch.setattr(bench, "ALSO_BUDGET_S", 0.0)
     out = bench.also_block()
     assert not calls and all("skipped" in out[k] for k in ("config3", "config5", "config1", "render_image"))
+
+
+def test_bench_full_is_opt_in(monkeypatch):
+    """A plain `bench.py` run is headline-only; `--full` opts into the rest.  The `also` block's children run with
+    `--full` so that their entries keep the dominant kernel's roofline."""
+    import importlib.util
+    import subprocess
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod_full", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+    cmds = []
+
+    def fake_run(cmd, capture_output, text, timeout):
+        cmds.append(cmd)
+        return subprocess.CompletedProcess(cmd, 1, "", "")
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    bench.also_block()
+    kids = [c for c in cmds if os.path.basename(c[1]) == "bench.py"]
+    assert len(kids) == 3 and all("--full" in c and "--no-also" in c for c in kids)
 
 
 def test_bench_dump_outputs(tmp_path, monkeypatch):

@@ -23,7 +23,7 @@ if [ -n "$KEXPR" ]; then
 fi
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
-    env $(envs_of "$v") timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-also --no-calibration $BARGS 2>/dev/null | tail -1 | \
+    env $(envs_of "$v") timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-also --no-calibration $BARGS 2>/dev/null | tail -1 | \
       AB_LABEL="${v%%:*}" python tools/ab_line.py
   done
 done | tee /tmp/ab_lines.$$
