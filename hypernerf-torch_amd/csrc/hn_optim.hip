@@ -1,0 +1,233 @@
+// Fused SGD, RAdam and Ranger over a flat parameter arena: the other three optimizers of the reference's get_optimizer
+// (utils/__init__.py:23-41; RAdam and Ranger from utils/optimizers.py:6-95 and :266-405), built like hn_adam_kernel
+// (hn_render.hip): a grid-stride pass of at most 256 blocks x 256 threads over f32x4 vectors (scalar tail), the step
+// counter on the device and advanced by the last block (hn_adam_ticket), the gradient cleared on the way out.
+//
+// The reference computes its schedule scalars (beta^t, N_sma, the step size and the products with lr) as Python doubles
+// and hands them to fp32 tensor ops, which round them once.  Here thread 0 of every block does the same in fp64 from the
+// device step counter and the fp64 hyper-parameter array, rounds each coefficient to fp32 once and passes them and the
+// branch flags to the block through LDS.  (fp32 is not enough: for beta2 = 0.999 it puts N_sma at t = 6 at 6.0005
+// instead of 5.9942, and the first rectified step size 0.3 % off.)  The per-element arithmetic is the reference's fp32
+// tensor arithmetic, operation for operation.
+#include "hn_common.h"
+
+// ------------------------------------------------------------------------------------------------
+// SGD (torch.optim.SGD, which get_optimizer builds directly): d = g*gscale + wd*p; with momentum buf = d on update 1,
+// buf = momentum*buf + (1-dampening)*d after that; d = d + momentum*buf (Nesterov) or buf; p += (-lr)*d.
+// ------------------------------------------------------------------------------------------------
+struct HnSgdCoef {
+  float gscale, wd, momentum, one_m_damp, neg_lr, t;
+  int use_buf, first, nesterov;
+};
+
+HN_DEV void hn_sgd_update(const HnSgdCoef& c, float& p, float g, float* buf) {
+  float d = g * c.gscale;
+  d = d + c.wd * p;
+  if (c.use_buf) {
+    float b = c.first ? d : *buf * c.momentum + c.one_m_damp * d;
+    *buf = b;
+    d = c.nesterov ? d + c.momentum * b : b;
+  }
+  p = p + c.neg_lr * d;
+}
+
+__global__ __launch_bounds__(256) void hn_sgd_kernel(float* p, float* g, float* buf, long long n,
+                                                      const double* __restrict__ hyper, float* step, int zero_grad) {
+  __shared__ HnSgdCoef sc;
+  if (threadIdx.x == 0) {
+    // every block reads step[0] here, before its ticket; the block that finishes LAST advances it
+    const double lr = hyper[0], momentum = hyper[1], dampening = hyper[2], wd = hyper[3];
+    HnSgdCoef c;
+    c.t = step[0] + 1.0f;
+    c.gscale = (float)hyper[5];
+    c.wd = (float)wd;
+    c.momentum = (float)momentum;
+    c.one_m_damp = (float)(1.0 - dampening);
+    c.neg_lr = (float)(-lr);
+    c.use_buf = (momentum != 0.0 && buf != nullptr) ? 1 : 0;
+    c.first = c.t == 1.0f;
+    c.nesterov = hyper[4] != 0.0;
+    sc = c;
+  }
+  __syncthreads();
+  const HnSgdCoef k = sc;
+  const long long stride = (long long)gridDim.x * blockDim.x * 4;
+  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<f32x4*>(g + i);
+      if (k.use_buf) {
+        f32x4 bb = k.first ? f32x4{0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<f32x4*>(buf + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = pp[e], be = bb[e];
+          hn_sgd_update(k, pe, gg[e], &be);
+          pp[e] = pe; bb[e] = be;
+        }
+        *reinterpret_cast<f32x4*>(buf + i) = bb;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float pe = pp[e];
+          hn_sgd_update(k, pe, gg[e], nullptr);
+          pp[e] = pe;
+        }
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pp;
+      if (zero_grad) *reinterpret_cast<f32x4*>(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      for (long long j = i; j < n; ++j) {
+        hn_sgd_update(k, p[j], g[j], k.use_buf ? buf + j : nullptr);
+        if (zero_grad) g[j] = 0.f;
+      }
+    }
+  }
+  hn_adam_ticket(step, k.t);
+}
+
+extern "C" int hn_sgd_step(float* params, float* grads, float* momentum_buf, long long n, const double* hyper_dev,
+                           float* step_dev, int zero_grad, hnStream_t stream) {
+  if (n <= 0) return -2;
+  if (params == nullptr || grads == nullptr || hyper_dev == nullptr || step_dev == nullptr) return -3;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) != 0 || ((uintptr_t)hyper_dev & 7) != 0 ||
+      ((uintptr_t)step_dev & 3) != 0)
+    return -4;
+  long long blocks = (n / 4 + 255) / 256;
+  if (blocks > 256) blocks = 256;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(hn_sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads,
+                     momentum_buf, n, hyper_dev, step_dev, zero_grad);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// RAdam (utils/optimizers.py:29-95) and Ranger = RAdam + lookahead (:322-405).  Per element, in the reference's order:
+//   v = v*b2 + ((1-b2)*g)*g;  m = m*b1 + (1-b1)*g
+//   weight decay (RAdam: only when an update happens; Ranger: always):  p = p + (-wd*lr)*p
+//   rectified (RAdam N_sma >= 5, Ranger N_sma > threshold):  p = p + ((-step_size*lr)*m) / (sqrt(v) + eps)
+//   otherwise (degenerated to SGD):                          p = p + (-step_size*lr)*m
+//   RAdam with degenerated_to_sgd = False below the threshold: no update at all.
+//   Ranger: slow = p before update 1; after every update t with t % k == 0: slow = slow + alpha*(p - slow), p = slow.
+// ------------------------------------------------------------------------------------------------
+struct HnRadamCoef {
+  float gscale, b1, b2, one_m_b1, one_m_b2, eps, neg_step_lr, neg_wd_lr, alpha, t;
+  int rect, update, decay, first, sync;
+};
+
+HN_DEV void hn_radam_update(const HnRadamCoef& c, float& p, float g, float& m, float& v) {
+  g = g * c.gscale;
+  v = v * c.b2 + c.one_m_b2 * g * g;
+  m = m * c.b1 + c.one_m_b1 * g;
+  if (c.decay) p = p + c.neg_wd_lr * p;
+  if (c.rect) {
+    const float denom = sqrtf(v) + c.eps;
+    p = p + c.neg_step_lr * m / denom;
+  } else if (c.update) {
+    p = p + c.neg_step_lr * m;
+  }
+}
+
+template <bool RANGER>
+__global__ __launch_bounds__(256) void hn_radam_kernel(float* p, float* g, float* m, float* v, float* slow, long long n,
+                                                        int k_la, const double* __restrict__ hyper, float* step,
+                                                        int zero_grad) {
+  __shared__ HnRadamCoef sc;
+  if (threadIdx.x == 0) {
+    const double lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], wd = hyper[4];
+    HnRadamCoef c;
+    c.t = step[0] + 1.0f;
+    const double t = (double)c.t;
+    const double beta2_t = pow(beta2, t);
+    const double n_sma_max = 2.0 / (1.0 - beta2) - 1.0;
+    const double n_sma = n_sma_max - 2.0 * t * beta2_t / (1.0 - beta2_t);
+    const bool rect = RANGER ? n_sma > hyper[6] : n_sma >= 5.0;
+    double step_size;
+    if (rect)
+      step_size = sqrt((1.0 - beta2_t) * (n_sma - 4.0) / (n_sma_max - 4.0) * (n_sma - 2.0) / n_sma * n_sma_max /
+                       (n_sma_max - 2.0)) /
+                  (1.0 - pow(beta1, t));
+    else if (RANGER || hyper[7] != 0.0)
+      step_size = 1.0 / (1.0 - pow(beta1, t));
+    else
+      step_size = -1.0;
+    c.rect = rect;
+    c.update = rect || step_size > 0.0;
+    c.decay = wd != 0.0 && (RANGER || c.update);
+    c.gscale = (float)hyper[5];
+    c.b1 = (float)beta1;
+    c.b2 = (float)beta2;
+    c.one_m_b1 = (float)(1.0 - beta1);
+    c.one_m_b2 = (float)(1.0 - beta2);
+    c.eps = (float)hyper[3];
+    c.neg_step_lr = (float)(-step_size * lr);
+    c.neg_wd_lr = (float)(-wd * lr);
+    c.alpha = (float)hyper[8];
+    c.first = RANGER && c.t == 1.0f;
+    c.sync = RANGER && ((long long)c.t % (long long)k_la) == 0;
+    sc = c;
+  }
+  __syncthreads();
+  const HnRadamCoef k = sc;
+  const long long stride = (long long)gridDim.x * blockDim.x * 4;
+  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<f32x4*>(g + i);
+      f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
+      // update 1 and lookahead updates only (uniform across the grid): the slow buffer
+      f32x4 ss = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (RANGER && (k.first || k.sync)) ss = k.first ? pp : *reinterpret_cast<f32x4*>(slow + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        hn_radam_update(k, pe, gg[e], me, ve);
+        if (RANGER && k.sync) {
+          ss[e] = ss[e] + k.alpha * (pe - ss[e]);
+          pe = ss[e];
+        }
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pp;
+      *reinterpret_cast<f32x4*>(m + i) = mm;
+      *reinterpret_cast<f32x4*>(v + i) = vv;
+      if (RANGER && (k.first || k.sync)) *reinterpret_cast<f32x4*>(slow + i) = ss;
+      if (zero_grad) *reinterpret_cast<f32x4*>(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      for (long long j = i; j < n; ++j) {
+        float s = 0.f;
+        if (RANGER && (k.first || k.sync)) s = k.first ? p[j] : slow[j];
+        float pj = p[j];
+        hn_radam_update(k, pj, g[j], m[j], v[j]);
+        if (RANGER && k.sync) {
+          s = s + k.alpha * (pj - s);
+          pj = s;
+        }
+        p[j] = pj;
+        if (RANGER && (k.first || k.sync)) slow[j] = s;
+        if (zero_grad) g[j] = 0.f;
+      }
+    }
+  }
+  hn_adam_ticket(step, k.t);
+}
+
+extern "C" int hn_radam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* slow, long long n,
+                             int k, const double* hyper_dev, float* step_dev, int zero_grad, hnStream_t stream) {
+  if (n <= 0 || k < 1) return -2;
+  if (params == nullptr || grads == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || hyper_dev == nullptr ||
+      step_dev == nullptr)
+    return -3;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)slow) & 15) != 0 ||
+      ((uintptr_t)hyper_dev & 7) != 0 || ((uintptr_t)step_dev & 3) != 0)
+    return -4;
+  long long blocks = (n / 4 + 255) / 256;
+  if (blocks > 256) blocks = 256;
+  if (blocks < 1) blocks = 1;
+  if (slow != nullptr)
+    hipLaunchKernelGGL(hn_radam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads,
+                       exp_avg, exp_avg_sq, slow, n, k, hyper_dev, step_dev, zero_grad);
+  else
+    hipLaunchKernelGGL(hn_radam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads,
+                       exp_avg, exp_avg_sq, slow, n, k, hyper_dev, step_dev, zero_grad);
+  HN_CHECK_LAUNCH();
+  return 0;
+}

@@ -1,7 +1,8 @@
 """Fused Adam on a ParamArena: one HIP kernel updates every parameter of the model and clears the
 gradient buffer for the next step (`hn_adam_step`).  Same update rule and defaults as torch.optim.Adam, which is what
 the reference's `get_optimizer` builds (utils/__init__.py:23-41), and `MultiStepLR` — its 'steplr' scheduler
-(utils/__init__.py:43-46).
+(utils/__init__.py:43-46).  The other optimizers `get_optimizer` can build — SGD, RAdam, Ranger — follow below
+(`ArenaSGD`, `ArenaRAdam`, `ArenaRanger`, `get_optimizer`), with the rest of its schedulers.
 
 Everything a captured launch depends on lives ON THE DEVICE: the step counter and the hyper-parameters
 [lr, beta1, beta2, eps, weight_decay, grad_scale].  `param_groups[0]` stays the user-facing source of truth (torch
@@ -280,3 +281,235 @@ def get_scheduler(hparams, optimizer):
     if warm:
         sch = GradualWarmup(optimizer, hparams.warmup_multiplier, hparams.warmup_epochs, sch)
     return sch
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the other optimizers of the reference's get_optimizer (utils/__init__.py:23-41): torch.optim.SGD, RAdam and Ranger
+# (utils/optimizers.py:6-95, 266-405), each one HIP launch over the arena (hn_sgd_step / hn_radam_step,
+# csrc/hn_optim.hip).  Same protocol as ArenaAdam: `param_groups[0]` is the source of truth, `sync_hyper()` uploads it
+# (as doubles: the kernels compute the schedule scalars in fp64, as the reference does in Python), the step counter
+# lives on the device.  A pending reduce of the arena's gradient is completed first (no fused form for these).
+# ------------------------------------------------------------------------------------------------------------------
+class _ArenaOptimizer:
+    _N_HYPER = 8
+    _STATE = ()                 # names of the flat state tensors, in state_dict order
+
+    def _setup(self, arena: ParamArena, group: dict, zero_grad: bool, grad_scale: float):
+        L.require_gpu(arena.data)
+        self.arena = arena
+        self.param_groups = [group]
+        self.grad_scale = float(grad_scale)        # 1 / world size when the gradients arrive SUM-all-reduced
+        self.zero_grad_in_step = zero_grad
+        dev = arena.data.device
+        self._step_words = torch.zeros(2, dtype=torch.float32, device=dev)      # [updates done, ticket counter]
+        self.step_count = self._step_words[:1]
+        self.hyper = torch.zeros(self._N_HYPER, dtype=torch.float64, device=dev)
+        self._uploaded = None
+
+    def _hyper_values(self):
+        raise NotImplementedError
+
+    def sync_hyper(self) -> bool:
+        """Upload the hyper-parameters if they changed since the last upload (never while a stream capture is in
+        progress: a captured copy would freeze the values into the graph)."""
+        vals = self._hyper_values()
+        if vals == self._uploaded:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise L.HnError(f"{type(self).__name__}: hyper-parameters changed inside a stream capture; "
+                            "call sync_hyper() before")
+        self.hyper.copy_(torch.tensor(vals, dtype=torch.float64))
+        self._uploaded = vals
+        return True
+
+    def _launch(self):
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def step(self):
+        L.load()
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyper()
+        from . import machine
+        machine.flush_pending_reduce(self.arena.grad)
+        self._launch()
+        self.arena.bump()
+
+    def finish_gradients(self):
+        from . import machine
+        machine.flush_pending_reduce(self.arena.grad)
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.arena.zero_grad()
+
+    def state_tensors(self):
+        """Every device tensor the optimizer's state lives in (the step counter included): what a caller saves and
+        restores around warm-up runs of a graph capture (training.TrainStep)."""
+        return [t for t in (getattr(self, n) for n in self._STATE) if t is not None] + [self._step_words]
+
+    def state_dict(self):
+        sd = {n: getattr(self, n) for n in self._STATE}
+        sd["step"] = self.step_count
+        sd["param_groups"] = self.param_groups
+        return sd
+
+    def load_state_dict(self, sd):
+        for n in self._STATE:
+            dst = getattr(self, n)
+            if (dst is None) != (sd.get(n) is None):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: '{n}' present in one state but not the other")
+            if dst is not None:
+                dst.copy_(sd[n])
+        self.step_count.copy_(sd["step"])
+        self.param_groups = [dict(g) for g in sd["param_groups"]]
+        self.sync_hyper()
+
+
+class ArenaSGD(_ArenaOptimizer):
+    """torch.optim.SGD (get_optimizer's 'sgd': momentum and weight_decay from hparams) over a ParamArena."""
+    _STATE = ("momentum_buffer",)
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-3, momentum: float = 0, dampening: float = 0,
+                 weight_decay: float = 0, nesterov: bool = False, zero_grad: bool = True, grad_scale: float = 1.0):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        self._setup(arena, {"lr": lr, "momentum": momentum, "dampening": dampening, "weight_decay": weight_decay,
+                            "nesterov": bool(nesterov)}, zero_grad, grad_scale)
+        # torch keeps no momentum buffer when momentum is 0: neither does this (16 B per parameter instead of 24)
+        self.momentum_buffer = torch.zeros_like(arena.data) if momentum != 0 else None
+        self.sync_hyper()
+
+    def _hyper_values(self):
+        g = self.param_groups[0]
+        if g["momentum"] != 0 and self.momentum_buffer is None:
+            raise ValueError("ArenaSGD: momentum switched on after construction with momentum 0 (no momentum buffer)")
+        return (float(g["lr"]), float(g["momentum"]), float(g["dampening"]), float(g["weight_decay"]),
+                1.0 if g["nesterov"] else 0.0, float(self.grad_scale), 0.0, 0.0)
+
+    def _launch(self):
+        a = self.arena
+        L.launch("hn_sgd_step", L.ptr(a.data), L.ptr(a.grad), L.ptr(self.momentum_buffer), C.c_longlong(a.numel),
+                 L.ptr(self.hyper), L.ptr(self._step_words), C.c_int(int(self.zero_grad_in_step)), L.stream_handle())
+
+
+def _check_radam_args(lr, betas, eps):
+    if not 0.0 <= lr:
+        raise ValueError("Invalid learning rate: {}".format(lr))
+    if not 0.0 <= eps:
+        raise ValueError("Invalid epsilon value: {}".format(eps))
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError("Invalid beta parameter at index 0: {}".format(betas[0]))
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError("Invalid beta parameter at index 1: {}".format(betas[1]))
+
+
+class ArenaRAdam(_ArenaOptimizer):
+    """The reference's RAdam (utils/optimizers.py:6-95) over a ParamArena, operation for operation: rectified update
+    when N_sma >= 5, otherwise the degenerated-to-SGD update (or none at all with degenerated_to_sgd=False); decoupled
+    weight decay p += (-wd*lr)*p, applied only when an update happens."""
+    _N_HYPER = 12
+    _STATE = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0, degenerated_to_sgd: bool = True, zero_grad: bool = True,
+                 grad_scale: float = 1.0):
+        _check_radam_args(lr, betas, eps)
+        self.degenerated_to_sgd = bool(degenerated_to_sgd)
+        self._setup(arena, {"lr": lr, "betas": tuple(betas), "eps": eps, "weight_decay": weight_decay},
+                    zero_grad, grad_scale)
+        self._init_state()
+
+    def _init_state(self):
+        self.exp_avg = torch.zeros_like(self.arena.data)
+        self.exp_avg_sq = torch.zeros_like(self.arena.data)
+        self.sync_hyper()
+
+    def _hyper_values(self):
+        g = self.param_groups[0]
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                float(g["weight_decay"]), float(self.grad_scale), 5.0, 1.0 if self.degenerated_to_sgd else 0.0,
+                0.0, 0.0, 0.0, 0.0)
+
+    def _slow(self):
+        return None
+
+    def _k(self) -> int:
+        return 1
+
+    def _launch(self):
+        a = self.arena
+        L.launch("hn_radam_step", L.ptr(a.data), L.ptr(a.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                 L.ptr(self._slow()), C.c_longlong(a.numel), C.c_int(self._k()), L.ptr(self.hyper),
+                 L.ptr(self._step_words), C.c_int(int(self.zero_grad_in_step)), L.stream_handle())
+
+
+class ArenaRanger(ArenaRAdam):
+    """The reference's Ranger (utils/optimizers.py:266-405): RAdam with the threshold N_sma > N_sma_threshhold, weight
+    decay on every step, and lookahead — the slow buffer takes the parameters before update 1, and after every update
+    t with t % k == 0 moves alpha of the way to them and is copied back.  (`N_sma_threshhold`: the reference's
+    spelling.)  `k` is a launch argument: a captured step keeps the k it was captured with."""
+    _STATE = ("exp_avg", "exp_avg_sq", "slow_buffer")
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-3, alpha: float = 0.5, k: int = 6, N_sma_threshhold=5,
+                 betas=(.95, 0.999), eps: float = 1e-5, weight_decay: float = 0, zero_grad: bool = True,
+                 grad_scale: float = 1.0):
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f'Invalid slow update rate: {alpha}')
+        if not 1 <= k:
+            raise ValueError(f'Invalid lookahead steps: {k}')
+        if not lr > 0:
+            raise ValueError(f'Invalid Learning Rate: {lr}')
+        if not eps > 0:
+            raise ValueError(f'Invalid eps: {eps}')
+        self.N_sma_threshhold = N_sma_threshhold
+        self._setup(arena, {"lr": lr, "alpha": alpha, "k": int(k), "step_counter": 0, "betas": tuple(betas),
+                            "N_sma_threshhold": N_sma_threshhold, "eps": eps, "weight_decay": weight_decay},
+                    zero_grad, grad_scale)
+        self.slow_buffer = torch.zeros_like(arena.data)      # set to the parameters by update 1 (in the kernel)
+        self._init_state()
+
+    def _hyper_values(self):
+        g = self.param_groups[0]
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                float(g["weight_decay"]), float(self.grad_scale), float(g["N_sma_threshhold"]), 1.0,
+                float(g["alpha"]), 0.0, 0.0, 0.0)
+
+    def _slow(self):
+        return self.slow_buffer
+
+    def _k(self) -> int:
+        return int(self.param_groups[0]["k"])
+
+
+OPTIMIZERS = ("sgd", "adam", "radam", "ranger")
+
+
+def make_optimizer(name: str, arena: ParamArena, lr: float, eps: float = 1e-8, weight_decay: float = 0.0,
+                   momentum: float = 0.9, **kw):
+    """The optimizer `name` of the reference's get_optimizer with its arguments: 'sgd' takes lr, momentum and
+    weight_decay, 'adam' / 'radam' / 'ranger' lr, eps and weight_decay (everything else at the class defaults).
+    `kw` (zero_grad, grad_scale) goes to the constructor."""
+    if name not in OPTIMIZERS:
+        raise ValueError('optimizer not recognized!')
+    if name == 'sgd':
+        return ArenaSGD(arena, lr=lr, momentum=momentum, weight_decay=weight_decay, **kw)
+    if name == 'adam':
+        return ArenaAdam(arena, lr=lr, eps=eps, weight_decay=weight_decay, **kw)
+    if name == 'radam':
+        return ArenaRAdam(arena, lr=lr, eps=eps, weight_decay=weight_decay, **kw)
+    return ArenaRanger(arena, lr=lr, eps=eps, weight_decay=weight_decay, **kw)
+
+
+def get_optimizer(hparams, arena: ParamArena, **kw):
+    """The reference's get_optimizer (utils/__init__.py:23-41) on a ParamArena: hparams needs `optimizer`, `lr`,
+    `weight_decay` and, for 'sgd', `momentum`.  An unknown name raises before any device work."""
+    if hparams.optimizer not in OPTIMIZERS:
+        raise ValueError('optimizer not recognized!')
+    return make_optimizer(hparams.optimizer, arena, lr=hparams.lr, eps=1e-8, weight_decay=hparams.weight_decay,
+                          momentum=getattr(hparams, "momentum", 0.9) if hparams.optimizer == 'sgd' else 0.9, **kw)

@@ -28,7 +28,7 @@ from .dist import GradSync, collective_capturable
 from .graphs import GraphedStep
 from .hypernerf import model_utils
 from .losses import MSELoss, psnr
-from .optim import ArenaAdam, MultiStepLR, get_scheduler
+from .optim import OPTIMIZERS, ArenaAdam, MultiStepLR, get_scheduler, make_optimizer
 
 _EXTRA = {'nerf_alpha': None, 'warp_alpha': None, 'hyper_alpha': None, 'hyper_sheet_alpha': None}
 
@@ -37,7 +37,16 @@ class TrainStep:
     def __init__(self, model: torch.nn.Module, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, use_graph: bool = True, group=None, chunk: int = 32 * 1024,
                  decay_step: Optional[Sequence[int]] = None, decay_gamma: float = 0.1, overlap_grad_sync: bool = False,
-                 hparams=None, force_dp: bool = False, capture_collective: bool = True):
+                 hparams=None, force_dp: bool = False, capture_collective: bool = True, optimizer: str = "adam",
+                 momentum: float = 0.9):
+        # the optimizer of the reference's get_optimizer (utils/__init__.py:23-41): hparams.optimizer (and
+        # hparams.momentum for 'sgd') when hparams carries one, the keywords otherwise; lr / eps / weight_decay always
+        # from the keywords.  Checked before any device work.
+        if hparams is not None and getattr(hparams, "optimizer", None):
+            optimizer = hparams.optimizer
+            momentum = getattr(hparams, "momentum", momentum)
+        if optimizer not in OPTIMIZERS:
+            raise ValueError('optimizer not recognized!')
         self.model = model
         self.arena = ParamArena(model.parameters())
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -63,8 +72,14 @@ class TrainStep:
         # Without a collective between backward and the optimizer (one GPU) the launch that completes the gradient also
         # applies the update (hn_mlp_wgrad_reduce_adam: no gradient write-back, no second pass over the arena)
         from . import optim as _optim
-        self.optimizer = ArenaAdam(self.arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, zero_grad=True,
-                                   grad_scale=1.0 / self.world, fuse_reduce=(not self.dp) and _optim.FUSE_REDUCE)
+        if optimizer == "adam":
+            self.optimizer = ArenaAdam(self.arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, zero_grad=True,
+                                       grad_scale=1.0 / self.world, fuse_reduce=(not self.dp) and _optim.FUSE_REDUCE)
+        else:
+            # SGD / RAdam / Ranger: one launch of their own after the gradient is complete (no fused reduce); betas at
+            # the class defaults, as get_optimizer passes none
+            self.optimizer = make_optimizer(optimizer, self.arena, lr=lr, eps=eps, weight_decay=weight_decay,
+                                            momentum=momentum, zero_grad=True, grad_scale=1.0 / self.world)
         # 'steplr' of the reference (utils/__init__.py:43-46): stepped once per epoch by the caller (`epoch_end`)
         self.scheduler = MultiStepLR(self.optimizer, decay_step, decay_gamma) if decay_step else None
         # any scheduler of the reference's get_scheduler (utils/__init__.py:43-59): `hparams` carries lr_scheduler
@@ -120,14 +135,19 @@ class TrainStep:
         self.arena.all_reduce_sum(self.group, force=True)
         self.optimizer.step()
 
-    def _snapshot(self):
+    def _state(self):
+        """Parameters, gradient buffer and every tensor of the optimizer's state (step counter, moments, momentum /
+        slow buffers)."""
         o = self.optimizer
-        return [t.clone() for t in (self.arena.data, self.arena.grad, o.exp_avg, o.exp_avg_sq, o.step_count)]
+        opt = (o.exp_avg, o.exp_avg_sq, o.step_count) if isinstance(o, ArenaAdam) else tuple(o.state_tensors())
+        return (self.arena.data, self.arena.grad) + opt
+
+    def _snapshot(self):
+        return [t.clone() for t in self._state()]
 
     def _restore(self, snap):
-        o = self.optimizer
         with torch.no_grad():
-            for dst, src in zip((self.arena.data, self.arena.grad, o.exp_avg, o.exp_avg_sq, o.step_count), snap):
+            for dst, src in zip(self._state(), snap):
                 dst.copy_(src)
         self.arena.bump()
 

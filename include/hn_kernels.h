@@ -576,6 +576,27 @@ int hn_mse_loss_forward_grad(const float* coarse, const float* fine, const float
 int hn_adam_step(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, long long n,
                  const float* hyper_dev, float* step_dev, int zero_grad, hnStream_t stream);
 
+/* The other optimizers of the reference's get_optimizer (utils/__init__.py:23-41) over ONE flat fp32 buffer, launched
+ * like hn_adam_step: `step_dev` = the same two words ([0] updates done as a float, advanced by the launch; [1] a ticket
+ * the launch leaves at zero), zero_grad != 0 clears `grads`, grad_scale multiplies the gradient first.  The
+ * hyper-parameters are DOUBLES on the device: the kernels compute the reference's schedule scalars (beta^t, N_sma, the
+ * step size and its product with lr, Python doubles there) in fp64 once per workgroup and round each to fp32 once.
+ * Status: -2 n <= 0 (or k < 1), -3 a NULL pointer that must not be, -4 a buffer not 16-byte aligned (hyper: 8).
+ *
+ * hn_sgd_step: torch.optim.SGD.  hyper_dev: 8 doubles [lr, momentum, dampening, weight_decay, nesterov (0/1),
+ * grad_scale, 0, 0].  d = g*grad_scale + wd*p; with momentum != 0 (and momentum_buf != NULL) buf = d on update 1,
+ * buf = momentum*buf + (1-dampening)*d after that, d = d + momentum*buf (Nesterov) or buf; p -= lr*d.  momentum_buf
+ * may be NULL when momentum is 0. */
+int hn_sgd_step(float* params_dev, float* grads_dev, float* momentum_buf_dev, long long n, const double* hyper_dev,
+                float* step_dev, int zero_grad, hnStream_t stream);
+/* hn_radam_step: RAdam (utils/optimizers.py:29-95) when slow_dev == NULL, Ranger (utils/optimizers.py:322-405, RAdam
+ * with threshold N_sma > N_sma_threshhold, weight decay on every step and lookahead: slow = p before update 1, and after
+ * every update t with t % k == 0 slow += alpha*(p - slow), p = slow) otherwise.  hyper_dev: 12 doubles [lr, beta1,
+ * beta2, eps, weight_decay, grad_scale, N_sma_threshhold (Ranger), degenerated_to_sgd (RAdam, 0/1), alpha (Ranger), 0,
+ * 0, 0].  k: Ranger's lookahead period (>= 1; RAdam ignores it, pass 1). */
+int hn_radam_step(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* slow_dev,
+                  long long n, int k, const double* hyper_dev, float* step_dev, int zero_grad, hnStream_t stream);
+
 /* All rays of one H x W image on the device: get_ray_directions + get_rays (+ get_ndc_rays when `ndc`)
  * (datasets/ray_utils.py:5-93) and the ray-row layout of datasets/llff.py:244-264:
  * rays[(j*W + i)] = [origin(3), direction(3), near, far(, image_id)], row_floats = 8 or 9.
