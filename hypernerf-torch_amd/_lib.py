@@ -19,7 +19,7 @@ PRODUCT_LIB_PATH = os.path.join(CSRC, "libhn_hip.so")
 # HN_LIB_PATH: run under ANOTHER build of the library (the A/B tools compare prebuilt variants without ever overwriting
 # the product library); build() / needs_build() only ever write the product path
 LIB_PATH = os.environ.get("HN_LIB_PATH") or PRODUCT_LIB_PATH
-SOURCES = ["hn_mlp.hip", "hn_render.hip", "hn_calib.hip", "hn_optim.hip"]
+SOURCES = ["hn_mlp.hip", "hn_render.hip", "hn_calib.hip", "hn_optim.hip", "hn_metrics.hip"]
 CSRC_HEADERS = ["hn_common.h", "hn_pack.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hn_kernels.h")
 BUILD_MACROS = ("HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT")     # build-time tuning knobs (A/B experiments)
@@ -173,7 +173,8 @@ EXPORTS = ["hn_version", "hn_abi_sizes", "hn_build_config", "hn_mlp_wgrad_reduce
            "hn_mlp_wgrad_batched", "hn_mlp_wgrad_batched_t", "hn_mlp_wgrad_reduce", "hn_mlp_workspace_bytes",
            "hn_sample_along_rays", "hn_sample_legacy", "hn_posenc", "hn_composite_forward", "hn_composite_backward", "hn_sample_pdf", "hn_sample_pdf_split", "hn_composite_sample_pdf",
            "hn_embed_gather", "hn_embed_backward", "hn_se3_apply_forward", "hn_se3_apply_backward", "hn_se3_warp_forward", "hn_se3_warp_backward", "hn_generate_rays", "hn_adam_step", "hn_sgd_step", "hn_radam_step",
-           "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad", "hn_depth_index", "hn_random_fill",
+           "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad",
+           "hn_ssim_workspace_bytes", "hn_ssim_forward", "hn_ssim_backward", "hn_depth_index", "hn_random_fill",
            "hn_probe_mfma", "hn_calib_mfma", "hn_calib_stream", "hn_calib_stream_pattern", "hn_calib_ring"]
 
 _lib = None

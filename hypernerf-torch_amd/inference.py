@@ -119,21 +119,79 @@ def read_png(path: str):
     return rows[:, 1:].reshape(h, w, 3).copy()
 
 
+def write_pfm(path: str, image, scale: float = 1) -> None:
+    """float32 (H, W), (H, W, 1) or (H, W, 3) array / tensor -> a PFM file, byte for byte what the reference's save_pfm
+    writes (datasets/depth_utils.py:43-69): 'Pf' (greyscale) or 'PF' (colour), 'W H', the scale negated on a
+    little-endian array ('%f', so '-1.000000'), then the rows bottom to top.  numpy and the standard library only."""
+    import sys
+    import numpy as np
+    a = image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else np.asarray(image)
+    if a.dtype.name != "float32":          # either byte order
+        raise ValueError("write_pfm: the image must be float32")
+    if a.ndim == 3 and a.shape[2] == 3:
+        color = True
+    elif a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1):
+        color = False
+    else:
+        raise ValueError("write_pfm: (H, W), (H, W, 1) or (H, W, 3)")
+    a = np.flipud(a)
+    endian = a.dtype.byteorder
+    if endian == '<' or (endian == '=' and sys.byteorder == 'little'):
+        scale = -scale
+    with open(path, "wb") as f:
+        f.write(b"PF\n" if color else b"Pf\n")
+        f.write(f"{a.shape[1]} {a.shape[0]}\n".encode())
+        f.write(("%f\n" % scale).encode())
+        a.tofile(f)
+
+
+def read_pfm(path: str):
+    """A PFM file -> (data, scale) as the reference's read_pfm returns them (datasets/depth_utils.py:5-40): (H, W) for
+    'Pf', (H, W, 3) for 'PF', either endianness (a negative scale marks little-endian; the scale comes back positive),
+    rows top to bottom."""
+    import re
+    import numpy as np
+    with open(path, "rb") as f:
+        header = f.readline().decode("utf-8").rstrip()
+        if header not in ("PF", "Pf"):
+            raise ValueError("not a PFM file")
+        color = header == "PF"
+        dims = re.match(r"^(\d+)\s(\d+)\s$", f.readline().decode("utf-8"))
+        if dims is None:
+            raise ValueError("malformed PFM header")
+        width, height = map(int, dims.groups())
+        scale = float(f.readline().rstrip())
+        endian = "<" if scale < 0 else ">"
+        scale = abs(scale)
+        data = np.fromfile(f, endian + "f")
+    data = data.reshape((height, width, 3) if color else (height, width))
+    return np.flipud(data), scale
+
+
 @torch.no_grad()
 def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False, save_dir=None, group=None,
-                    image_format: str = "png") -> Dict:
+                    image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm") -> Dict:
     """The per-image loop of the reference's eval.py:145-178 on the GPU: for every sample {'rays': (H*W, 8|9),
     'rgbs': (H*W, 3) optional, 'hw': (H, W) optional} render the fine level in chunks, form the (H, W, 3) image,
     its 8-bit version (eval.py:165 `(img*255).astype(uint8)`) and, when ground truth is present, the PSNR
-    (metrics.psnr, eval.py:169-172).  Returns {'images': [uint8 (H,W,3) CPU tensors], 'depths': [...],
-    'psnrs': [float], 'mean_psnr': float | None}.  With `save_dir` the 8-bit frames are also written as `{i:03d}.png`
+    (metrics.psnr, eval.py:169-172) and the SSIM (metrics.ssim on (1, 3, H, W) views, no copy).  Returns
+    {'images': [uint8 (H,W,3) CPU tensors], 'depths': [...], 'psnrs': [float], 'mean_psnr': float | None,
+    'ssims': [float], 'mean_ssim': float | None}.  With `save_dir` the 8-bit frames are also written as `{i:03d}.png`
     (eval.py:166; `write_png`: standard library only — round 6; `image_format="ppm"` keeps the binary PPM of rounds 2-5).
+    `save_depth` writes every depth map (after nan_to_num) into `save_dir` (eval.py:150-158): `depth_{i:03d}.pfm`
+    (`write_pfm`, the reference's save_pfm layout) for depth_format 'pfm', the raw float32 bytes as `depth_{i:03d}` for
+    'bytes' — the reference writes that file into the current directory (eval.py:157), this port into `save_dir`.
     The reference's GIF of all frames (eval.py:172, imageio.mimsave) is not written: the frames are in the result.
     `white_back` is accepted and ignored as in the reference's batched_inference (eval.py:77-85)."""
     if image_format not in ("png", "ppm"):
         raise ValueError("image_format: 'png' or 'ppm'")
+    if depth_format not in ("pfm", "bytes"):
+        raise ValueError("depth_format: 'pfm' or 'bytes'")
+    if save_depth and save_dir is None:
+        raise ValueError("save_depth needs save_dir")
     from .losses import psnr as _psnr
-    imgs, depths, psnrs = [], [], []
+    from .losses import ssim as _ssim
+    imgs, depths, psnrs, ssims = [], [], [], []
     for i, sample in enumerate(images):
         rays = sample['rays']
         res = render_image(model, rays, chunk=chunk, keys=('rgb', 'depth'), group=group)
@@ -146,13 +204,21 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
         if sample.get('rgbs') is not None:
             gt = sample['rgbs'].to(img.device).view(h, w, 3)
             psnrs.append(float(_psnr(gt, img)))
+            ssims.append(float(_ssim(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None])))
         if save_dir is not None:
             import os
             os.makedirs(save_dir, exist_ok=True)
+            if save_depth:
+                if depth_format == "pfm":
+                    write_pfm(os.path.join(save_dir, f"depth_{i:03d}.pfm"), depths[-1].numpy())
+                else:
+                    with open(os.path.join(save_dir, f"depth_{i:03d}"), "wb") as f:
+                        f.write(depths[-1].numpy().tobytes())
             if image_format == "png":
                 write_png(os.path.join(save_dir, f"{i:03d}.png"), img8)
             else:
                 with open(os.path.join(save_dir, f"{i:03d}.ppm"), "wb") as f:
                     f.write(f"P6 {w} {h} 255\n".encode() + img8.numpy().tobytes())
     return {'images': imgs, 'depths': depths, 'psnrs': psnrs,
-            'mean_psnr': (sum(psnrs) / len(psnrs)) if psnrs else None}
+            'mean_psnr': (sum(psnrs) / len(psnrs)) if psnrs else None,
+            'ssims': ssims, 'mean_ssim': (sum(ssims) / len(ssims)) if ssims else None}

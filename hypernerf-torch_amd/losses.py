@@ -1,8 +1,9 @@
-"""Loss head and PSNR of the reference (losses.py:4-14, metrics.py:4-13) — scalar reductions over (B,3) pixels.
+"""Loss head and metrics of the reference (losses.py:4-14, metrics.py:4-20) — scalar reductions over (B,3) pixels.
 
 `MSELoss` is one HIP launch forward (both levels, both means, their sum) and one backward (`hn_mse_loss_*`,
-functional.mse_loss); the metrics (`mse`, `psnr`: logging only, no gradient path in the reference) are torch
-one-liners.  GPU tensors only, like every op of the package."""
+functional.mse_loss); the metrics `mse` and `psnr` (logging only, no gradient path in the reference) are torch
+one-liners; `ssim` runs kornia's windowed SSIM in HIP (`hn_ssim_*`, functional.ssim_dssim), differentiable as kornia's.
+GPU tensors only, like every op of the package."""
 import torch
 from torch import nn
 
@@ -31,3 +32,9 @@ def mse(image_pred, image_gt, valid_mask=None, reduction='mean'):
 def psnr(image_pred, image_gt, valid_mask=None, reduction='mean'):
     """metrics.py:11-13."""
     return -10.0 * torch.log10(mse(image_pred, image_gt, valid_mask, reduction))
+
+
+def ssim(image_pred, image_gt, reduction='mean'):
+    """metrics.py:15-20: 1 - 2 * dssim(pred, gt, window 3), in [-1, 1]; image_pred and image_gt (N, 3, H, W) (the reference
+    documents (1, 3, H, W)), any strides.  dssim is kornia's ssim loss (functional.ssim_dssim, two HIP launches)."""
+    return 1 - 2 * F.ssim_dssim(image_pred, image_gt, 3, reduction=reduction)

@@ -565,6 +565,25 @@ int hn_mse_loss_backward(const float* coarse, const float* fine, const float* gt
 int hn_mse_loss_forward_grad(const float* coarse, const float* fine, const float* gt, int64_t n, float* loss_out,
                              float* d_coarse, float* d_fine, hnStream_t stream);
 
+/* SSIM of the reference's metrics.py:15-20 (kornia's ssim loss, `dssim`): per (n, c) plane the dissimilarity map
+ * dssim = clamp((1 - S) / 2, 0, 1), S = ((2 mux muy + c1)(2 sxy + c2)) / ((mux^2 + muy^2 + c1)(sxx + syy + c2) + eps), the
+ * moments filtered with the outer product of the 1-D window `window_host` (HOST array of `window` floats: kornia's
+ * get_gaussian_kernel1d(window, 1.5)) over a reflect-padded image (F.pad mode='reflect').  pred / gt: fp32 (n, c, h, w)
+ * with arbitrary element strides (`*_strides`: HOST arrays of 4).  window: odd, 3 .. 15; h and w > window / 2 (else -2).
+ * hn_ssim_forward writes the map (dssim_map, contiguous, may be NULL) and/or the sum of the map over all n*c*h*w elements
+ * (sum_out: ONE device float, written, not accumulated; may be NULL), the sum with per-workgroup partials in `workspace`
+ * (hn_ssim_workspace_bytes: host arithmetic) and a second launch that adds them in a fixed order: bit-reproducible.
+ * hn_ssim_backward: the upstream gradient is either g_scalar (ONE device float: every element of the map gets it) or
+ * g_map (contiguous (n, c, h, w)), exactly one of them; d_pred (and d_gt unless NULL) are written, contiguous, as the
+ * adjoint of the forward including the reflect padding. */
+int hn_ssim_workspace_bytes(int n, int c, int h, int w, int window, int64_t* bytes);
+int hn_ssim_forward(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int n,
+                    int c, int h, int w, const float* window_host, int window, float c1, float c2, float eps,
+                    float* dssim_map, float* sum_out, void* workspace, hnStream_t stream);
+int hn_ssim_backward(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int n,
+                     int c, int h, int w, const float* window_host, int window, float c1, float c2, float eps,
+                     const float* g_scalar, const float* g_map, float* d_pred, float* d_gt, hnStream_t stream);
+
 /* torch.optim.Adam (the reference's default optimizer, utils/__init__.py get_optimizer) over ONE flat fp32 buffer
  * (ParamArena): p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps), m,v updated first, L2 weight decay added to the
  * gradient.  `hyper_dev`: 8 floats ON THE DEVICE, [lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0] — read by the

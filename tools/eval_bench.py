@@ -1,7 +1,8 @@
 """Diagnostic: throughput of the evaluation path (SURVEY.md §8 f4 — eval.py's image loop): one 378 x 504 LLFF-sized
 image rendered by `inference.render_image` with the BASELINE config-2 model (64+64 samples, bf16), chunked.
 Prints one JSON line: images/s, rays/s, ray-samples/s, and the share of the dense bf16 MFMA peak of the forward
-FLOPs (SURVEY.md §8d's per-point FLOP count / 3, the forward third).
+FLOPs (SURVEY.md §8d's per-point FLOP count / 3, the forward third); then images/s of the whole eval loop
+(`inference.evaluate_images`) without and with ground truth (the latter adds PSNR and SSIM).
 
 usage: python tools/eval_bench.py [chunk] [reps]"""
 import json
@@ -53,6 +54,16 @@ def main():
     res["forward_flops"] = fl
     res["forward_tflops"] = fl / dt / 1e12
     res["mfma_frac_of_2.5PF"] = fl / dt / 2.5e15
+    # the whole eval loop (inference.evaluate_images: 8-bit frame, depth to the host; with ground truth also PSNR and SSIM)
+    gt = torch.rand(n, 3, generator=g).to(dev)
+    for key, sample in (("loop_images_per_s_no_gt", {"rays": rays, "hw": (h, w)}),
+                        ("loop_images_per_s_gt", {"rays": rays, "rgbs": gt, "hw": (h, w)})):
+        inference.evaluate_images(m, [sample], chunk=chunk)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        inference.evaluate_images(m, [sample] * reps, chunk=chunk)
+        torch.cuda.synchronize()
+        res[key] = reps / (time.perf_counter() - t0)
     from hypernerf_torch_amd import _lib
     res["build"] = _lib.build_id()
     print(json.dumps(res))
