@@ -845,15 +845,13 @@ extern "C" int hn_embed_backward(const float* d_points, int ld, int col0, const 
 // origin = c2w[:, 3]; optional NDC transform (near plane 1.0 in the reference's call); one thread per pixel writes
 // the whole (8|9)-float ray row [o, d, near, far(, image id)] — 36 B/pixel, HBM bound.
 // ------------------------------------------------------------------------------------------------
-__global__ void hn_generate_rays_kernel(int H, int W, float focal, const float* c2w, int ndc, float ndc_near,
-                                        float near, float far, float image_id, int row_floats, float* rays) {
-  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pix >= H * W) return;
-  const int j = pix / W, i = pix - j * W;
+// The pixel -> ray arithmetic, shared by hn_generate_rays_kernel and hn_ray_batch_kernel (one definition: a training
+// batch gathers exactly the rows the whole-image launch writes).
+__device__ __forceinline__ void hn_pixel_ray(int H, int W, float focal, const float* c2w, int ndc, float ndc_near, int i,
+                                             int j, float o[3], float d[3]) {
   const float dx = __fdiv_rn(__fsub_rn((float)i, __fdiv_rn((float)W, 2.0f)), focal);
   const float dy = -__fdiv_rn(__fsub_rn((float)j, __fdiv_rn((float)H, 2.0f)), focal);
   const float dz = -1.0f;
-  float d[3], o[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     d[k] = __fadd_rn(__fadd_rn(__fmul_rn(dx, c2w[4 * k]), __fmul_rn(dy, c2w[4 * k + 1])), __fmul_rn(dz, c2w[4 * k + 2]));
@@ -876,6 +874,15 @@ __global__ void hn_generate_rays_kernel(int H, int W, float focal, const float* 
     const float d2 = __fsub_rn(1.0f, o2);
     o[0] = o0; o[1] = o1; o[2] = o2; d[0] = d0; d[1] = d1; d[2] = d2;
   }
+}
+
+__global__ void hn_generate_rays_kernel(int H, int W, float focal, const float* c2w, int ndc, float ndc_near,
+                                        float near, float far, float image_id, int row_floats, float* rays) {
+  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= H * W) return;
+  const int j = pix / W, i = pix - j * W;
+  float d[3], o[3];
+  hn_pixel_ray(H, W, focal, c2w, ndc, ndc_near, i, j, o, d);
   float* r = rays + (size_t)pix * row_floats;
   r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2]; r[6] = near; r[7] = far;
   if (row_floats > 8) r[8] = image_id;
@@ -888,6 +895,116 @@ extern "C" int hn_generate_rays(int H, int W, float focal, const float* c2w, int
   const int n = H * W;
   hipLaunchKernelGGL(hn_generate_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W, focal,
                      c2w, ndc, ndc_near, near, far, image_id, row_floats, rays);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One training batch of an LLFF dataset gathered on the device (datasets/llff.py's all_rays / all_rgbs rows, in the
+// order a shuffled DataLoader reads them).  state[0] is the cursor into `perm`, state[1] an arrival counter, state[2]
+// an error flag: every workgroup reads the cursor, then arrives; the last to arrive advances the cursor by `batch` and
+// clears the counter, so nothing returns to the host and the launch replays inside a captured graph.  A ray index g
+// decodes to training slot g / (H*W) and pixel g % (H*W); the row comes from hn_pixel_ray with that slot's c2w, the
+// colour from the uint8 stack as u8 / 255 (torchvision's ToTensor: a division, rounded once).  A position past the end
+// of `perm`, or an index outside the dataset, writes a NaN row and colour and sets the error flag (the host checks it
+// once per epoch): nothing is read out of bounds and a bookkeeping error cannot pass as a plausible batch.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, long long n_perm,
+        unsigned long long* state, int batch, long long n_rays, int H, int W, float focal, const float* c2w,
+        const float* image_ids, int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
+        float* rays, float* rgbs) {
+  __shared__ long long s_cur;
+  if (threadIdx.x == 0) s_cur = (long long)state[0];
+  __syncthreads();
+  const long long cur = s_cur;
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row < batch) {
+    const long long p = cur + row;
+    const long long g = (p >= 0 && p < n_perm) ? perm[p] : -1;
+    float* r = rays + (size_t)row * row_floats;
+    float* c = rgbs + (size_t)row * 3;
+    if (g < 0 || g >= n_rays) {
+      const float nan = __int_as_float(0x7fc00000);
+      for (int k = 0; k < row_floats; ++k) r[k] = nan;
+      c[0] = nan; c[1] = nan; c[2] = nan;
+      __hip_atomic_store(&state[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      const long long hw = (long long)H * W;
+      const int slot = (int)(g / hw);
+      const int pix = (int)(g - (long long)slot * hw);
+      const int j = pix / W, i = pix - j * W;
+      float d[3], o[3];
+      hn_pixel_ray(H, W, focal, c2w + 12 * slot, ndc, ndc_near, i, j, o, d);
+      r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2]; r[6] = near; r[7] = far;
+      if (row_floats > 8) r[8] = image_ids[slot];
+      const uint8_t* px = rgb8 + 3 * g;
+      c[0] = __fdiv_rn((float)px[0], 255.0f);
+      c[1] = __fdiv_rn((float)px[1], 255.0f);
+      c[2] = __fdiv_rn((float)px[2], 255.0f);
+    }
+  }
+  __syncthreads();                 // every lane of this workgroup has consumed the cursor
+  if (threadIdx.x == 0) {
+    const unsigned long long arrived =
+        __hip_atomic_fetch_add(&state[1], 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (arrived == gridDim.x - 1) {                                        // the last workgroup: no one reads it now
+      __hip_atomic_store(&state[1], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&state[0], (unsigned long long)(cur + batch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+extern "C" int hn_ray_batch(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
+                            long long n_rays, int H, int W, float focal, const float* c2w, const float* image_ids,
+                            int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
+                            float* rays, float* rgbs, hnStream_t stream) {
+  if (batch <= 0 || n_perm <= 0 || n_rays <= 0 || H <= 0 || W <= 0 || !(focal > 0.0f) ||
+      (row_floats != 8 && row_floats != 9))
+    return -2;
+  if (n_rays % ((long long)H * W) != 0) return -2;
+  if (perm == nullptr || state == nullptr || c2w == nullptr || rgb8 == nullptr || rays == nullptr || rgbs == nullptr ||
+      (row_floats == 9 && image_ids == nullptr))
+    return -3;
+  hipLaunchKernelGGL(hn_ray_batch_kernel, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, perm, n_perm,
+                     state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near, far, row_floats, rgb8,
+                     rays, rgbs);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One pass of Pillow's 8-bit resampling (Image.resize, ImagingResampleHorizontal_8bpc / Vertical_8bpc): out[x] =
+// clamp(((1 << 21) + sum_k in[bounds[x].min + k] * kk[x][k]) >> 22, 0, 255) per channel, int32 coefficients with 22
+// fraction bits from the host (the coefficient tables are float64 host math).  vertical = 0: (rows, cols, C) ->
+// (rows, out_len, C) along the columns; vertical = 1: (rows, cols, C) -> (out_len, cols, C) along the rows.
+// The sum wraps modulo 2^32 as Pillow's int32 does.  One thread per output pixel, all channels.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_resample_u8_kernel(const uint8_t* in, int rows, int cols, int channels,
+        int out_len, int vertical, const int32_t* bounds, const int32_t* kk, int ksize, uint8_t* out) {
+  const int out_rows = vertical ? out_len : rows, out_cols = vertical ? cols : out_len;
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long long)out_rows * out_cols) return;
+  const int y = (int)(id / out_cols), x = (int)(id - (long long)y * out_cols);
+  const int o = vertical ? y : x;
+  const int lo = bounds[2 * o], n = bounds[2 * o + 1];
+  const int32_t* k = kk + (size_t)o * ksize;
+  const long long step = vertical ? (long long)cols * channels : channels;
+  const uint8_t* src = vertical ? in + ((long long)lo * cols + x) * channels : in + ((long long)y * cols + lo) * channels;
+  for (int c = 0; c < channels; ++c) {
+    uint32_t ss = 1u << 21;
+    for (int t = 0; t < n; ++t) ss += (uint32_t)src[t * step + c] * (uint32_t)k[t];
+    const int v = ((int32_t)ss) >> 22;
+    out[id * channels + c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+  }
+}
+
+extern "C" int hn_resample_u8(const uint8_t* in, int rows, int cols, int channels, int out_len, int vertical,
+                              const int32_t* bounds, const int32_t* kk, int ksize, uint8_t* out, hnStream_t stream) {
+  if (rows <= 0 || cols <= 0 || channels <= 0 || channels > 4 || out_len <= 0 || ksize <= 0) return -2;
+  if (in == nullptr || bounds == nullptr || kk == nullptr || out == nullptr) return -3;
+  const long long n = (long long)(vertical ? out_len : rows) * (vertical ? cols : out_len);
+  hipLaunchKernelGGL(hn_resample_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in,
+                     rows, cols, channels, out_len, vertical, bounds, kk, ksize, out);
   HN_CHECK_LAUNCH();
   return 0;
 }

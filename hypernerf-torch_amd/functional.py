@@ -1043,6 +1043,78 @@ def generate_rays(h: int, w: int, focal: float, c2w: torch.Tensor, near: float, 
     return rays
 
 
+def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float, c2w: torch.Tensor,
+              rgb8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float, far: float, ndc: bool = False,
+              ndc_near: float = 1.0, image_ids: Optional[torch.Tensor] = None) -> None:
+    """One training batch gathered on the GPU (hn_ray_batch): rows perm[cursor : cursor + batch] of the dataset whose
+    rays are the pixels of `rgb8` ((n_images, h, w, 3) uint8) seen through `c2w` ((n_images, 3, 4) fp32), written into
+    rays[:batch] ((B, 8|9) fp32, column 8 = image_ids[slot] when rays has 9 columns) and rgbs[:batch] ((B, 3) fp32).
+    `state` (3 int64 words: cursor, arrival counter, error flag) is advanced by `batch` on the device: no host sync.
+    A row whose position lies past the permutation, or whose index lies outside the dataset, is written as NaN and sets
+    the error flag."""
+    L.require_gpu(perm, state, c2w, rgb8, rays, rgbs, image_ids)
+    L.load()
+    cols = rays.shape[1]
+    n_img = rgb8.shape[0]
+    ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
+          and c2w.dtype == torch.float32 and c2w.is_contiguous() and tuple(c2w.shape) == (n_img, 3, 4)
+          and rgb8.dtype == torch.uint8 and rgb8.is_contiguous() and tuple(rgb8.shape[1:]) == (h, w, 3)
+          and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
+          and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
+          and rgbs.shape[0] >= batch and 0 < batch and perm.numel() > 0
+          and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
+    if not ok:
+        raise L.HnError("ray_batch: bad shapes / dtypes")
+    L.launch("hn_ray_batch", L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
+             C.c_longlong(rgb8.numel() // 3), C.c_int(h), C.c_int(w), C.c_float(focal), L.ptr(c2w),
+             L.ptr(image_ids if cols == 9 else None), C.c_int(int(ndc)), C.c_float(ndc_near), C.c_float(near),
+             C.c_float(far), C.c_int(cols), L.ptr(rgb8), L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+
+
+_RESAMPLE_TABLES: Dict[tuple, tuple] = {}
+
+
+def _resample_tables(in_size: int, out_size: int, device):
+    key = (in_size, out_size, str(device))
+    t = _RESAMPLE_TABLES.get(key)
+    if t is None:
+        from .datasets.image_io import lanczos_tables
+        bounds, kk, ksize = lanczos_tables(in_size, out_size)
+        if not ((bounds[:, 0] >= 0).all() and (bounds[:, 1] >= 0).all() and (bounds.sum(1) <= in_size).all()
+                and (bounds[:, 1] <= ksize).all()):
+            raise L.HnError("resize: coefficient bounds outside the input")
+        t = _RESAMPLE_TABLES[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize)
+    return t
+
+
+def resize_lanczos_u8(img: torch.Tensor, size) -> torch.Tensor:
+    """Pillow's `Image.resize(size, Image.LANCZOS)` of an 8-bit (H, W, C) image on the GPU, byte for byte: the
+    horizontal pass first (uint8 intermediate), then the vertical one; a pass whose axis keeps its length is skipped.
+    size = (width, height) as Pillow takes it."""
+    L.require_gpu(img)
+    L.load()
+    if img.dtype != torch.uint8 or img.dim() != 3 or not 1 <= img.shape[2] <= 4:
+        raise L.HnError("resize_lanczos_u8: (H, W, C) uint8, C <= 4")
+    out_w, out_h = int(size[0]), int(size[1])
+    if out_w <= 0 or out_h <= 0:
+        raise L.HnError("resize_lanczos_u8: the size must be positive")
+    x = img.contiguous()
+    h, w, c = x.shape
+    if out_w != w:
+        bounds, kk, ksize = _resample_tables(w, out_w, x.device)
+        y = torch.empty((h, out_w, c), dtype=torch.uint8, device=x.device)
+        L.launch("hn_resample_u8", L.ptr(x), C.c_int(h), C.c_int(w), C.c_int(c), C.c_int(out_w), C.c_int(0),
+                 L.ptr(bounds), L.ptr(kk), C.c_int(ksize), L.ptr(y), L.stream_handle())
+        x, w = y, out_w
+    if out_h != h:
+        bounds, kk, ksize = _resample_tables(h, out_h, x.device)
+        y = torch.empty((out_h, w, c), dtype=torch.uint8, device=x.device)
+        L.launch("hn_resample_u8", L.ptr(x), C.c_int(h), C.c_int(w), C.c_int(c), C.c_int(out_h), C.c_int(1),
+                 L.ptr(bounds), L.ptr(kk), C.c_int(ksize), L.ptr(y), L.stream_handle())
+        x = y
+    return x if x is not img else x.clone()
+
+
 # --------------------------------------------------------------------------------------------
 # SE(3) exponential-map warp
 # --------------------------------------------------------------------------------------------

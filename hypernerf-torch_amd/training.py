@@ -38,7 +38,7 @@ class TrainStep:
                  weight_decay: float = 0.0, use_graph: bool = True, group=None, chunk: int = 32 * 1024,
                  decay_step: Optional[Sequence[int]] = None, decay_gamma: float = 0.1, overlap_grad_sync: bool = False,
                  hparams=None, force_dp: bool = False, capture_collective: bool = True, optimizer: str = "adam",
-                 momentum: float = 0.9):
+                 momentum: float = 0.9, batcher=None):
         # the optimizer of the reference's get_optimizer (utils/__init__.py:23-41): hparams.optimizer (and
         # hparams.momentum for 'sgd') when hparams carries one, the keywords otherwise; lr / eps / weight_decay always
         # from the keywords.  Checked before any device work.
@@ -91,6 +91,12 @@ class TrainStep:
         self._rays = self._rgbs = None
         self._rng: Optional[Dict[str, torch.Tensor]] = None    # fixed buffers of injected random draws (tests)
         self._log: Dict[str, torch.Tensor] = {}
+        # batcher (datasets.RayBatcher): step() takes no tensors; the batch is gathered on the device by the first
+        # launch of the step's graph.  One cached program per batch size (the full one and the epoch's short last one)
+        self.batcher = batcher
+        self._batched: Dict[tuple, tuple] = {}
+        self._batched_state = None
+        self._batched_rng: Dict[int, Dict[str, torch.Tensor]] = {}
 
     # ---- the step body (what gets captured) ---------------------------------------------------
     def _forward_backward(self):
@@ -151,12 +157,13 @@ class TrainStep:
                 dst.copy_(src)
         self.arena.bump()
 
-    def _capture(self, fn):
-        """Warm-up runs + capture execute `fn` for real; parameters, gradient buffer and optimizer state are put back
-        afterwards so that the first step() applies exactly ONE update (and, with N>1, all-reduces ONE gradient)."""
+    def _capture(self, fn, warmup_fn=None):
+        """Warm-up runs + capture execute `fn` (the warm-up runs: `warmup_fn` when given) for real; parameters,
+        gradient buffer and optimizer state are put back afterwards so that the first step() applies exactly ONE
+        update (and, with N>1, all-reduces ONE gradient)."""
         snap = self._snapshot()
         try:
-            g = GraphedStep(fn, warmup=2)
+            g = GraphedStep(fn, warmup=2, warmup_fn=warmup_fn)
         finally:
             self._restore(snap)
         return g
@@ -209,11 +216,19 @@ class TrainStep:
         return self._capture_data_parallel()
 
     # ---- public -----------------------------------------------------------------------------------
-    def step(self, rays: torch.Tensor, rgbs: torch.Tensor, rng: Optional[Dict[str, torch.Tensor]] = None
-             ) -> Dict[str, torch.Tensor]:
+    def step(self, rays: Optional[torch.Tensor] = None, rgbs: Optional[torch.Tensor] = None,
+             rng: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """rays (B, 8|9), rgbs (B, 3) on the GPU; B must stay the same from call to call when graphs are on.
         `rng` optionally supplies the random draws of NerfModel.forward ('t_rand', 'u', 'noise_coarse', 'noise_fine',
-        one row per ray) instead of torch's generator: parity runs against the CPU oracle share the draws this way."""
+        one row per ray) instead of torch's generator: parity runs against the CPU oracle share the draws this way.
+        With a batcher, step() takes no rays / rgbs: the next batch of the batcher's epoch is gathered on the device
+        (an epoch that ran out starts the next one); `rng` rows then match that batch's size."""
+        if self.batcher is not None:
+            if rays is not None or rgbs is not None:
+                raise ValueError("TrainStep(batcher=...): step() takes no rays / rgbs")
+            return self._step_batched(rng)
+        if rays is None or rgbs is None:
+            raise ValueError("step() needs rays and rgbs (or a TrainStep built with batcher=...)")
         if self._rays is None or self._rays.shape != rays.shape or (rng is None) != (self._rng is None):
             self._rays, self._rgbs = rays.clone(), rgbs.clone()
             self._rng = None if rng is None else {k: v.clone() for k, v in rng.items()}
@@ -258,6 +273,87 @@ class TrainStep:
         return log
 
     def epoch_end(self):
-        """Advance the LR schedule by one epoch (Lightning steps the scheduler of configure_optimizers per epoch)."""
+        """Advance the LR schedule by one epoch (Lightning steps the scheduler of configure_optimizers per epoch); with
+        a batcher, end its epoch too: the next step() draws a new order (for the epoch a set_epoch() call in between
+        names, else the next one)."""
         if self.scheduler is not None:
             self.scheduler.step()
+        if self.batcher is not None:
+            self.batcher.end_epoch()
+
+    # ---- the batched step (batcher=...) ---------------------------------------------------------------
+    def _whole_batched(self, rows: int):
+        self.batcher.launch(rows)
+        self._whole()
+
+    def _capture_batched(self, rows: int):
+        """The step of `rows` rays as one graph, hn_ray_batch first.  Each warm-up run gathers the epoch's first
+        `rows` rays (cursor reset to 0: never past the permutation); the device state is put back with the optimizer
+        state, so the first replay reads the batch that is due."""
+        b = self.batcher
+        state = b.state.clone()
+
+        def warm():
+            b.state.zero_()
+            self._whole_batched(rows)
+        try:
+            return self._capture(lambda: self._whole_batched(rows), warmup_fn=warm)
+        finally:
+            b.state.copy_(state)
+
+    def _step_batched(self, rng: Optional[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
+        b = self.batcher
+        rows = b.next_rows()              # host bookkeeping only; the cursor itself lives on the device
+        self._rays, self._rgbs = b.views(rows)
+        if rng is None:
+            self._rng = None
+        else:
+            bufs = self._batched_rng.get(rows)
+            if bufs is None or set(bufs) != set(rng):
+                bufs = self._batched_rng[rows] = {k: v.clone() for k, v in rng.items()}
+                self._batched.pop((rows, True), None)
+            else:
+                for k, v in rng.items():
+                    bufs[k].copy_(v)
+            self._rng = bufs
+        state = (F.get_precision(), self.model.training)
+        if self._batched_state != state:
+            self._batched_state = state
+            self._batched = {}
+        self.optimizer.sync_hyper()
+        key = (rows, rng is not None)
+        if not self.use_graph:
+            b.launch(rows)
+            self._forward_backward()
+            if self.dp:
+                self.sync.reduce(F.flush_held_wgrads, force=True)
+            self.optimizer.step()
+            log = self._log
+        elif not self.dp:
+            prog = self._batched.get(key)
+            if prog is None:
+                g = self._capture_batched(rows)
+                prog = self._batched[key] = (g, self._log)
+            prog[0]()
+            log = prog[1]
+        else:
+            # data-parallel: the gather runs on its own ahead of the step's program(s), cached per batch size
+            b.launch(rows)
+            prog = self._batched.get(key)
+            if prog is None:
+                self._graph = None
+                prog = self._batched[key] = (self._capture_dp(), self._log)
+            g = prog[0]
+            if isinstance(g, GraphedStep):
+                g()
+            else:
+                fwd_bwd, held = g
+                fwd_bwd()
+                self.sync.reduce(held, force=True)
+                self.optimizer.step()
+            log = prog[1]
+        self.arena.bump()
+        machine.note_parameters_changed()
+        out = {k: v.clone() for k, v in log.items()}
+        out['lr'] = self.optimizer.param_groups[0]['lr']
+        return out

@@ -623,6 +623,27 @@ int hn_radam_step(float* params_dev, float* grads_dev, float* exp_avg_dev, float
 int hn_generate_rays(int H, int W, float focal, const float* c2w_dev, int ndc, float ndc_near, float near,
                      float far, float image_id, int row_floats, float* rays_dev, hnStream_t stream);
 
+/* One training batch of an LLFF dataset (datasets/llff.py's all_rays / all_rgbs, as a shuffled DataLoader reads them),
+ * gathered on the device without a host round trip.  The dataset is n_rays = n_images*H*W rays: ray g is pixel
+ * g % (H*W) of training slot g / (H*W).  For row r < batch: g = perm[state[0] + r];
+ * rays[r] = the row hn_generate_rays writes for that pixel with c2w_dev[slot] ((n_images, 3, 4) fp32) and, for
+ * row_floats 9, image_ids_dev[slot] (fp32); rgbs[r] = rgb8_dev[g] / 255 ((n_rays, 3) uint8; ToTensor's rounded
+ * division).  state_dev: three uint64 words [cursor, arrival counter, error flag], zero-initialised by the caller;
+ * the launch advances the cursor by `batch` and leaves the counter at 0.  A position at or past n_perm, or an index g
+ * outside [0, n_rays), writes NaN into that row of rays and rgbs and sets the error flag to 1.  Graph-capturable. */
+int hn_ray_batch(const int64_t* perm_dev, long long n_perm, unsigned long long* state_dev, int batch, long long n_rays,
+                 int H, int W, float focal, const float* c2w_dev, const float* image_ids_dev, int ndc, float ndc_near,
+                 float near, float far, int row_floats, const uint8_t* rgb8_dev, float* rays_dev, float* rgbs_dev,
+                 hnStream_t stream);
+
+/* One pass of Pillow's 8-bit Image.resize (ImagingResampleHorizontal_8bpc / Vertical_8bpc), bit-exact given its
+ * tables: out = clamp(((1 << 21) + sum_k in[bounds[2o] + k] * kk[o*ksize + k]) >> 22, 0, 255) per channel, k <
+ * bounds[2o+1].  in: (rows, cols, channels) uint8; vertical = 0 resamples along cols into (rows, out_len, channels),
+ * vertical = 1 along rows into (out_len, cols, channels).  bounds (out_len, 2) [first, count] and kk (out_len, ksize)
+ * int32 (22 fraction bits) on the device; the caller keeps first + count within the input axis. */
+int hn_resample_u8(const uint8_t* in_dev, int rows, int cols, int channels, int out_len, int vertical,
+                   const int32_t* bounds_dev, const int32_t* kk_dev, int ksize, uint8_t* out_dev, hnStream_t stream);
+
 /* SE(3) exponential-map warp of warping.SE3Field.warp (hypernerf/warping.py:226-238 with rigid_body.exp_se3,
  * rigid_body.py:55-83, applied per point): theta = |w|, a = w/theta, b = v/theta,
  * y = p + sin(theta) a x p + (1-cos(theta)) a x (a x p) + theta b + (1-cos(theta)) a x b + (theta-sin(theta)) a x (a x b).
