@@ -908,7 +908,22 @@ extern "C" int hn_generate_rays(int H, int W, float focal, const float* c2w, int
 // colour from the uint8 stack as u8 / 255 (torchvision's ToTensor: a division, rounded once).  A position past the end
 // of `perm`, or an index outside the dataset, writes a NaN row and colour and sets the error flag (the host checks it
 // once per epoch): nothing is read out of bounds and a bookkeeping error cannot pass as a plausible batch.
+//
+// CH = 3: the LLFF stack above.  CH = 4: a Blender stack of RGBA pixels (datasets/blender.py:57-58): the pixel is one
+// aligned 32-bit load and the colour is its blend onto white, hn_blend_white — the definition hn_blend_white_u8 uses.
 // ------------------------------------------------------------------------------------------------
+// An RGBA pixel (little endian: R in the low byte, A in the high one) blended onto white as the reference does on
+// ToTensor values: x = c / 255 and al = a / 255 (divisions, rounded once), then x * al, 1 - al and their sum as three
+// separately rounded operations (a fused multiply-add differs in the last bit for about one pixel in ten).
+__device__ __forceinline__ void hn_blend_white(uint32_t px, float c[3]) {
+  const float al = __fdiv_rn((float)(px >> 24), 255.0f);
+  const float rest = __fsub_rn(1.0f, al);
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    c[k] = __fadd_rn(__fmul_rn(__fdiv_rn((float)((px >> (8 * k)) & 0xffu), 255.0f), al), rest);
+}
+
+template <int CH>
 __global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, long long n_perm,
         unsigned long long* state, int batch, long long n_rays, int H, int W, float focal, const float* c2w,
         const float* image_ids, int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
@@ -937,10 +952,16 @@ __global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, 
       hn_pixel_ray(H, W, focal, c2w + 12 * slot, ndc, ndc_near, i, j, o, d);
       r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2]; r[6] = near; r[7] = far;
       if (row_floats > 8) r[8] = image_ids[slot];
-      const uint8_t* px = rgb8 + 3 * g;
-      c[0] = __fdiv_rn((float)px[0], 255.0f);
-      c[1] = __fdiv_rn((float)px[1], 255.0f);
-      c[2] = __fdiv_rn((float)px[2], 255.0f);
+      if (CH == 4) {
+        float col[3];
+        hn_blend_white(reinterpret_cast<const uint32_t*>(rgb8)[g], col);
+        c[0] = col[0]; c[1] = col[1]; c[2] = col[2];
+      } else {
+        const uint8_t* px = rgb8 + 3 * g;
+        c[0] = __fdiv_rn((float)px[0], 255.0f);
+        c[1] = __fdiv_rn((float)px[1], 255.0f);
+        c[2] = __fdiv_rn((float)px[2], 255.0f);
+      }
     }
   }
   __syncthreads();                 // every lane of this workgroup has consumed the cursor
@@ -954,20 +975,105 @@ __global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, 
   }
 }
 
-extern "C" int hn_ray_batch(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
-                            long long n_rays, int H, int W, float focal, const float* c2w, const float* image_ids,
-                            int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
-                            float* rays, float* rgbs, hnStream_t stream) {
+template <int CH>
+static int hn_ray_batch_launch(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
+                               long long n_rays, int H, int W, float focal, const float* c2w, const float* image_ids,
+                               int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* px8,
+                               float* rays, float* rgbs, hnStream_t stream) {
   if (batch <= 0 || n_perm <= 0 || n_rays <= 0 || H <= 0 || W <= 0 || !(focal > 0.0f) ||
       (row_floats != 8 && row_floats != 9))
     return -2;
   if (n_rays % ((long long)H * W) != 0) return -2;
-  if (perm == nullptr || state == nullptr || c2w == nullptr || rgb8 == nullptr || rays == nullptr || rgbs == nullptr ||
+  if (perm == nullptr || state == nullptr || c2w == nullptr || px8 == nullptr || rays == nullptr || rgbs == nullptr ||
       (row_floats == 9 && image_ids == nullptr))
     return -3;
-  hipLaunchKernelGGL(hn_ray_batch_kernel, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, perm, n_perm,
-                     state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near, far, row_floats, rgb8,
-                     rays, rgbs);
+  if (CH == 4 && (reinterpret_cast<uintptr_t>(px8) & 3u) != 0) return -3;      // pixels are read as 32-bit words
+  hipLaunchKernelGGL(hn_ray_batch_kernel<CH>, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, perm,
+                     n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near, far, row_floats,
+                     px8, rays, rgbs);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int hn_ray_batch(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
+                            long long n_rays, int H, int W, float focal, const float* c2w, const float* image_ids,
+                            int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
+                            float* rays, float* rgbs, hnStream_t stream) {
+  return hn_ray_batch_launch<3>(perm, n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near,
+                                far, row_floats, rgb8, rays, rgbs, stream);
+}
+
+extern "C" int hn_ray_batch_rgba(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
+                                 long long n_rays, int H, int W, float focal, const float* c2w,
+                                 const float* image_ids, int ndc, float ndc_near, float near, float far,
+                                 int row_floats, const uint8_t* rgba8, float* rays, float* rgbs, hnStream_t stream) {
+  return hn_ray_batch_launch<4>(perm, n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near,
+                                far, row_floats, rgba8, rays, rgbs, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// (N, 4) uint8 RGBA -> (N, 3) fp32 blended onto white (hn_blend_white) and, when `mask` is given, (N,) bytes a > 0
+// (the reference's valid_mask, datasets/blender.py:93).  One thread per pixel, one aligned 32-bit load.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_blend_white_u8_kernel(const uint32_t* rgba, long long n, float* rgbs,
+                                                                 uint8_t* mask) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n) return;
+  const uint32_t px = rgba[id];
+  float c[3];
+  hn_blend_white(px, c);
+  float* o = rgbs + 3 * id;
+  o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+  if (mask != nullptr) mask[id] = (uint8_t)((px >> 24) != 0u);
+}
+
+extern "C" int hn_blend_white_u8(const uint8_t* rgba8, long long n, float* rgbs, uint8_t* mask, hnStream_t stream) {
+  if (n <= 0 || (n + 255) / 256 > 0x7fffffffLL) return -2;
+  if (rgba8 == nullptr || rgbs == nullptr || (reinterpret_cast<uintptr_t>(rgba8) & 3u) != 0) return -3;
+  hipLaunchKernelGGL(hn_blend_white_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const uint32_t*>(rgba8), n, rgbs, mask);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pillow's RGBA <-> RGBa conversions around a resize of an RGBA image (Image.resize converts to premultiplied alpha,
+// resamples, converts back; Convert.c rgbA2rgba / rgba2rgbA).  inverse = 0: c' = MULDIV255(c, a) = ((t >> 8) + t) >> 8
+// with t = c * a + 128.  inverse = 1: a == 0 or a == 255 keeps the bytes, else c = min(255, 255 * c' / a) (integer
+// division).  Alpha is unchanged either way.  One thread per pixel, one aligned 32-bit load and store; in == out is
+// allowed.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_premultiply_u8_kernel(const uint32_t* in, long long n, int inverse,
+                                                                 uint32_t* out) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= n) return;
+  const uint32_t px = in[id];
+  const uint32_t a = px >> 24;
+  uint32_t res = px & 0xff000000u;
+  if (!inverse) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t t = ((px >> (8 * k)) & 0xffu) * a + 128u;
+      res |= ((((t >> 8) + t) >> 8) & 0xffu) << (8 * k);
+    }
+  } else if (a == 0u || a == 255u) {
+    res = px;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const uint32_t v = (255u * ((px >> (8 * k)) & 0xffu)) / a;
+      res |= (v > 255u ? 255u : v) << (8 * k);
+    }
+  }
+  out[id] = res;
+}
+
+extern "C" int hn_premultiply_u8(const uint8_t* in, long long n, int inverse, uint8_t* out, hnStream_t stream) {
+  if (n <= 0 || (n + 255) / 256 > 0x7fffffffLL) return -2;
+  if (in == nullptr || out == nullptr || ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3u) != 0)
+    return -3;
+  hipLaunchKernelGGL(hn_premultiply_u8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const uint32_t*>(in), n, inverse, reinterpret_cast<uint32_t*>(out));
   HN_CHECK_LAUNCH();
   return 0;
 }

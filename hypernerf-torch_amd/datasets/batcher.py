@@ -1,9 +1,11 @@
-"""Per-step training batches gathered on the GPU (hn_ray_batch), in the order a shuffled DataLoader reads them.
+"""Per-step training batches gathered on the GPU (hn_ray_batch, hn_ray_batch_rgba), in the order a shuffled DataLoader
+reads them.
 
 `RayBatcher(dataset, batch_size, generator=g)` reproduces `DataLoader(dataset, batch_size, shuffle=True,
 generator=g)` over `dataset.all_rays` / `dataset.all_rgbs` bit for bit — without building those tensors: each batch
-is gathered from the dataset's uint8 image stack and poses by one launch that reads a device permutation at a device
-cursor and advances the cursor itself, so the launch can sit at the head of a captured training graph
+is gathered from the dataset's uint8 image stack and poses by one launch (the dataset's `gather_batch`) that reads a
+device permutation at a device cursor and advances the cursor itself, so the launch can sit at the head of a captured
+training graph
 (`TrainStep(model, batcher=...)`).  The permutation is host plumbing, drawn once per epoch and copied into the
 captured buffer in place.  With torch.distributed initialised the order is DistributedSampler's (shuffle=True,
 drop_last=False) for this rank.
@@ -55,9 +57,10 @@ def distributed_sampler_order(n: int, rank: int, world: int, seed: int = 0, epoc
 class RayBatcher:
     def __init__(self, dataset, batch_size: int, generator: Optional[torch.Generator] = None, drop_last: bool = False,
                  seed: int = 0, group=None):
-        """dataset: an LLFFDataset of split 'train'.  generator / drop_last: DataLoader's; seed: DistributedSampler's
-        (used only with torch.distributed initialised)."""
-        if getattr(dataset, 'split', None) != 'train' or not hasattr(dataset, 'rgb8'):
+        """dataset: an LLFFDataset or a BlenderDataset of split 'train' (anything with `n_rays`, `ray_cols`, `c2w` on
+        the device and `gather_batch(perm, state, rows, rays, rgbs)`).  generator / drop_last: DataLoader's; seed:
+        DistributedSampler's (used only with torch.distributed initialised)."""
+        if getattr(dataset, 'split', None) != 'train' or not hasattr(dataset, 'gather_batch'):
             raise ValueError("RayBatcher needs a 'train' split dataset")
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
@@ -75,7 +78,7 @@ class RayBatcher:
         if self.drop_last and self.n_samples < self.batch_size:
             raise ValueError("drop_last with fewer rays than one batch leaves no step")
         self.epoch = 0
-        dev = dataset.rgb8.device
+        dev = dataset.c2w.device
         self.perm = torch.zeros(self.n_samples, dtype=torch.int64, device=dev)
         self.state = torch.zeros(3, dtype=torch.int64, device=dev)      # [cursor, arrival counter, error flag]
         self.rays = torch.empty((self.batch_size, dataset.ray_cols), dtype=torch.float32, device=dev)
@@ -117,8 +120,8 @@ class RayBatcher:
         """Raise if a gather read outside the permutation or the dataset (its rows were written as NaN).  Reads one
         device word: a host sync."""
         if int(self.state[2].item()) != 0:
-            raise F.L.HnError("hn_ray_batch read past the end of the epoch's permutation or found an index outside the "
-                              "dataset (the batch rows were NaN): the host's epoch bookkeeping is out of step")
+            raise F.L.HnError("the batch gather read past the end of the epoch's permutation or found an index outside "
+                              "the dataset (the batch rows were NaN): the host's epoch bookkeeping is out of step")
 
     def begin_epoch(self) -> None:
         """Draw the next epoch's order and put it in the device buffer, cursor at 0.  Checks the previous epoch's
@@ -144,11 +147,7 @@ class RayBatcher:
 
     def launch(self, rows: int) -> None:
         """Gather the next `rows` rays at the device cursor into rays[:rows] / rgbs[:rows] (graph-capturable)."""
-        ds = self.dataset
-        w, h = ds.img_wh
-        F.ray_batch(self.perm, self.state, rows, h, w, float(ds.focal), ds.c2w, ds.rgb8, self.rays, self.rgbs,
-                    near=float(ds.near), far=float(ds.far), ndc=not ds.spheric_poses, ndc_near=1.0,
-                    image_ids=ds.image_ids)
+        self.dataset.gather_batch(self.perm, self.state, rows, self.rays, self.rgbs)
 
     def next_rows(self) -> int:
         """Host bookkeeping of one step: start an epoch if the last one ran out, return this step's row count."""

@@ -1,5 +1,5 @@
-"""Host side of the dataset's image path: decoding an image file to 8-bit RGB, and the coefficient tables of Pillow's
-LANCZOS resize that the GPU passes (functional.resize_lanczos_u8, hn_resample_u8) apply.
+"""Host side of the dataset's image path: decoding an image file to 8-bit RGB (LLFF) or RGBA (Blender), and the
+coefficient tables of Pillow's LANCZOS resize that the GPU passes (functional.resize_lanczos_u8, hn_resample_u8) apply.
 
 Decoding uses Pillow when it imports (`Image.open(p).convert('RGB')`, what the reference's datasets/llff.py does);
 without Pillow a PNG decoder of the standard library (zlib) reads 8-bit greyscale, grey+alpha, RGB and RGBA files with
@@ -44,6 +44,24 @@ def load_rgb8(path: str, use_pillow: bool = True) -> np.ndarray:
         raise ValueError(f"{path}: JPEG images need Pillow, which is not installed (convert the images to PNG, or "
                          "install Pillow)")
     raise ValueError(f"{path}: not a PNG image, and Pillow is not installed to read other formats")
+
+
+def load_rgba8(path: str, use_pillow: bool = True) -> np.ndarray:
+    """An RGBA image file -> (H, W, 4) uint8, the bytes as stored (no mode conversion: the reference's Blender reader
+    hands the opened image to ToTensor and fails in `img.view(4, -1)` on anything but four channels)."""
+    if use_pillow and _PILImage is not None:
+        with _PILImage.open(path) as im:
+            if im.mode != 'RGBA':
+                raise ValueError(f"{path}: the Blender dataset reads RGBA images (this one has mode '{im.mode}')")
+            return np.asarray(im, dtype=np.uint8).copy()
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG image, and Pillow is not installed to read other formats")
+    try:
+        return decode_png_rgba8(data)
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
 
 
 def image_size(path: str, use_pillow: bool = True) -> Tuple[int, int]:
@@ -102,9 +120,8 @@ def _unfilter(raw: bytes, h: int, stride: int, bpp: int) -> np.ndarray:
     return out
 
 
-def decode_png_rgb8(data: bytes) -> np.ndarray:
-    """A PNG file's bytes -> (H, W, 3) uint8 RGB (alpha dropped, grey replicated: Pillow's convert('RGB') of those
-    modes).  8 bits per sample, no interlace."""
+def _decode_png(data: bytes) -> np.ndarray:
+    """A PNG file's bytes -> (H, W, samples per pixel) uint8 as stored.  8 bits per sample, no interlace."""
     if data[:8] != b"\x89PNG\r\n\x1a\n":
         raise ValueError("not a PNG")
     pos, idat, hdr = 8, [], None
@@ -129,10 +146,26 @@ def decode_png_rgb8(data: bytes) -> np.ndarray:
     if interlace:
         raise ValueError("PNG: interlaced images are read only with Pillow")
     ch = _CHANNELS[colour]
-    px = _unfilter(zlib.decompress(b"".join(idat)), h, w * ch, ch).reshape(h, w, ch)
-    if ch in (1, 2):
+    return _unfilter(zlib.decompress(b"".join(idat)), h, w * ch, ch).reshape(h, w, ch)
+
+
+def decode_png_rgb8(data: bytes) -> np.ndarray:
+    """A PNG file's bytes -> (H, W, 3) uint8 RGB (alpha dropped, grey replicated: Pillow's convert('RGB') of those
+    modes).  8 bits per sample, no interlace."""
+    px = _decode_png(data)
+    if px.shape[2] in (1, 2):
         return np.repeat(px[..., :1], 3, axis=2)
     return np.ascontiguousarray(px[..., :3])
+
+
+def decode_png_rgba8(data: bytes) -> np.ndarray:
+    """A PNG file's bytes -> (H, W, 4) uint8 RGBA, alpha kept.  Colour type 6 (8-bit RGBA) only: any other type is
+    refused, as Pillow's mode of such a file is not 'RGBA'."""
+    px = _decode_png(data)
+    if px.shape[2] != 4:
+        raise ValueError(f"PNG: the Blender dataset reads RGBA images (colour type 6); this one has {px.shape[2]} "
+                         "sample(s) per pixel")
+    return np.ascontiguousarray(px)
 
 
 # --------------------------------------------------------------------------------------------
@@ -208,3 +241,30 @@ def resample_u8_reference(img: np.ndarray, size) -> np.ndarray:
     if out_h != x.shape[0]:
         x = one_pass(x, out_h, 0)
     return np.ascontiguousarray(x)
+
+
+def premultiply_u8_reference(img: np.ndarray) -> np.ndarray:
+    """Pillow's RGBA -> RGBa: c' = ((t >> 8) + t) >> 8 with t = c * a + 128; alpha unchanged."""
+    x = np.asarray(img, dtype=np.uint8).astype(np.int64)
+    t = x[..., :3] * x[..., 3:] + 128
+    x[..., :3] = ((t >> 8) + t) >> 8
+    return x.astype(np.uint8)
+
+
+def unpremultiply_u8_reference(img: np.ndarray) -> np.ndarray:
+    """Pillow's RGBa -> RGBA: the colour bytes stay where a is 0 or 255, else c = min(255, (255 * c') // a)."""
+    x = np.asarray(img, dtype=np.uint8).astype(np.int64)
+    a = x[..., 3:]
+    x[..., :3] = np.where((a == 0) | (a == 255), x[..., :3], np.minimum(255, (255 * x[..., :3]) // np.maximum(a, 1)))
+    return x.astype(np.uint8)
+
+
+def resample_rgba8_reference(img: np.ndarray, size) -> np.ndarray:
+    """A NumPy statement of functional.resize_lanczos_rgba8 (tests): Pillow's LANCZOS resize of an (H, W, 4) RGBA
+    image — a copy at equal size, else premultiply, the two fixed-point passes on four channels, un-premultiply."""
+    x = np.asarray(img, dtype=np.uint8)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError("resample_rgba8_reference: (H, W, 4) uint8")
+    if (int(size[1]), int(size[0])) == x.shape[:2]:
+        return x.copy()
+    return unpremultiply_u8_reference(resample_u8_reference(premultiply_u8_reference(x), size))

@@ -239,6 +239,16 @@ class LLFFDataset(Dataset):
         w, h = self.img_wh
         return len(self.train_ids) * h * w
 
+    def gather_batch(self, perm: torch.Tensor, state: torch.Tensor, rows: int, rays: torch.Tensor,
+                     rgbs: torch.Tensor) -> None:
+        """RayBatcher's launch: rows perm[cursor : cursor + rows] of all_rays / all_rgbs, gathered from the uint8 stack
+        and the poses by one launch."""
+        from .. import functional as F
+        w, h = self.img_wh
+        F.ray_batch(perm, state, rows, h, w, float(self.focal), self.c2w, self.rgb8, rays, rgbs,
+                    near=float(self.near), far=float(self.far), ndc=not self.spheric_poses, ndc_near=1.0,
+                    image_ids=self.image_ids)
+
     def __len__(self):
         if self.split == 'train':
             return self.n_rays

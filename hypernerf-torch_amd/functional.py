@@ -1043,6 +1043,27 @@ def generate_rays(h: int, w: int, focal: float, c2w: torch.Tensor, near: float, 
     return rays
 
 
+def _ray_batch(entry: str, channels: int, perm, state, batch, h, w, focal, c2w, px8, rays, rgbs, near, far, ndc,
+               ndc_near, image_ids) -> None:
+    L.require_gpu(perm, state, c2w, px8, rays, rgbs, image_ids)
+    L.load()
+    cols = rays.shape[1]
+    n_img = px8.shape[0]
+    ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
+          and c2w.dtype == torch.float32 and c2w.is_contiguous() and tuple(c2w.shape) == (n_img, 3, 4)
+          and px8.dtype == torch.uint8 and px8.is_contiguous() and tuple(px8.shape[1:]) == (h, w, channels)
+          and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
+          and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
+          and rgbs.shape[0] >= batch and 0 < batch and perm.numel() > 0
+          and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
+    if not ok:
+        raise L.HnError(f"{entry[3:]}: bad shapes / dtypes")
+    L.launch(entry, L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
+             C.c_longlong(px8.numel() // channels), C.c_int(h), C.c_int(w), C.c_float(focal), L.ptr(c2w),
+             L.ptr(image_ids if cols == 9 else None), C.c_int(int(ndc)), C.c_float(ndc_near), C.c_float(near),
+             C.c_float(far), C.c_int(cols), L.ptr(px8), L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+
+
 def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float, c2w: torch.Tensor,
               rgb8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float, far: float, ndc: bool = False,
               ndc_near: float = 1.0, image_ids: Optional[torch.Tensor] = None) -> None:
@@ -1052,23 +1073,34 @@ def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: in
     `state` (3 int64 words: cursor, arrival counter, error flag) is advanced by `batch` on the device: no host sync.
     A row whose position lies past the permutation, or whose index lies outside the dataset, is written as NaN and sets
     the error flag."""
-    L.require_gpu(perm, state, c2w, rgb8, rays, rgbs, image_ids)
+    _ray_batch("hn_ray_batch", 3, perm, state, batch, h, w, focal, c2w, rgb8, rays, rgbs, near, far, ndc, ndc_near,
+               image_ids)
+
+
+def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float,
+                   c2w: torch.Tensor, rgba8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float,
+                   far: float, ndc: bool = False, ndc_near: float = 1.0,
+                   image_ids: Optional[torch.Tensor] = None) -> None:
+    """`ray_batch` over an RGBA stack ((n_images, h, w, 4) uint8, hn_ray_batch_rgba): rgbs[:batch] is each pixel
+    blended onto white as `blend_white_u8` computes it, in the same launch."""
+    _ray_batch("hn_ray_batch_rgba", 4, perm, state, batch, h, w, focal, c2w, rgba8, rays, rgbs, near, far, ndc,
+               ndc_near, image_ids)
+
+
+def blend_white_u8(rgba8: torch.Tensor, with_mask: bool = False):
+    """(..., 4) uint8 RGBA -> (N, 3) fp32 `rgb * a + (1 - a)` on u8 / 255 values, bit for bit the reference's blend
+    (datasets/blender.py:58; hn_blend_white_u8: a multiply, a subtraction and an addition, each rounded).  With
+    `with_mask` also the (N,) bool mask a > 0 (blender.py:93): returns (rgbs, mask)."""
+    L.require_gpu(rgba8)
     L.load()
-    cols = rays.shape[1]
-    n_img = rgb8.shape[0]
-    ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
-          and c2w.dtype == torch.float32 and c2w.is_contiguous() and tuple(c2w.shape) == (n_img, 3, 4)
-          and rgb8.dtype == torch.uint8 and rgb8.is_contiguous() and tuple(rgb8.shape[1:]) == (h, w, 3)
-          and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
-          and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
-          and rgbs.shape[0] >= batch and 0 < batch and perm.numel() > 0
-          and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
-    if not ok:
-        raise L.HnError("ray_batch: bad shapes / dtypes")
-    L.launch("hn_ray_batch", L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
-             C.c_longlong(rgb8.numel() // 3), C.c_int(h), C.c_int(w), C.c_float(focal), L.ptr(c2w),
-             L.ptr(image_ids if cols == 9 else None), C.c_int(int(ndc)), C.c_float(ndc_near), C.c_float(near),
-             C.c_float(far), C.c_int(cols), L.ptr(rgb8), L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+    if rgba8.dtype != torch.uint8 or rgba8.dim() < 1 or rgba8.shape[-1] != 4 or rgba8.numel() == 0:
+        raise L.HnError("blend_white_u8: (..., 4) uint8")
+    x = rgba8.contiguous()
+    n = x.numel() // 4
+    rgbs = torch.empty((n, 3), dtype=torch.float32, device=x.device)
+    mask = torch.empty(n, dtype=torch.bool, device=x.device) if with_mask else None
+    L.launch("hn_blend_white_u8", L.ptr(x), C.c_longlong(n), L.ptr(rgbs), L.ptr(mask), L.stream_handle())
+    return (rgbs, mask) if with_mask else rgbs
 
 
 _RESAMPLE_TABLES: Dict[tuple, tuple] = {}
@@ -1113,6 +1145,34 @@ def resize_lanczos_u8(img: torch.Tensor, size) -> torch.Tensor:
                  L.ptr(bounds), L.ptr(kk), C.c_int(ksize), L.ptr(y), L.stream_handle())
         x = y
     return x if x is not img else x.clone()
+
+
+def premultiply_u8(img: torch.Tensor, inverse: bool = False) -> torch.Tensor:
+    """Pillow's RGBA -> RGBa conversion of an (H, W, 4) uint8 image (hn_premultiply_u8), or with `inverse` RGBa ->
+    RGBA: both round, alpha stays."""
+    L.require_gpu(img)
+    L.load()
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 4 or img.numel() == 0:
+        raise L.HnError("premultiply_u8: (H, W, 4) uint8")
+    x = img.contiguous()
+    out = torch.empty_like(x)
+    L.launch("hn_premultiply_u8", L.ptr(x), C.c_longlong(x.numel() // 4), C.c_int(int(inverse)), L.ptr(out),
+             L.stream_handle())
+    return out
+
+
+def resize_lanczos_rgba8(img: torch.Tensor, size) -> torch.Tensor:
+    """Pillow's `Image.resize(size, Image.LANCZOS)` of an 8-bit RGBA (H, W, 4) image on the GPU, byte for byte: Pillow
+    resamples such an image in premultiplied alpha, so the colour bytes are premultiplied, the four channels go
+    through the passes of `resize_lanczos_u8`, and the colours are divided by the new alpha.  At equal size Pillow
+    returns a copy, without that round trip (it would change bytes).  size = (width, height)."""
+    L.require_gpu(img)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 4:
+        raise L.HnError("resize_lanczos_rgba8: (H, W, 4) uint8")
+    out_w, out_h = int(size[0]), int(size[1])
+    if (out_h, out_w) == tuple(img.shape[:2]):
+        return img.clone(memory_format=torch.contiguous_format)
+    return premultiply_u8(resize_lanczos_u8(premultiply_u8(img), (out_w, out_h)), inverse=True)
 
 
 # --------------------------------------------------------------------------------------------

@@ -170,7 +170,8 @@ def read_pfm(path: str):
 
 @torch.no_grad()
 def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False, save_dir=None, group=None,
-                    image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm") -> Dict:
+                    image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm",
+                    use_valid_mask: bool = False) -> Dict:
     """The per-image loop of the reference's eval.py:145-178 on the GPU: for every sample {'rays': (H*W, 8|9),
     'rgbs': (H*W, 3) optional, 'hw': (H, W) optional} render the fine level in chunks, form the (H, W, 3) image,
     its 8-bit version (eval.py:165 `(img*255).astype(uint8)`) and, when ground truth is present, the PSNR
@@ -182,7 +183,9 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     (`write_pfm`, the reference's save_pfm layout) for depth_format 'pfm', the raw float32 bytes as `depth_{i:03d}` for
     'bytes' — the reference writes that file into the current directory (eval.py:157), this port into `save_dir`.
     The reference's GIF of all frames (eval.py:172, imageio.mimsave) is not written: the frames are in the result.
-    `white_back` is accepted and ignored as in the reference's batched_inference (eval.py:77-85)."""
+    `white_back` is accepted and ignored as in the reference's batched_inference (eval.py:77-85).
+    `use_valid_mask` restricts the PSNR to the sample's 'valid_mask' ((H*W,) bool; the Blender splits carry alpha > 0)
+    through metrics.psnr's own argument; off by default, as the reference's eval.py does not mask."""
     if image_format not in ("png", "ppm"):
         raise ValueError("image_format: 'png' or 'ppm'")
     if depth_format not in ("pfm", "bytes"):
@@ -203,7 +206,8 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
         depths.append(torch.nan_to_num(res['depth'].view(h, w)).cpu())
         if sample.get('rgbs') is not None:
             gt = sample['rgbs'].to(img.device).view(h, w, 3)
-            psnrs.append(float(_psnr(gt, img)))
+            mask = sample.get('valid_mask') if use_valid_mask else None
+            psnrs.append(float(_psnr(gt, img, None if mask is None else mask.to(img.device).view(h, w))))
             ssims.append(float(_ssim(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None])))
         if save_dir is not None:
             import os

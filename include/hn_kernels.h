@@ -636,6 +636,25 @@ int hn_ray_batch(const int64_t* perm_dev, long long n_perm, unsigned long long* 
                  float near, float far, int row_floats, const uint8_t* rgb8_dev, float* rays_dev, float* rgbs_dev,
                  hnStream_t stream);
 
+/* hn_ray_batch over a Blender dataset (datasets/blender.py): rgba8_dev is (n_rays, 4) uint8 RGBA, 4-byte aligned, each
+ * pixel read as one 32-bit word, and rgbs[r] is that pixel blended onto white exactly as hn_blend_white_u8 writes it
+ * (one device function).  Everything else — state words, NaN rows and the error flag, the ray row — as hn_ray_batch. */
+int hn_ray_batch_rgba(const int64_t* perm_dev, long long n_perm, unsigned long long* state_dev, int batch,
+                      long long n_rays, int H, int W, float focal, const float* c2w_dev, const float* image_ids_dev,
+                      int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgba8_dev,
+                      float* rays_dev, float* rgbs_dev, hnStream_t stream);
+
+/* The reference's blend of an RGBA image onto white (datasets/blender.py:58, :93-95) on ToTensor values:
+ * rgbs[i][k] = fl(fl(fl(c_k / 255) * al) + fl(1 - al)), al = fl(a / 255) — every operation rounded on its own, no fused
+ * multiply-add — and, when mask_dev != NULL, mask[i] = (a > 0) as one byte.  rgba8_dev: (n, 4) uint8, 4-byte aligned;
+ * rgbs_dev: (n, 3) fp32. */
+int hn_blend_white_u8(const uint8_t* rgba8_dev, long long n, float* rgbs_dev, uint8_t* mask_dev, hnStream_t stream);
+
+/* Pillow's conversions around a resize of an RGBA image (n pixels, 4-byte aligned; in_dev == out_dev allowed).
+ * inverse = 0, RGBA -> premultiplied: c' = ((t >> 8) + t) >> 8 with t = c*a + 128.  inverse = 1, back: the bytes stay
+ * for a == 0 or a == 255, else c = min(255, (255*c') / a) in integer division.  Alpha is copied. */
+int hn_premultiply_u8(const uint8_t* in_dev, long long n, int inverse, uint8_t* out_dev, hnStream_t stream);
+
 /* One pass of Pillow's 8-bit Image.resize (ImagingResampleHorizontal_8bpc / Vertical_8bpc), bit-exact given its
  * tables: out = clamp(((1 << 21) + sum_k in[bounds[2o] + k] * kk[o*ksize + k]) >> 22, 0, 255) per channel, k <
  * bounds[2o+1].  in: (rows, cols, channels) uint8; vertical = 0 resamples along cols into (rows, out_len, channels),

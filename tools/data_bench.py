@@ -1,4 +1,4 @@
-"""Data-path measurements of the LLFF dataset (hypernerf_torch_amd.datasets), one JSON line per part:
+"""Data-path measurements of the datasets (hypernerf_torch_amd.datasets), one JSON line per part:
 
   python tools/data_bench.py --part load     # dataset load: decode, HIP LANCZOS resize vs Pillow's, whole constructor
   python tools/data_bench.py --part steps    # steps/s at config 2 (1024 rays x (64+64), bf16, graphs): fed the
@@ -7,7 +7,11 @@
   python tools/data_bench.py --part kernel   # hn_ray_batch launches only, for a run of its own under
                                              # rocprofv3 --kernel-trace --stats (kernel time from the trace)
 
-Scenes are synthetic and seeded (tests/llff_scene.py), written to a temporary directory.  Times are host wall clock
+`--dataset blender` (default: llff) measures the same parts on a Blender scene of RGBA images (20 images of 512 x 512
+resized to 436 x 436: as many rays as the LLFF scene within 0.3 %); its `kernel` part launches the RGB gather on the
+LLFF scene as well, so that one trace holds hn_ray_batch_kernel<3> and <4> side by side at 8 ray columns each.
+
+Scenes are synthetic and seeded (tests/llff_scene.py, tests/blender_scene.py), written to a temporary directory.  Times are host wall clock
 around work that ends in a device synchronise, after warm-up.
 """
 import argparse
@@ -25,10 +29,17 @@ import torch  # noqa: E402
 
 import hypernerf_torch_amd as HN  # noqa: E402
 from hypernerf_torch_amd import functional as F  # noqa: E402
-from hypernerf_torch_amd.datasets import LLFFDataset, RayBatcher, image_io  # noqa: E402
+from hypernerf_torch_amd.datasets import BlenderDataset, LLFFDataset, RayBatcher, image_io  # noqa: E402
+import blender_scene  # noqa: E402
 from llff_scene import make_scene, write_scene  # noqa: E402
 
 DEV = "cuda:0"
+BLENDER_SRC, BLENDER_WH = 512, (436, 436)
+
+
+def _blender_train(a, tmp, seed):
+    scene = blender_scene.make_scene(seed=seed, size=BLENDER_SRC, frames=(("train", a.images),))
+    return blender_scene.write_scene(os.path.join(tmp, f"blender{seed}"), scene)
 
 
 def _sync_time(fn, reps=1):
@@ -40,7 +51,41 @@ def _sync_time(fn, reps=1):
     return (time.perf_counter() - t0) / reps
 
 
+def part_load_blender(a, tmp):
+    root = _blender_train(a, tmp, 11)
+    paths = sorted(os.path.join(root, "train", f) for f in os.listdir(os.path.join(root, "train")))
+    decoded = [image_io.load_rgba8(p) for p in paths[:2]]
+    wh = BLENDER_WH
+    out = {"part": "load", "dataset": "blender", "images": a.images, "source_hw": [BLENDER_SRC, BLENDER_SRC],
+           "img_wh": list(wh), "pillow": image_io.have_pillow()}
+    t0 = time.perf_counter()
+    for p in paths:
+        image_io.load_rgba8(p)
+    out["decode_ms_per_image"] = (time.perf_counter() - t0) / len(paths) * 1e3
+    x = torch.from_numpy(decoded[0]).to(DEV)
+    F.resize_lanczos_rgba8(x, wh)                              # tables + first launches
+    out["hip_resize_ms_per_image"] = _sync_time(lambda: F.resize_lanczos_rgba8(x, wh), reps=20) * 1e3
+    if image_io.have_pillow():
+        from PIL import Image
+        im = Image.fromarray(decoded[0], "RGBA")
+        t0 = time.perf_counter()
+        for _ in range(5):
+            r = im.resize(wh, Image.Resampling.LANCZOS)
+        out["pillow_resize_ms_per_image"] = (time.perf_counter() - t0) / 5 * 1e3
+        out["hip_equals_pillow"] = bool(np.array_equal(np.asarray(r), F.resize_lanczos_rgba8(x, wh).cpu().numpy()))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    ds = BlenderDataset(root, split="train", img_wh=wh)
+    torch.cuda.synchronize()
+    out["dataset_train_s"] = time.perf_counter() - t0
+    out["dataset_device_bytes"] = ds.rgba8.numel() + ds.c2w.numel() * 4
+    out["all_rays_rgbs_bytes_if_built"] = ds.n_rays * (ds.ray_cols + 3) * 4
+    return out
+
+
 def part_load(a, tmp):
+    if a.dataset == "blender":
+        return part_load_blender(a, tmp)
     src_h, src_w = a.src_hw
     pix, pb = make_scene(a.images, src_h, src_w, seed=11, focal=1.1 * src_w)
     root = write_scene(os.path.join(tmp, "load"), pix, pb)
@@ -101,11 +146,16 @@ def _config2_step(batcher=None):
 
 
 def part_steps(a, tmp):
-    pix, pb = make_scene(a.images, 378, 504, seed=12, focal=400.0)
-    root = write_scene(os.path.join(tmp, "steps"), pix, pb)
-    ds = LLFFDataset(root, split="train", img_wh=(504, 378), include_idx=True)
+    if a.dataset == "blender":
+        ds = BlenderDataset(_blender_train(a, tmp, 12), split="train", img_wh=BLENDER_WH)
+        head = {"part": "steps", "dataset": "blender"}
+    else:
+        pix, pb = make_scene(a.images, 378, 504, seed=12, focal=400.0)
+        root = write_scene(os.path.join(tmp, "steps"), pix, pb)
+        ds = LLFFDataset(root, split="train", img_wh=(504, 378), include_idx=True)
+        head = {"part": "steps"}
     b, steps, warm = 1024, a.steps, a.warmup
-    out = {"part": "steps", "rays": ds.n_rays, "batch": b, "steps": steps, "warmup": warm,
+    out = {**head, "rays": ds.n_rays, "batch": b, "steps": steps, "warmup": warm,
            "workload": "NerfModel use_warp bendy_sheet nerf_embed+alpha_cond, 1024 rays x (64+64), bf16, graphs"}
 
     # batcher-fed: the gather is the first launch of the captured step
@@ -141,7 +191,30 @@ def part_steps(a, tmp):
     return out
 
 
+def part_kernel_blender(a, tmp):
+    """Both gathers in one process, 8 ray columns each, alternating in blocks of 50 launches."""
+    pix, pb = make_scene(a.images, 378, 504, seed=13, focal=400.0)
+    llff = LLFFDataset(write_scene(os.path.join(tmp, "kernel"), pix, pb), split="train", img_wh=(504, 378))
+    blender = BlenderDataset(_blender_train(a, tmp, 13), split="train", img_wh=BLENDER_WH)
+    bts = [RayBatcher(ds, 1024, generator=torch.Generator().manual_seed(0)) for ds in (llff, blender)]
+    for bt in bts:
+        bt.begin_epoch()
+    n = min(a.steps * 10, min(bt.steps_per_epoch for bt in bts) - 1)
+    for k in range(0, n, 50):
+        for bt in bts:
+            for _ in range(min(50, n - k)):
+                bt.launch(1024)
+    torch.cuda.synchronize()
+    for bt in bts:
+        bt.check()
+    return {"part": "kernel", "dataset": "blender", "launches_each": n, "batch": 1024,
+            "rays": {"llff": llff.n_rays, "blender": blender.n_rays}, "bytes_written_per_launch": 1024 * (8 + 3) * 4,
+            "kernels": {"llff": "hn_ray_batch_kernel<3>", "blender": "hn_ray_batch_kernel<4>"}}
+
+
 def part_kernel(a, tmp):
+    if a.dataset == "blender":
+        return part_kernel_blender(a, tmp)
     pix, pb = make_scene(a.images, 378, 504, seed=13, focal=400.0)
     root = write_scene(os.path.join(tmp, "kernel"), pix, pb)
     ds = LLFFDataset(root, split="train", img_wh=(504, 378), include_idx=True)
@@ -158,6 +231,7 @@ def part_kernel(a, tmp):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", choices=("load", "steps", "kernel"), required=True)
+    ap.add_argument("--dataset", choices=("llff", "blender"), default="llff")
     ap.add_argument("--images", type=int, default=20)
     ap.add_argument("--src-hw", type=int, nargs=2, default=(1512, 2016), dest="src_hw")
     ap.add_argument("--steps", type=int, default=200)
