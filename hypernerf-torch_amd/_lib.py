@@ -172,7 +172,7 @@ class HnAdamFuse(C.Structure):
 EXPORTS = ["hn_version", "hn_abi_sizes", "hn_build_config", "hn_mlp_wgrad_reduce_adam", "hn_render_prologue", "hn_pack_units", "hn_pack_units_multi", "hn_mlp_forward", "hn_mlp_backward", "hn_mlp_wgrad",
            "hn_mlp_wgrad_batched", "hn_mlp_wgrad_batched_t", "hn_mlp_wgrad_reduce", "hn_mlp_workspace_bytes",
            "hn_sample_along_rays", "hn_sample_legacy", "hn_posenc", "hn_composite_forward", "hn_composite_backward", "hn_sample_pdf", "hn_sample_pdf_split", "hn_composite_sample_pdf",
-           "hn_embed_gather", "hn_embed_backward", "hn_se3_apply_forward", "hn_se3_apply_backward", "hn_se3_warp_forward", "hn_se3_warp_backward", "hn_generate_rays", "hn_ray_batch", "hn_ray_batch_rgba", "hn_blend_white_u8", "hn_premultiply_u8", "hn_resample_u8", "hn_adam_step", "hn_sgd_step", "hn_radam_step",
+           "hn_embed_gather", "hn_embed_backward", "hn_se3_apply_forward", "hn_se3_apply_backward", "hn_se3_warp_forward", "hn_se3_warp_backward", "hn_generate_rays", "hn_ray_batch", "hn_ray_batch_rgba", "hn_generate_rays_nerfies", "hn_ray_batch_nerfies", "hn_blend_white_u8", "hn_premultiply_u8", "hn_resample_u8", "hn_adam_step", "hn_sgd_step", "hn_radam_step",
            "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad",
            "hn_ssim_workspace_bytes", "hn_ssim_forward", "hn_ssim_backward", "hn_depth_index", "hn_random_fill",
            "hn_probe_mfma", "hn_calib_mfma", "hn_calib_stream", "hn_calib_stream_pattern", "hn_calib_ring"]

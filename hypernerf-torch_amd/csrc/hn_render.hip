@@ -900,6 +900,89 @@ extern "C" int hn_generate_rays(int H, int W, float focal, const float* c2w, int
 }
 
 // ------------------------------------------------------------------------------------------------
+// Rays of a Nerfies-format capture (datasets/nerfies.py): every image has its own camera with a principal point, skew,
+// a pixel aspect ratio and radial + tangential lens distortion.  `cam` is that image's record of HN_NERFIES_CAM_FLOATS
+// floats: orientation (9, world to camera, rows), position (3), f, aspect, skew, cx, cy, k1, k2, k3, p1, p2, two zeros.
+// Pixel (col i, row j) has its centre at (i + 0.5, j + 0.5):
+//   y = (j + 0.5 - cy) / (f aspect);  x = (i + 0.5 - cx - y skew) / f;  (x, y) <- undistort(x, y)
+//   d = normalise(orientation^T normalise((x, y, 1)));  o = position
+// undistort is 10 Newton steps from (x, y) = (xd, yd) on  D x + 2 p1 x y + p2 (r + 2 x^2) = xd,
+// D y + 2 p2 x y + p1 (r + 2 y^2) = yd  with r = x^2 + y^2, D = 1 + r (k1 + r (k2 + k3 r)); a step whose determinant
+// is within 1e-9 of zero moves nothing.  It is skipped for a camera without distortion (one branch per image).
+// Shared by hn_generate_rays_nerfies_kernel and the Nerfies instance of hn_ray_batch_kernel; every operation is rounded
+// on its own, so that both write the same bits whatever either inlining context would contract.
+// ------------------------------------------------------------------------------------------------
+#define HN_NERFIES_CAM_FLOATS 24
+#define HN_NERFIES_NEWTON_STEPS 10
+
+__device__ __forceinline__ void hn_nerfies_pixel_ray(const float* cam, int i, int j, float o[3], float d[3]) {
+  const float f = cam[12], aspect = cam[13], skew = cam[14], cx = cam[15], cy = cam[16];
+  const float k1 = cam[17], k2 = cam[18], k3 = cam[19], p1 = cam[20], p2 = cam[21];
+  float y = __fdiv_rn(__fsub_rn(__fadd_rn((float)j, 0.5f), cy), __fmul_rn(f, aspect));
+  float x = __fdiv_rn(__fsub_rn(__fsub_rn(__fadd_rn((float)i, 0.5f), cx), __fmul_rn(y, skew)), f);
+  if (k1 != 0.0f || k2 != 0.0f || k3 != 0.0f || p1 != 0.0f || p2 != 0.0f) {
+    const float xd = x, yd = y;
+    for (int it = 0; it < HN_NERFIES_NEWTON_STEPS; ++it) {
+      const float xx = __fmul_rn(x, x), yy = __fmul_rn(y, y), xy = __fmul_rn(x, y);
+      const float r = __fadd_rn(xx, yy);
+      const float D = __fadd_rn(1.0f, __fmul_rn(r, __fadd_rn(k1, __fmul_rn(r, __fadd_rn(k2, __fmul_rn(k3, r))))));
+      const float fx = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(D, x), __fmul_rn(__fmul_rn(2.0f, p1), xy)),
+                                           __fmul_rn(p2, __fadd_rn(r, __fmul_rn(2.0f, xx)))), xd);
+      const float fy = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(D, y), __fmul_rn(__fmul_rn(2.0f, p2), xy)),
+                                           __fmul_rn(p1, __fadd_rn(r, __fmul_rn(2.0f, yy)))), yd);
+      const float D_r = __fadd_rn(k1, __fmul_rn(r, __fadd_rn(__fmul_rn(2.0f, k2), __fmul_rn(__fmul_rn(3.0f, k3), r))));
+      const float D_x = __fmul_rn(__fmul_rn(2.0f, x), D_r), D_y = __fmul_rn(__fmul_rn(2.0f, y), D_r);
+      const float fx_x = __fadd_rn(__fadd_rn(__fadd_rn(D, __fmul_rn(D_x, x)), __fmul_rn(__fmul_rn(2.0f, p1), y)),
+                                   __fmul_rn(__fmul_rn(6.0f, p2), x));
+      const float fx_y = __fadd_rn(__fadd_rn(__fmul_rn(D_y, x), __fmul_rn(__fmul_rn(2.0f, p1), x)),
+                                   __fmul_rn(__fmul_rn(2.0f, p2), y));
+      const float fy_x = __fadd_rn(__fadd_rn(__fmul_rn(D_x, y), __fmul_rn(__fmul_rn(2.0f, p2), y)),
+                                   __fmul_rn(__fmul_rn(2.0f, p1), x));
+      const float fy_y = __fadd_rn(__fadd_rn(__fadd_rn(D, __fmul_rn(D_y, y)), __fmul_rn(__fmul_rn(2.0f, p2), x)),
+                                   __fmul_rn(__fmul_rn(6.0f, p1), y));
+      const float den = __fsub_rn(__fmul_rn(fy_x, fx_y), __fmul_rn(fx_x, fy_y));
+      if (fabsf(den) > 1e-9f) {
+        x = __fadd_rn(x, __fdiv_rn(__fsub_rn(__fmul_rn(fx, fy_y), __fmul_rn(fy, fx_y)), den));
+        y = __fadd_rn(y, __fdiv_rn(__fsub_rn(__fmul_rn(fy, fx_x), __fmul_rn(fx, fy_x)), den));
+      }
+    }
+  }
+  const float ln = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), 1.0f));
+  const float lx = __fdiv_rn(x, ln), ly = __fdiv_rn(y, ln), lz = __fdiv_rn(1.0f, ln);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    d[k] = __fadd_rn(__fadd_rn(__fmul_rn(cam[k], lx), __fmul_rn(cam[3 + k], ly)), __fmul_rn(cam[6 + k], lz));
+    o[k] = cam[9 + k];
+  }
+  const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = __fdiv_rn(d[k], nrm);
+}
+
+__global__ void hn_generate_rays_nerfies_kernel(int H, int W, const float* cam, float near, float far, float image_id,
+                                                int row_floats, float* rays) {
+  const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= H * W) return;
+  const int j = pix / W, i = pix - j * W;
+  float d[3], o[3];
+  hn_nerfies_pixel_ray(cam, i, j, o, d);
+  float* r = rays + (size_t)pix * row_floats;
+  r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2]; r[6] = near; r[7] = far;
+  if (row_floats > 8) r[8] = image_id;
+}
+
+extern "C" int hn_generate_rays_nerfies(int H, int W, const float* cam, float near, float far, float image_id,
+                                        int row_floats, float* rays, hnStream_t stream) {
+  if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL || (row_floats != 8 && row_floats != 9)) return -2;
+  if (cam == nullptr || rays == nullptr) return -3;
+  const int n = H * W;
+  hipLaunchKernelGGL(hn_generate_rays_nerfies_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, H, W,
+                     cam, near, far, image_id, row_floats, rays);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // One training batch of an LLFF dataset gathered on the device (datasets/llff.py's all_rays / all_rgbs rows, in the
 // order a shuffled DataLoader reads them).  state[0] is the cursor into `perm`, state[1] an arrival counter, state[2]
 // an error flag: every workgroup reads the cursor, then arrives; the last to arrive advances the cursor by `batch` and
@@ -911,6 +994,10 @@ extern "C" int hn_generate_rays(int H, int W, float focal, const float* c2w, int
 //
 // CH = 3: the LLFF stack above.  CH = 4: a Blender stack of RGBA pixels (datasets/blender.py:57-58): the pixel is one
 // aligned 32-bit load and the colour is its blend onto white, hn_blend_white — the definition hn_blend_white_u8 uses.
+//
+// NERFIES = true: a Nerfies capture (datasets/nerfies.py).  `c2w` is then the (n_images, HN_NERFIES_CAM_FLOATS) camera
+// table and the row comes from hn_nerfies_pixel_ray with that slot's record; focal, ndc and ndc_near are not read.
+// The cursor, the arrival counter, the error flag, the NaN rows and the colour are this one definition for all three.
 // ------------------------------------------------------------------------------------------------
 // An RGBA pixel (little endian: R in the low byte, A in the high one) blended onto white as the reference does on
 // ToTensor values: x = c / 255 and al = a / 255 (divisions, rounded once), then x * al, 1 - al and their sum as three
@@ -923,7 +1010,7 @@ __device__ __forceinline__ void hn_blend_white(uint32_t px, float c[3]) {
     c[k] = __fadd_rn(__fmul_rn(__fdiv_rn((float)((px >> (8 * k)) & 0xffu), 255.0f), al), rest);
 }
 
-template <int CH>
+template <int CH, bool NERFIES>
 __global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, long long n_perm,
         unsigned long long* state, int batch, long long n_rays, int H, int W, float focal, const float* c2w,
         const float* image_ids, int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
@@ -949,7 +1036,10 @@ __global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, 
       const int pix = (int)(g - (long long)slot * hw);
       const int j = pix / W, i = pix - j * W;
       float d[3], o[3];
-      hn_pixel_ray(H, W, focal, c2w + 12 * slot, ndc, ndc_near, i, j, o, d);
+      if (NERFIES)
+        hn_nerfies_pixel_ray(c2w + (size_t)HN_NERFIES_CAM_FLOATS * slot, i, j, o, d);
+      else
+        hn_pixel_ray(H, W, focal, c2w + 12 * slot, ndc, ndc_near, i, j, o, d);
       r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2]; r[6] = near; r[7] = far;
       if (row_floats > 8) r[8] = image_ids[slot];
       if (CH == 4) {
@@ -975,12 +1065,12 @@ __global__ __launch_bounds__(256) void hn_ray_batch_kernel(const int64_t* perm, 
   }
 }
 
-template <int CH>
+template <int CH, bool NERFIES>
 static int hn_ray_batch_launch(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
                                long long n_rays, int H, int W, float focal, const float* c2w, const float* image_ids,
                                int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* px8,
                                float* rays, float* rgbs, hnStream_t stream) {
-  if (batch <= 0 || n_perm <= 0 || n_rays <= 0 || H <= 0 || W <= 0 || !(focal > 0.0f) ||
+  if (batch <= 0 || n_perm <= 0 || n_rays <= 0 || H <= 0 || W <= 0 || (!NERFIES && !(focal > 0.0f)) ||
       (row_floats != 8 && row_floats != 9))
     return -2;
   if (n_rays % ((long long)H * W) != 0) return -2;
@@ -988,7 +1078,7 @@ static int hn_ray_batch_launch(const int64_t* perm, long long n_perm, unsigned l
       (row_floats == 9 && image_ids == nullptr))
     return -3;
   if (CH == 4 && (reinterpret_cast<uintptr_t>(px8) & 3u) != 0) return -3;      // pixels are read as 32-bit words
-  hipLaunchKernelGGL(hn_ray_batch_kernel<CH>, dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, perm,
+  hipLaunchKernelGGL((hn_ray_batch_kernel<CH, NERFIES>), dim3((batch + 255) / 256), dim3(256), 0, (hipStream_t)stream, perm,
                      n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near, far, row_floats,
                      px8, rays, rgbs);
   HN_CHECK_LAUNCH();
@@ -999,7 +1089,7 @@ extern "C" int hn_ray_batch(const int64_t* perm, long long n_perm, unsigned long
                             long long n_rays, int H, int W, float focal, const float* c2w, const float* image_ids,
                             int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgb8,
                             float* rays, float* rgbs, hnStream_t stream) {
-  return hn_ray_batch_launch<3>(perm, n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near,
+  return hn_ray_batch_launch<3, false>(perm, n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near,
                                 far, row_floats, rgb8, rays, rgbs, stream);
 }
 
@@ -1007,8 +1097,16 @@ extern "C" int hn_ray_batch_rgba(const int64_t* perm, long long n_perm, unsigned
                                  long long n_rays, int H, int W, float focal, const float* c2w,
                                  const float* image_ids, int ndc, float ndc_near, float near, float far,
                                  int row_floats, const uint8_t* rgba8, float* rays, float* rgbs, hnStream_t stream) {
-  return hn_ray_batch_launch<4>(perm, n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near,
+  return hn_ray_batch_launch<4, false>(perm, n_perm, state, batch, n_rays, H, W, focal, c2w, image_ids, ndc, ndc_near, near,
                                 far, row_floats, rgba8, rays, rgbs, stream);
+}
+
+extern "C" int hn_ray_batch_nerfies(const int64_t* perm, long long n_perm, unsigned long long* state, int batch,
+                                    long long n_rays, int H, int W, const float* cams, const float* image_ids,
+                                    float near, float far, int row_floats, const uint8_t* rgb8, float* rays,
+                                    float* rgbs, hnStream_t stream) {
+  return hn_ray_batch_launch<3, true>(perm, n_perm, state, batch, n_rays, H, W, 0.0f, cams, image_ids, 0, 0.0f, near,
+                                      far, row_floats, rgb8, rays, rgbs, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Per-step training batches gathered on the GPU (hn_ray_batch, hn_ray_batch_rgba), in the order a shuffled DataLoader
+"""Per-step training batches gathered on the GPU (hn_ray_batch, hn_ray_batch_rgba, hn_ray_batch_nerfies), in the order a shuffled DataLoader
 reads them.
 
 `RayBatcher(dataset, batch_size, generator=g)` reproduces `DataLoader(dataset, batch_size, shuffle=True,
@@ -57,8 +57,9 @@ def distributed_sampler_order(n: int, rank: int, world: int, seed: int = 0, epoc
 class RayBatcher:
     def __init__(self, dataset, batch_size: int, generator: Optional[torch.Generator] = None, drop_last: bool = False,
                  seed: int = 0, group=None):
-        """dataset: an LLFFDataset or a BlenderDataset of split 'train' (anything with `n_rays`, `ray_cols`, `c2w` on
-        the device and `gather_batch(perm, state, rows, rays, rgbs)`).  generator / drop_last: DataLoader's; seed:
+        """dataset: an LLFFDataset, a BlenderDataset or a NerfiesDataset of split 'train' (anything with `n_rays`,
+        `ray_cols`, `c2w` on the device — the Nerfies camera table goes by that name too — and
+        `gather_batch(perm, state, rows, rays, rgbs)`).  generator / drop_last: DataLoader's; seed:
         DistributedSampler's (used only with torch.distributed initialised)."""
         if getattr(dataset, 'split', None) != 'train' or not hasattr(dataset, 'gather_batch'):
             raise ValueError("RayBatcher needs a 'train' split dataset")

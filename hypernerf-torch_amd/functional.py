@@ -1087,6 +1087,52 @@ def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, 
                ndc_near, image_ids)
 
 
+NERFIES_CAM_FLOATS = 24      # hn_kernels.h: orientation 9, position 3, f, aspect, skew, cx, cy, k1 k2 k3, p1 p2, 2 zeros
+
+
+def generate_rays_nerfies(h: int, w: int, cam: torch.Tensor, near: float, far: float,
+                          image_id: Optional[int] = None) -> torch.Tensor:
+    """(h*w, 8|9) ray rows [o, d, near, far(, image id)] of one image of a Nerfies-format capture, generated on the GPU
+    (hn_generate_rays_nerfies) from its camera record `cam` ((24,) fp32, datasets.nerfies.camera_record): pixel
+    centres at (i + 0.5, j + 0.5), principal point, skew, pixel aspect ratio, and 10 Newton steps that undo the radial
+    and tangential distortion."""
+    L.require_gpu(cam)
+    L.load()
+    if tuple(cam.shape) != (NERFIES_CAM_FLOATS,):
+        raise L.HnError(f"cam must be ({NERFIES_CAM_FLOATS},)")
+    c = cam.detach().contiguous().float()
+    cols = 9 if image_id is not None else 8
+    rays = torch.empty(h * w, cols, dtype=torch.float32, device=cam.device)
+    L.launch("hn_generate_rays_nerfies", C.c_int(h), C.c_int(w), L.ptr(c), C.c_float(near), C.c_float(far),
+             C.c_float(float(image_id or 0)), C.c_int(cols), L.ptr(rays), L.stream_handle())
+    return rays
+
+
+def ray_batch_nerfies(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, cams: torch.Tensor,
+                      rgb8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float, far: float,
+                      image_ids: Optional[torch.Tensor] = None) -> None:
+    """`ray_batch` over a Nerfies-format capture (hn_ray_batch_nerfies): `cams` is the (n_images, 24) fp32 table of
+    camera records and rays[:batch] holds the rows `generate_rays_nerfies` writes for those pixels, bit for bit (one
+    device function); perm, state, rgb8, rgbs, image_ids and the NaN rows are `ray_batch`'s."""
+    L.require_gpu(perm, state, cams, rgb8, rays, rgbs, image_ids)
+    L.load()
+    cols = rays.shape[1]
+    n_img = rgb8.shape[0]
+    ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
+          and cams.dtype == torch.float32 and cams.is_contiguous() and tuple(cams.shape) == (n_img, NERFIES_CAM_FLOATS)
+          and rgb8.dtype == torch.uint8 and rgb8.is_contiguous() and tuple(rgb8.shape[1:]) == (h, w, 3)
+          and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
+          and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
+          and rgbs.shape[0] >= batch and 0 < batch and perm.numel() > 0
+          and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
+    if not ok:
+        raise L.HnError("ray_batch_nerfies: bad shapes / dtypes")
+    L.launch("hn_ray_batch_nerfies", L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
+             C.c_longlong(rgb8.numel() // 3), C.c_int(h), C.c_int(w), L.ptr(cams),
+             L.ptr(image_ids if cols == 9 else None), C.c_float(near), C.c_float(far), C.c_int(cols), L.ptr(rgb8),
+             L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+
+
 def blend_white_u8(rgba8: torch.Tensor, with_mask: bool = False):
     """(..., 4) uint8 RGBA -> (N, 3) fp32 `rgb * a + (1 - a)` on u8 / 255 values, bit for bit the reference's blend
     (datasets/blender.py:58; hn_blend_white_u8: a multiply, a subtraction and an addition, each rounded).  With

@@ -644,6 +644,27 @@ int hn_ray_batch_rgba(const int64_t* perm_dev, long long n_perm, unsigned long l
                       int ndc, float ndc_near, float near, float far, int row_floats, const uint8_t* rgba8_dev,
                       float* rays_dev, float* rgbs_dev, hnStream_t stream);
 
+/* All rays of one H x W image of a Nerfies-format capture (datasets/nerfies.py), rows as hn_generate_rays writes them.
+ * cam_dev: that image's camera record of 24 fp32 on the device: orientation (9: world to camera, row-major),
+ * position (3), focal_length, pixel_aspect_ratio, skew, principal point (cx, cy), radial distortion (k1, k2, k3),
+ * tangential distortion (p1, p2), two zeros.  Pixel (col i, row j), centre (i + 0.5, j + 0.5):
+ *   y = (j + 0.5 - cy) / (f*aspect);  x = (i + 0.5 - cx - y*skew) / f;  (x, y) <- undistort(x, y);
+ *   direction = normalise(orientation^T normalise((x, y, 1)));  origin = position.
+ * undistort: exactly 10 Newton steps from the distorted point on  D x + 2 p1 x y + p2 (r + 2 x^2) = xd,
+ * D y + 2 p2 x y + p1 (r + 2 y^2) = yd,  r = x^2 + y^2,  D = 1 + r (k1 + r (k2 + k3 r)); a step whose determinant is
+ * within 1e-9 of zero moves nothing; skipped when all five coefficients are zero.  No NDC. */
+int hn_generate_rays_nerfies(int H, int W, const float* cam_dev, float near, float far, float image_id, int row_floats,
+                             float* rays_dev, hnStream_t stream);
+
+/* hn_ray_batch over a Nerfies-format capture: cams_dev is the (n_images, 24) fp32 table of the camera records above,
+ * rgb8_dev (n_rays, 3) uint8, and rays[r] is the row hn_generate_rays_nerfies writes for that pixel with cams_dev[slot]
+ * (one device function) and, for row_floats 9, image_ids_dev[slot].  Everything else — state words, NaN rows and the
+ * error flag, rgbs = u8 / 255 — as hn_ray_batch. */
+int hn_ray_batch_nerfies(const int64_t* perm_dev, long long n_perm, unsigned long long* state_dev, int batch,
+                         long long n_rays, int H, int W, const float* cams_dev, const float* image_ids_dev, float near,
+                         float far, int row_floats, const uint8_t* rgb8_dev, float* rays_dev, float* rgbs_dev,
+                         hnStream_t stream);
+
 /* The reference's blend of an RGBA image onto white (datasets/blender.py:58, :93-95) on ToTensor values:
  * rgbs[i][k] = fl(fl(fl(c_k / 255) * al) + fl(1 - al)), al = fl(a / 255) — every operation rounded on its own, no fused
  * multiply-add — and, when mask_dev != NULL, mask[i] = (a > 0) as one byte.  rgba8_dev: (n, 4) uint8, 4-byte aligned;

@@ -9,9 +9,15 @@
 
 `--dataset blender` (default: llff) measures the same parts on a Blender scene of RGBA images (20 images of 512 x 512
 resized to 436 x 436: as many rays as the LLFF scene within 0.3 %); its `kernel` part launches the RGB gather on the
-LLFF scene as well, so that one trace holds hn_ray_batch_kernel<3> and <4> side by side at 8 ray columns each.
+LLFF scene as well, so that one trace holds hn_ray_batch_kernel<3, false> and <4, false> side by side at 8 ray columns
+each.
 
-Scenes are synthetic and seeded (tests/llff_scene.py, tests/blender_scene.py), written to a temporary directory.  Times are host wall clock
+`--dataset nerfies` measures `steps` (batcher-fed only: there is no reference loader to feed a DataLoader from) and
+`kernel` on a Nerfies-format capture of 20 images of 504 x 378 at image_scale 1, every camera with lens distortion but
+the first (as many rays as the LLFF scene); its `kernel` part launches the LLFF gather as well, 9 ray columns each, so
+that one trace holds hn_ray_batch_kernel<3, false> and hn_ray_batch_kernel<3, true> (the Nerfies camera) side by side.
+
+Scenes are synthetic and seeded (tests/llff_scene.py, tests/blender_scene.py, tests/nerfies_scene.py), written to a temporary directory.  Times are host wall clock
 around work that ends in a device synchronise, after warm-up.
 """
 import argparse
@@ -29,8 +35,9 @@ import torch  # noqa: E402
 
 import hypernerf_torch_amd as HN  # noqa: E402
 from hypernerf_torch_amd import functional as F  # noqa: E402
-from hypernerf_torch_amd.datasets import BlenderDataset, LLFFDataset, RayBatcher, image_io  # noqa: E402
+from hypernerf_torch_amd.datasets import BlenderDataset, LLFFDataset, NerfiesDataset, RayBatcher, image_io  # noqa: E402
 import blender_scene  # noqa: E402
+import nerfies_scene  # noqa: E402
 from llff_scene import make_scene, write_scene  # noqa: E402
 
 DEV = "cuda:0"
@@ -40,6 +47,12 @@ BLENDER_SRC, BLENDER_WH = 512, (436, 436)
 def _blender_train(a, tmp, seed):
     scene = blender_scene.make_scene(seed=seed, size=BLENDER_SRC, frames=(("train", a.images),))
     return blender_scene.write_scene(os.path.join(tmp, f"blender{seed}"), scene)
+
+
+def _nerfies_train(a, tmp, seed):
+    scene = nerfies_scene.make_scene(seed, wh=(504, 378), n_train=a.images, n_val=0, image_scale=1)
+    root = nerfies_scene.write_scene(os.path.join(tmp, f"nerfies{seed}"), scene)
+    return NerfiesDataset(root, split="train", image_scale=1)
 
 
 def _sync_time(fn, reps=1):
@@ -86,6 +99,8 @@ def part_load_blender(a, tmp):
 def part_load(a, tmp):
     if a.dataset == "blender":
         return part_load_blender(a, tmp)
+    if a.dataset == "nerfies":
+        raise SystemExit("--dataset nerfies has no `load` part: its images are read as they are, without a resize")
     src_h, src_w = a.src_hw
     pix, pb = make_scene(a.images, src_h, src_w, seed=11, focal=1.1 * src_w)
     root = write_scene(os.path.join(tmp, "load"), pix, pb)
@@ -134,18 +149,28 @@ class _DictRays(torch.utils.data.Dataset):
         return {'rays': self.rays[i], 'rgbs': self.rgbs[i]}
 
 
-def _config2_step(batcher=None):
+def _config2_step(batcher=None, near=0.0, far=1.0):
     from gpu_common import EMB
     from hypernerf_torch_amd.hypernerf.models import NerfModel
     from hypernerf_torch_amd.training import TrainStep
     HN.set_precision("bf16")
     torch.manual_seed(0)
-    m = NerfModel(EMB, near=0.0, far=1.0, n_samples_coarse=64, n_samples_fine=64, noise_std=1.0, view_fourier_dim=6,
+    m = NerfModel(EMB, near=near, far=far, n_samples_coarse=64, n_samples_fine=64, noise_std=1.0, view_fourier_dim=6,
                   hyper_slice_method="bendy_sheet", use_warp=True, use_nerf_embed=True, use_alpha_cond=True).to(DEV)
     return TrainStep(m, lr=5e-4, batcher=batcher)
 
 
 def part_steps(a, tmp):
+    if a.dataset == "nerfies":
+        ds = _nerfies_train(a, tmp, 12)
+        ts = _config2_step(RayBatcher(ds, 1024, generator=torch.Generator().manual_seed(0)), near=ds.near, far=ds.far)
+        for _ in range(a.warmup):
+            ts.step()
+        dt = _sync_time(ts.step, reps=a.steps)
+        ts.batcher.check()
+        return {"part": "steps", "dataset": "nerfies", "rays": ds.n_rays, "batch": 1024, "steps": a.steps,
+                "warmup": a.warmup, "batcher_ms_per_step": dt * 1e3, "batcher_steps_per_s": 1.0 / dt,
+                "workload": "NerfModel use_warp bendy_sheet nerf_embed+alpha_cond, 1024 rays x (64+64), bf16, graphs"}
     if a.dataset == "blender":
         ds = BlenderDataset(_blender_train(a, tmp, 12), split="train", img_wh=BLENDER_WH)
         head = {"part": "steps", "dataset": "blender"}
@@ -209,12 +234,36 @@ def part_kernel_blender(a, tmp):
         bt.check()
     return {"part": "kernel", "dataset": "blender", "launches_each": n, "batch": 1024,
             "rays": {"llff": llff.n_rays, "blender": blender.n_rays}, "bytes_written_per_launch": 1024 * (8 + 3) * 4,
-            "kernels": {"llff": "hn_ray_batch_kernel<3>", "blender": "hn_ray_batch_kernel<4>"}}
+            "kernels": {"llff": "hn_ray_batch_kernel<3, false>", "blender": "hn_ray_batch_kernel<4, false>"}}
+
+
+def part_kernel_nerfies(a, tmp):
+    """The LLFF and the Nerfies gather in one process, 9 ray columns each, alternating in blocks of 50 launches."""
+    pix, pb = make_scene(a.images, 378, 504, seed=13, focal=400.0)
+    llff = LLFFDataset(write_scene(os.path.join(tmp, "kernel"), pix, pb), split="train", img_wh=(504, 378),
+                       include_idx=True)
+    nerfies = _nerfies_train(a, tmp, 13)
+    bts = [RayBatcher(ds, 1024, generator=torch.Generator().manual_seed(0)) for ds in (llff, nerfies)]
+    for bt in bts:
+        bt.begin_epoch()
+    n = min(a.steps * 10, min(bt.steps_per_epoch for bt in bts) - 1)
+    for k in range(0, n, 50):
+        for bt in bts:
+            for _ in range(min(50, n - k)):
+                bt.launch(1024)
+    torch.cuda.synchronize()
+    for bt in bts:
+        bt.check()
+    return {"part": "kernel", "dataset": "nerfies", "launches_each": n, "batch": 1024,
+            "rays": {"llff": llff.n_rays, "nerfies": nerfies.n_rays}, "bytes_written_per_launch": 1024 * (9 + 3) * 4,
+            "kernels": {"llff": "hn_ray_batch_kernel<3, false>", "nerfies": "hn_ray_batch_kernel<3, true>"}}
 
 
 def part_kernel(a, tmp):
     if a.dataset == "blender":
         return part_kernel_blender(a, tmp)
+    if a.dataset == "nerfies":
+        return part_kernel_nerfies(a, tmp)
     pix, pb = make_scene(a.images, 378, 504, seed=13, focal=400.0)
     root = write_scene(os.path.join(tmp, "kernel"), pix, pb)
     ds = LLFFDataset(root, split="train", img_wh=(504, 378), include_idx=True)
@@ -231,7 +280,7 @@ def part_kernel(a, tmp):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", choices=("load", "steps", "kernel"), required=True)
-    ap.add_argument("--dataset", choices=("llff", "blender"), default="llff")
+    ap.add_argument("--dataset", choices=("llff", "blender", "nerfies"), default="llff")
     ap.add_argument("--images", type=int, default=20)
     ap.add_argument("--src-hw", type=int, nargs=2, default=(1512, 2016), dest="src_hw")
     ap.add_argument("--steps", type=int, default=200)
