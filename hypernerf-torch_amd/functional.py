@@ -1024,6 +1024,88 @@ def ssim_dssim(pred: torch.Tensor, gt: torch.Tensor, window_size: int = 3, max_v
 
 
 # --------------------------------------------------------------------------------------------
+# multi-scale SSIM (the metric the Nerfies / HyperNeRF tables report)
+# --------------------------------------------------------------------------------------------
+MSSSIM_LEVELS = 5
+MSSSIM_MAX_SIZE = 11          # hn_msssim_forward: window sizes 1 .. 11
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+_MSSSIM_TILE_W, _MSSSIM_TILE_H = 32, 16
+_MSSSIM_PLANS: Dict[tuple, tuple] = {}
+
+
+def msssim_window(size: int) -> torch.Tensor:
+    """The 1-D taps of one level's window, float64: exp(-x^2 / (2 sigma^2)) with sigma = size * 1.5 / 11 at the integer
+    offsets -(size//2) .. size//2 (odd size) or the half-integer offsets -(size/2) + 0.5 .. size/2 - 0.5 (even size),
+    normalised to sum 1.  Their outer product is the normalised 2-D Gaussian of the original exactly."""
+    sigma = size * 1.5 / MSSSIM_MAX_SIZE
+    x = torch.arange(size, dtype=torch.float64) - (size - 1) / 2.0
+    g = torch.exp(-x * x / (2.0 * sigma * sigma))
+    return g / g.sum()
+
+
+def msssim_pyramid(h: int, w: int):
+    """[(h_l, w_l, size_l)] of the five levels: sides halve rounding up, size_l = min(11, h_l, w_l)."""
+    out = []
+    for _ in range(MSSSIM_LEVELS):
+        out.append((h, w, min(MSSSIM_MAX_SIZE, h, w)))
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return out
+
+
+def msssim_workspace_bytes(n: int, c: int, h: int, w: int) -> int:
+    """hn_msssim_workspace_bytes in Python: the planes of levels 1 .. 4 of both images, then two partial sums per
+    32 x 16 tile of every plane of levels 0 .. 4, in floats, rounded up to 16 bytes."""
+    pyr = msssim_pyramid(h, w)
+    floats = sum(2 * n * c * hl * wl for hl, wl, _ in pyr[1:])
+    floats += sum(2 * n * c * (-(-wl // _MSSSIM_TILE_W)) * (-(-hl // _MSSSIM_TILE_H)) for hl, wl, _ in pyr)
+    return (floats * 4 + 15) // 16 * 16
+
+
+def _msssim_plan(n, c, h, w):
+    """(taps, sizes, workspace floats) of a shape: host arrays built once (float64 taps rounded to fp32)."""
+    plan = _MSSSIM_PLANS.get((n, c, h, w))
+    if plan is None:
+        sizes = [s for _, _, s in msssim_pyramid(h, w)]
+        taps = (C.c_float * (MSSSIM_LEVELS * MSSSIM_MAX_SIZE))()
+        for l, s in enumerate(sizes):
+            for i, v in enumerate(msssim_window(s).tolist()):
+                taps[l * MSSSIM_MAX_SIZE + i] = v
+        nbytes = C.c_int64(0)
+        L.check(L.load().hn_msssim_workspace_bytes(n, c, h, w, C.byref(nbytes)), "hn_msssim_workspace_bytes")
+        plan = _MSSSIM_PLANS[(n, c, h, w)] = (taps, (C.c_int * MSSSIM_LEVELS)(*sizes), nbytes.value // 4)
+    return plan
+
+
+@torch.no_grad()
+def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) -> torch.Tensor:
+    """(N, 5, 2) fp32: per image and pyramid level the mean SSIM and the mean contrast-structure term of multi-scale
+    SSIM (hn_msssim_forward: one launch per level and one that adds the tiles' sums, bit-reproducible).  pred / gt:
+    (N, C, H, W) fp32 on the GPU, any element strides, any H, W >= 1 (the window shrinks to min(11, h, w)).  A metric:
+    the result carries no gradient.  The host plan (taps, sizes, workspace size) is cached per shape; the workspace
+    itself comes from torch's allocator at every call, as ssim_dssim's does, so a call captured in a HIP graph takes it
+    from the graph's pool and the host arrays are consumed at the launch."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
+        raise ValueError("ms_ssim: pred and gt must be tensors")
+    if pred.dim() != 4 or pred.shape != gt.shape:
+        raise ValueError(f"ms_ssim: pred and gt must both be (N, C, H, W) of one shape, got {tuple(pred.shape)} and "
+                         f"{tuple(gt.shape)}")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise ValueError("ms_ssim: pred and gt must be float32")
+    if pred.numel() == 0:
+        raise ValueError("ms_ssim: empty images")
+    L.require_gpu(pred, gt)
+    x, y = pred.detach(), gt.detach()
+    n, c, h, w = x.shape
+    taps, sizes, ws_floats = _msssim_plan(n, c, h, w)
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=x.device)
+    out = torch.empty((n, MSSSIM_LEVELS, 2), dtype=torch.float32, device=x.device)
+    L.launch("hn_msssim_forward", x.data_ptr(), (C.c_int64 * 4)(*x.stride()), y.data_ptr(), (C.c_int64 * 4)(*y.stride()),
+             n, c, h, w, taps, sizes, (0.01 * max_val) ** 2, (0.03 * max_val) ** 2, out.data_ptr(), ws.data_ptr(),
+             torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # on-device ray generation
 # --------------------------------------------------------------------------------------------
 def generate_rays(h: int, w: int, focal: float, c2w: torch.Tensor, near: float, far: float, ndc: bool = False,

@@ -171,7 +171,7 @@ def read_pfm(path: str):
 @torch.no_grad()
 def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False, save_dir=None, group=None,
                     image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm",
-                    use_valid_mask: bool = False) -> Dict:
+                    use_valid_mask: bool = False, ms_ssim: bool = False) -> Dict:
     """The per-image loop of the reference's eval.py:145-178 on the GPU: for every sample {'rays': (H*W, 8|9),
     'rgbs': (H*W, 3) optional, 'hw': (H, W) optional} render the fine level in chunks, form the (H, W, 3) image,
     its 8-bit version (eval.py:165 `(img*255).astype(uint8)`) and, when ground truth is present, the PSNR
@@ -185,7 +185,10 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     The reference's GIF of all frames (eval.py:172, imageio.mimsave) is not written: the frames are in the result.
     `white_back` is accepted and ignored as in the reference's batched_inference (eval.py:77-85).
     `use_valid_mask` restricts the PSNR to the sample's 'valid_mask' ((H*W,) bool; the Blender splits carry alpha > 0)
-    through metrics.psnr's own argument; off by default, as the reference's eval.py does not mask."""
+    through metrics.psnr's own argument; off by default, as the reference's eval.py does not mask.
+    `ms_ssim` adds the multi-scale SSIM (losses.ms_ssim, the metric of the published Nerfies / HyperNeRF tables) of every
+    image with ground truth, on the same views as the SSIM: the result then also has 'ms_ssims': [float] and
+    'mean_ms_ssim': float | None.  Off by default: the result and the work done are unchanged."""
     if image_format not in ("png", "ppm"):
         raise ValueError("image_format: 'png' or 'ppm'")
     if depth_format not in ("pfm", "bytes"):
@@ -194,7 +197,8 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
         raise ValueError("save_depth needs save_dir")
     from .losses import psnr as _psnr
     from .losses import ssim as _ssim
-    imgs, depths, psnrs, ssims = [], [], [], []
+    from .losses import ms_ssim as _ms_ssim
+    imgs, depths, psnrs, ssims, ms_ssims = [], [], [], [], []
     for i, sample in enumerate(images):
         rays = sample['rays']
         res = render_image(model, rays, chunk=chunk, keys=('rgb', 'depth'), group=group)
@@ -209,6 +213,8 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
             mask = sample.get('valid_mask') if use_valid_mask else None
             psnrs.append(float(_psnr(gt, img, None if mask is None else mask.to(img.device).view(h, w))))
             ssims.append(float(_ssim(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None])))
+            if ms_ssim:
+                ms_ssims.append(float(_ms_ssim(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None])))
         if save_dir is not None:
             import os
             os.makedirs(save_dir, exist_ok=True)
@@ -223,6 +229,10 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
             else:
                 with open(os.path.join(save_dir, f"{i:03d}.ppm"), "wb") as f:
                     f.write(f"P6 {w} {h} 255\n".encode() + img8.numpy().tobytes())
-    return {'images': imgs, 'depths': depths, 'psnrs': psnrs,
-            'mean_psnr': (sum(psnrs) / len(psnrs)) if psnrs else None,
-            'ssims': ssims, 'mean_ssim': (sum(ssims) / len(ssims)) if ssims else None}
+    out = {'images': imgs, 'depths': depths, 'psnrs': psnrs,
+           'mean_psnr': (sum(psnrs) / len(psnrs)) if psnrs else None,
+           'ssims': ssims, 'mean_ssim': (sum(ssims) / len(ssims)) if ssims else None}
+    if ms_ssim:
+        out['ms_ssims'] = ms_ssims
+        out['mean_ms_ssim'] = (sum(ms_ssims) / len(ms_ssims)) if ms_ssims else None
+    return out

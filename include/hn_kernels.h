@@ -584,6 +584,27 @@ int hn_ssim_backward(const float* pred, const int64_t* pred_strides, const float
                      int c, int h, int w, const float* window_host, int window, float c1, float c2, float eps,
                      const float* g_scalar, const float* g_map, float* d_pred, float* d_gt, hnStream_t stream);
 
+/* Multi-scale SSIM (the widely used NumPy `MultiScaleSSIM`, max_val folded into c1 / c2): a metric, no backward.  Five
+ * levels; level 0 is the caller's pair pred / gt, fp32 (n, c, h, w) with arbitrary element strides (`*_strides`: HOST
+ * arrays of 4), level l + 1 the 2 x 2 box mean of level l (out[i][j] = mean(in[2i..2i+1][2j..2j+1]), an index past the
+ * edge replaced by the edge pixel, sides (h+1)/2 x (w+1)/2).  Per level the five moments are VALID correlations (no
+ * padding, (h_l - size_l + 1) x (w_l - size_l + 1) outputs) with the outer product of the level's 1-D window:
+ * taps_host = HOST array of 5 x 11 floats, row l holding sizes_host[l] taps; sizes_host = HOST array of 5 ints, each
+ * 1 .. 11 and no larger than either side of its level (the metric uses min(11, h_l, w_l), sigma = size * 1.5 / 11, even
+ * sizes sampled at half-integer offsets).  With s11 = E[xx] - mu1^2 etc., v1 = 2 s12 + c2, v2 = s11 + s22 + c2,
+ *   levels_out[i][l][0] = mean(((2 mu1 mu2 + c1) v1) / ((mu1^2 + mu2^2 + c1) v2)),  levels_out[i][l][1] = mean(v1 / v2),
+ * the means over all valid positions and all channels of image i; levels_out: (n, 5, 2) DEVICE floats, written.  The
+ * product over the levels is left to the caller.  `workspace` (hn_msssim_workspace_bytes: host arithmetic) holds, in
+ * floats, the planes of levels 1 .. 4 (per level the (n, c, h_l, w_l) first image, then the second), then per level
+ * 0 .. 4 two partial sums per workgroup (one workgroup per 32 x 16 input tile of a plane); six launches, the last adds
+ * the partial sums in a fixed order: no float atomics, bit-reproducible.  The host arrays are consumed at the call.
+ * Status: -2 for every refused argument (n, c, h, w < 1, a NULL pointer, a size outside 1 .. 11 or above its level's
+ * sides), checked before the first launch. */
+int hn_msssim_workspace_bytes(int n, int c, int h, int w, int64_t* bytes);
+int hn_msssim_forward(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int n,
+                      int c, int h, int w, const float* taps_host, const int* sizes_host, float c1, float c2,
+                      float* levels_out, void* workspace, hnStream_t stream);
+
 /* torch.optim.Adam (the reference's default optimizer, utils/__init__.py get_optimizer) over ONE flat fp32 buffer
  * (ParamArena): p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps), m,v updated first, L2 weight decay added to the
  * gradient.  `hyper_dev`: 8 floats ON THE DEVICE, [lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0] — read by the
