@@ -1,15 +1,72 @@
-// Fused SGD, RAdam and Ranger over a flat parameter arena: the other three optimizers of the reference's get_optimizer
-// (utils/__init__.py:23-41; RAdam and Ranger from utils/optimizers.py:6-95 and :266-405), built like hn_adam_kernel
-// (hn_render.hip): a grid-stride pass of at most 256 blocks x 256 threads over f32x4 vectors (scalar tail), the step
-// counter on the device and advanced by the last block (hn_adam_ticket), the gradient cleared on the way out.
+// Fused optimizer steps over a flat parameter arena: Adam (torch.optim.Adam, utils.get_optimizer's default) and the other
+// three optimizers of the reference's get_optimizer — SGD, RAdam and Ranger (utils/__init__.py:23-41; RAdam and Ranger
+// from utils/optimizers.py:6-95 and :266-405).  All are built alike: a grid-stride pass of at most 256 blocks x 256
+// threads over f32x4 vectors (scalar tail), the step counter on the device and advanced by the last block
+// (hn_adam_ticket), the gradient cleared on the way out.
 //
-// The reference computes its schedule scalars (beta^t, N_sma, the step size and the products with lr) as Python doubles
-// and hands them to fp32 tensor ops, which round them once.  Here thread 0 of every block does the same in fp64 from the
-// device step counter and the fp64 hyper-parameter array, rounds each coefficient to fp32 once and passes them and the
-// branch flags to the block through LDS.  (fp32 is not enough: for beta2 = 0.999 it puts N_sma at t = 6 at 6.0005
-// instead of 5.9942, and the first rectified step size 0.3 % off.)  The per-element arithmetic is the reference's fp32
-// tensor arithmetic, operation for operation.
+// For SGD, RAdam and Ranger the reference computes its schedule scalars (beta^t, N_sma, the step size and the products
+// with lr) as Python doubles and hands them to fp32 tensor ops, which round them once.  Here thread 0 of every block does
+// the same in fp64 from the device step counter and the fp64 hyper-parameter array, rounds each coefficient to fp32 once
+// and passes them and the branch flags to the block through LDS.  (fp32 is not enough: for beta2 = 0.999 it puts N_sma at
+// t = 6 at 6.0005 instead of 5.9942, and the first rectified step size 0.3 % off.)  The per-element arithmetic is the
+// reference's fp32 tensor arithmetic, operation for operation.
 #include "hn_common.h"
+
+// The launch grid of every *_step entry point: one block per CU, grid-stride: every thread pays the schedule arithmetic
+// (Adam: two powf, an rsqrtf) once for ~6 vectors instead of once per vector (Adam, 2048 blocks: 26.3 us per launch at
+// config 2, 512: 16.5, 256: 15.2)
+static unsigned hn_step_blocks(long long n) {
+  const long long blocks = (n / 4 + 255) / 256;
+  return (unsigned)(blocks > 256 ? 256 : blocks < 1 ? 1 : blocks);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Fused Adam over a flat parameter arena (torch.optim.Adam semantics, utils.get_optimizer's default):
+// one pass over p, g, m, v (28 B/parameter, HBM bound), the step counter lives on the device so the launch can be
+// captured in a HIP graph, and the gradient is zeroed on the way out (saves the separate fill of the next step).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_adam_kernel(float* p, float* g, float* m, float* v, long long n,
+                                                       const float* __restrict__ hyper, float* step,
+                                                       int zero_grad) {
+  // every block reads step[0] (hn_adam_consts) before it does anything else; the block that finishes LAST advances it
+  const HnAdamConsts k = hn_adam_consts(hyper, step);
+  const long long stride = (long long)gridDim.x * blockDim.x * 4;
+  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 4 <= n) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + i), gg = *reinterpret_cast<f32x4*>(g + i);
+      f32x4 mm = *reinterpret_cast<f32x4*>(m + i), vv = *reinterpret_cast<f32x4*>(v + i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        hn_adam_update(k, pe, gg[e], me, ve);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + i) = pp;
+      *reinterpret_cast<f32x4*>(m + i) = mm;
+      *reinterpret_cast<f32x4*>(v + i) = vv;
+      if (zero_grad) *reinterpret_cast<f32x4*>(g + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      for (long long j = i; j < n; ++j) {
+        hn_adam_update(k, p[j], g[j], m[j], v[j]);
+        if (zero_grad) g[j] = 0.f;
+      }
+    }
+  }
+  hn_adam_ticket(step, k.t);
+}
+
+extern "C" int hn_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long long n,
+                            const float* hyper_dev, float* step_dev, int zero_grad, hnStream_t stream) {
+  if (n <= 0) return -2;
+  if (params == nullptr || grads == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || step_dev == nullptr ||
+      hyper_dev == nullptr)
+    return -3;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) return -4;
+  hipLaunchKernelGGL(hn_adam_kernel, dim3(hn_step_blocks(n)), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg,
+                     exp_avg_sq, n, hyper_dev, step_dev, zero_grad);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // SGD (torch.optim.SGD, which get_optimizer builds directly): d = g*gscale + wd*p; with momentum buf = d on update 1,
@@ -91,10 +148,7 @@ extern "C" int hn_sgd_step(float* params, float* grads, float* momentum_buf, lon
   if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) != 0 || ((uintptr_t)hyper_dev & 7) != 0 ||
       ((uintptr_t)step_dev & 3) != 0)
     return -4;
-  long long blocks = (n / 4 + 255) / 256;
-  if (blocks > 256) blocks = 256;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(hn_sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads,
+  hipLaunchKernelGGL(hn_sgd_kernel, dim3(hn_step_blocks(n)), dim3(256), 0, (hipStream_t)stream, params, grads,
                      momentum_buf, n, hyper_dev, step_dev, zero_grad);
   HN_CHECK_LAUNCH();
   return 0;
@@ -219,14 +273,11 @@ extern "C" int hn_radam_step(float* params, float* grads, float* exp_avg, float*
   if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)slow) & 15) != 0 ||
       ((uintptr_t)hyper_dev & 7) != 0 || ((uintptr_t)step_dev & 3) != 0)
     return -4;
-  long long blocks = (n / 4 + 255) / 256;
-  if (blocks > 256) blocks = 256;
-  if (blocks < 1) blocks = 1;
   if (slow != nullptr)
-    hipLaunchKernelGGL(hn_radam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads,
+    hipLaunchKernelGGL(hn_radam_kernel<true>, dim3(hn_step_blocks(n)), dim3(256), 0, (hipStream_t)stream, params, grads,
                        exp_avg, exp_avg_sq, slow, n, k, hyper_dev, step_dev, zero_grad);
   else
-    hipLaunchKernelGGL(hn_radam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, params, grads,
+    hipLaunchKernelGGL(hn_radam_kernel<false>, dim3(hn_step_blocks(n)), dim3(256), 0, (hipStream_t)stream, params, grads,
                        exp_avg, exp_avg_sq, slow, n, k, hyper_dev, step_dev, zero_grad);
   HN_CHECK_LAUNCH();
   return 0;

@@ -57,10 +57,9 @@ def distributed_sampler_order(n: int, rank: int, world: int, seed: int = 0, epoc
 class RayBatcher:
     def __init__(self, dataset, batch_size: int, generator: Optional[torch.Generator] = None, drop_last: bool = False,
                  seed: int = 0, group=None):
-        """dataset: an LLFFDataset, a BlenderDataset or a NerfiesDataset of split 'train' (anything with `n_rays`,
-        `ray_cols`, `c2w` on the device — the Nerfies camera table goes by that name too — and
-        `gather_batch(perm, state, rows, rays, rgbs)`).  generator / drop_last: DataLoader's; seed:
-        DistributedSampler's (used only with torch.distributed initialised)."""
+        """dataset: an LLFFDataset, a BlenderDataset or a NerfiesDataset of split 'train' (anything with `split`,
+        `n_rays`, `ray_cols`, `device` and `gather_batch(perm, state, rows, rays, rgbs)`).  generator / drop_last:
+        DataLoader's; seed: DistributedSampler's (used only with torch.distributed initialised)."""
         if getattr(dataset, 'split', None) != 'train' or not hasattr(dataset, 'gather_batch'):
             raise ValueError("RayBatcher needs a 'train' split dataset")
         if batch_size <= 0:
@@ -79,7 +78,7 @@ class RayBatcher:
         if self.drop_last and self.n_samples < self.batch_size:
             raise ValueError("drop_last with fewer rays than one batch leaves no step")
         self.epoch = 0
-        dev = dataset.c2w.device
+        dev = dataset.device
         self.perm = torch.zeros(self.n_samples, dtype=torch.int64, device=dev)
         self.state = torch.zeros(3, dtype=torch.int64, device=dev)      # [cursor, arrival counter, error flag]
         self.rays = torch.empty((self.batch_size, dataset.ray_cols), dtype=torch.float32, device=dev)

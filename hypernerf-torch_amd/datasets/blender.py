@@ -17,9 +17,9 @@ import os
 
 import numpy as np
 import torch
-from torch.utils.data import Dataset
 
 from . import image_io
+from .base import GpuRayDataset
 
 SPLITS = ("train", "val", "test")
 VAL_IMAGES = 8               # the reference validates on 8 images only ("to support <= 8 gpus")
@@ -35,11 +35,12 @@ def read_transforms(root_dir: str, split: str, img_wh):
     return meta, focal
 
 
-class BlenderDataset(Dataset):
+class BlenderDataset(GpuRayDataset):
     def __init__(self, root_dir: str, split: str = 'train', img_wh=(800, 800), device=None, use_pillow: bool = True):
         """The reference's constructor (datasets/blender.py:12-20).  `device` (default: the current GPU) holds the
         images and generated rays; `use_pillow=False` decodes with the package's own PNG reader even when Pillow is
         installed."""
+        super().__init__(device)
         self.root_dir = root_dir
         self.split = split
         if img_wh[0] != img_wh[1]:
@@ -47,14 +48,7 @@ class BlenderDataset(Dataset):
         self.img_wh = tuple(int(v) for v in img_wh)
         self.white_back = True
         self._use_pillow = use_pillow
-        self._device = device
         self.read_meta()
-
-    @property
-    def device(self) -> torch.device:
-        if self._device is None:
-            self._device = torch.device('cuda', torch.cuda.current_device())
-        return torch.device(self._device)
 
     def read_meta(self):
         self.meta, self.focal = read_transforms(self.root_dir, self.split, self.img_wh)
@@ -64,7 +58,6 @@ class BlenderDataset(Dataset):
         frames = self.meta['frames']
         self.poses = [np.array(f['transform_matrix'])[:3, :4] for f in frames]
         self.image_paths = [os.path.join(self.root_dir, f"{f['file_path']}.png") for f in frames]
-        self._all_rays = self._all_rgbs = None
         if self.split == 'train':
             self._load_train_images()
 
@@ -90,24 +83,13 @@ class BlenderDataset(Dataset):
         w, h = self.img_wh
         return F.generate_rays(h, w, float(self.focal), c2w, near=self.near, far=self.far, ndc=False)
 
-    @property
-    def all_rays(self) -> torch.Tensor:
-        """(N_train*H*W, 8) fp32 on the device, built on first access."""
-        if self.split != 'train':
-            raise AttributeError(f"all_rays exists for the 'train' split only (this is '{self.split}')")
-        if self._all_rays is None:
-            self._all_rays = torch.cat([self._rays_of(c) for c in self.c2w], 0)
-        return self._all_rays
+    def _build_all_rays(self) -> torch.Tensor:
+        return torch.cat([self._rays_of(c) for c in self.c2w], 0)
 
-    @property
-    def all_rgbs(self) -> torch.Tensor:
-        """(N_train*H*W, 3) fp32 on the device, every pixel blended onto white, built on first access."""
-        if self.split != 'train':
-            raise AttributeError(f"all_rgbs exists for the 'train' split only (this is '{self.split}')")
-        if self._all_rgbs is None:
-            from .. import functional as F
-            self._all_rgbs = F.blend_white_u8(self.rgba8)
-        return self._all_rgbs
+    def _build_all_rgbs(self) -> torch.Tensor:
+        """Every pixel blended onto white."""
+        from .. import functional as F
+        return F.blend_white_u8(self.rgba8)
 
     @property
     def n_rays(self) -> int:
@@ -130,11 +112,10 @@ class BlenderDataset(Dataset):
             return VAL_IMAGES
         return len(self.meta['frames'])
 
-    def __getitem__(self, idx):
-        if self.split == 'train':
-            return {'rays': self.all_rays[idx], 'rgbs': self.all_rgbs[idx]}
-        if not -len(self.poses) <= idx < min(len(self), len(self.poses)):
-            raise IndexError(idx)             # ends iteration (evaluate_images loops over the dataset)
+    def _index_range(self):
+        return -len(self.poses), min(len(self), len(self.poses))
+
+    def _view(self, idx):
         from .. import functional as F
         c2w = torch.tensor(self.poses[idx], dtype=torch.float32).to(self.device)
         rgbs, valid_mask = F.blend_white_u8(self._to_device_resized(self.image_paths[idx]), with_mask=True)

@@ -14,9 +14,9 @@ from typing import Dict, List, Optional
 
 import numpy as np
 import torch
-from torch.utils.data import Dataset
 
 from . import image_io
+from .base import GpuRayDataset, u8_to_unit
 
 SPLITS = ("train", "val", "test")      # and any split ending in 'train' (the test path over the training poses)
 
@@ -114,24 +114,13 @@ def render_poses(poses: np.ndarray, bounds: np.ndarray, split: str, spheric_pose
 # --------------------------------------------------------------------------------------------
 # the dataset
 # --------------------------------------------------------------------------------------------
-_U8_TO_FLOAT = None
-
-
-def u8_to_unit(x: torch.Tensor) -> torch.Tensor:
-    """uint8 -> fp32 x / 255 rounded once (torchvision's ToTensor; a device multiply by 1/255 would differ in the last
-    bit for some values): a 256-entry table divided on the host, gathered on the device."""
-    global _U8_TO_FLOAT
-    if _U8_TO_FLOAT is None:
-        _U8_TO_FLOAT = torch.arange(256, dtype=torch.float32) / 255
-    return _U8_TO_FLOAT.to(x.device)[x.long()]
-
-
-class LLFFDataset(Dataset):
+class LLFFDataset(GpuRayDataset):
     def __init__(self, root_dir: str, split: str = 'train', img_wh=(504, 378), spheric_poses: bool = False,
                  val_num: int = 1, include_idx: bool = False, device=None, use_pillow: bool = True):
         """The reference's constructor (datasets/llff.py:174-193).  `device` (default: the current GPU) holds the
         images and generated rays; `use_pillow=False` decodes with the package's own PNG reader even when Pillow is
         installed."""
+        super().__init__(device)
         self.root_dir = root_dir
         self.split = split
         self.img_wh = tuple(int(v) for v in img_wh)
@@ -140,18 +129,11 @@ class LLFFDataset(Dataset):
         self.include_idx = bool(include_idx)
         self.white_back = False
         self._use_pillow = use_pillow
-        self._device = device
         if include_idx and split not in ('train', 'val'):
             # the reference fails here with AttributeError in __getitem__ (val_idx_list is set for 'val' only)
             raise ValueError(f"include_idx=True is not supported for split '{split}': the reference's test splits "
                              "carry no image index")
         self.read_meta()
-
-    @property
-    def device(self) -> torch.device:
-        if self._device is None:
-            self._device = torch.device('cuda', torch.cuda.current_device())
-        return torch.device(self._device)
 
     def read_meta(self):
         self.image_paths = sorted(glob.glob(os.path.join(self.root_dir, 'images/*')))
@@ -164,7 +146,6 @@ class LLFFDataset(Dataset):
         self.poses, self.pose_avg, self.bounds = meta['poses'], meta['pose_avg'], meta['bounds']
         self.val_idx = meta['val_idx']
         self.near, self.far = meta['near'], meta['far']
-        self._all_rays = self._all_rgbs = None
         if self.split == 'train':
             self.train_ids: List[int] = [i for i in range(len(self.image_paths)) if i != self.val_idx]
             self._load_train_images()
@@ -205,34 +186,15 @@ class LLFFDataset(Dataset):
         self.image_ids = torch.tensor(self.train_ids, dtype=torch.float32).to(self.device)
 
     # ---- rays --------------------------------------------------------------------------------------
-    @property
-    def ray_cols(self) -> int:
-        return 9 if self.include_idx else 8
-
     def _rays_of(self, c2w: torch.Tensor, image_id: Optional[int]) -> torch.Tensor:
         from .. import functional as F
         w, h = self.img_wh
         return F.generate_rays(h, w, float(self.focal), c2w, near=float(self.near), far=float(self.far),
                                ndc=not self.spheric_poses, ndc_near=1.0, image_id=image_id)
 
-    @property
-    def all_rays(self) -> torch.Tensor:
-        """(N_train*H*W, 8|9) fp32 on the device, built on first access."""
-        if self.split != 'train':
-            raise AttributeError(f"all_rays exists for the 'train' split only (this is '{self.split}')")
-        if self._all_rays is None:
-            self._all_rays = torch.cat([self._rays_of(self.c2w[k], i if self.include_idx else None)
-                                        for k, i in enumerate(self.train_ids)], 0)
-        return self._all_rays
-
-    @property
-    def all_rgbs(self) -> torch.Tensor:
-        """(N_train*H*W, 3) fp32 in [0, 1] on the device, built on first access."""
-        if self.split != 'train':
-            raise AttributeError(f"all_rgbs exists for the 'train' split only (this is '{self.split}')")
-        if self._all_rgbs is None:
-            self._all_rgbs = u8_to_unit(self.rgb8.reshape(-1, 3))
-        return self._all_rgbs
+    def _build_all_rays(self) -> torch.Tensor:
+        return torch.cat([self._rays_of(self.c2w[k], i if self.include_idx else None)
+                          for k, i in enumerate(self.train_ids)], 0)
 
     @property
     def n_rays(self) -> int:
@@ -256,11 +218,7 @@ class LLFFDataset(Dataset):
             return self.val_num
         return len(self.poses_test)
 
-    def __getitem__(self, idx):
-        if self.split == 'train':
-            return {'rays': self.all_rays[idx], 'rgbs': self.all_rgbs[idx]}
-        if not -len(self) <= idx < len(self):
-            raise IndexError(idx)             # ends iteration (evaluate_images loops over the dataset)
+    def _view(self, idx):
         pose = self.c2w_val if self.split == 'val' else self.poses_test[idx]
         c2w = torch.tensor(pose, dtype=torch.float32).to(self.device)
         image_id = self.val_idx_list[0] if self.include_idx else None

@@ -30,9 +30,9 @@ from typing import Dict, List, Optional
 
 import numpy as np
 import torch
-from torch.utils.data import Dataset
 
 from . import image_io
+from .base import GpuRayDataset, u8_to_unit
 
 SPLITS = ("train", "val", "test")
 METADATA_KEYS = ("warp_id", "appearance_id", "camera_id")
@@ -90,7 +90,7 @@ def camera_record(cam: Dict) -> np.ndarray:
     return rec.astype(np.float32)
 
 
-class NerfiesDataset(Dataset):
+class NerfiesDataset(GpuRayDataset):
     def __init__(self, root_dir: str, split: str = 'train', image_scale: int = 4, include_idx: bool = True,
                  metadata_key: str = 'warp_id', camera_path: Optional[str] = None, test_id: int = 0, device=None,
                  use_pillow: bool = True):
@@ -105,6 +105,7 @@ class NerfiesDataset(Dataset):
             raise ValueError(f"metadata_key must be one of {METADATA_KEYS} (got '{metadata_key}')")
         if split == 'test' and camera_path is None:
             raise ValueError("split 'test' needs camera_path (a directory name under camera-paths/)")
+        super().__init__(device)
         self.root_dir = root_dir
         self.split = split
         self.image_scale = image_scale
@@ -114,14 +115,7 @@ class NerfiesDataset(Dataset):
         self.test_id = int(test_id)
         self.white_back = False
         self._use_pillow = use_pillow
-        self._device = device
         self.read_meta()
-
-    @property
-    def device(self) -> torch.device:
-        if self._device is None:
-            self._device = torch.device('cuda', torch.cuda.current_device())
-        return torch.device(self._device)
 
     # ---- host metadata ---------------------------------------------------------------------------
     def _load_camera(self, path: str) -> Dict:
@@ -155,7 +149,6 @@ class NerfiesDataset(Dataset):
             vals = [int(m[name + '_id']) for m in self.metadata.values() if name + '_id' in m]
             self.num_embeddings[name] = (max(vals) + 1) if vals else 0
 
-        self._all_rays = self._all_rgbs = None
         if self.split == 'test':
             cam_dir = os.path.join(root, 'camera-paths', self.camera_path)
             paths = sorted(glob.glob(os.path.join(cam_dir, '*.json')))
@@ -213,38 +206,18 @@ class NerfiesDataset(Dataset):
         for k, path in enumerate(self.image_paths):
             self.rgb8[k] = self._decode(path)
         self.cams = torch.from_numpy(self.camera_table).to(self.device).contiguous()
-        self.c2w = self.cams          # the name RayBatcher reads its device from: this dataset's per-image camera table
+        self.c2w = self.cams
         self.image_ids = torch.tensor(self.metadata_ids, dtype=torch.float32).to(self.device)
 
     # ---- rays --------------------------------------------------------------------------------------
-    @property
-    def ray_cols(self) -> int:
-        return 9 if self.include_idx else 8
-
     def _rays_of(self, cam: torch.Tensor, image_id: int) -> torch.Tensor:
         from .. import functional as F
         w, h = self.img_wh
         return F.generate_rays_nerfies(h, w, cam, near=self.near, far=self.far,
                                        image_id=image_id if self.include_idx else None)
 
-    @property
-    def all_rays(self) -> torch.Tensor:
-        """(N_train*H*W, 8|9) fp32 on the device, built on first access."""
-        if self.split != 'train':
-            raise AttributeError(f"all_rays exists for the 'train' split only (this is '{self.split}')")
-        if self._all_rays is None:
-            self._all_rays = torch.cat([self._rays_of(self.cams[k], i) for k, i in enumerate(self.metadata_ids)], 0)
-        return self._all_rays
-
-    @property
-    def all_rgbs(self) -> torch.Tensor:
-        """(N_train*H*W, 3) fp32 in [0, 1] on the device, built on first access."""
-        if self.split != 'train':
-            raise AttributeError(f"all_rgbs exists for the 'train' split only (this is '{self.split}')")
-        if self._all_rgbs is None:
-            from .llff import u8_to_unit
-            self._all_rgbs = u8_to_unit(self.rgb8.reshape(-1, 3))
-        return self._all_rgbs
+    def _build_all_rays(self) -> torch.Tensor:
+        return torch.cat([self._rays_of(self.cams[k], i) for k, i in enumerate(self.metadata_ids)], 0)
 
     @property
     def n_rays(self) -> int:
@@ -263,12 +236,7 @@ class NerfiesDataset(Dataset):
     def __len__(self):
         return self.n_rays if self.split == 'train' else len(self.ids)
 
-    def __getitem__(self, idx):
-        if self.split == 'train':
-            return {'rays': self.all_rays[idx], 'rgbs': self.all_rgbs[idx]}
-        if not -len(self) <= idx < len(self):
-            raise IndexError(idx)             # ends iteration (evaluate_images loops over the dataset)
-        from .llff import u8_to_unit
+    def _view(self, idx):
         cam = torch.from_numpy(self.camera_table[idx]).to(self.device)
         w, h = self.img_wh
         sample = {'rays': self._rays_of(cam, self.metadata_ids[idx]), 'camera': cam, 'hw': (h, w)}

@@ -1108,31 +1108,40 @@ def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) ->
 # --------------------------------------------------------------------------------------------
 # on-device ray generation
 # --------------------------------------------------------------------------------------------
+def _generate_rays(entry: str, h: int, w: int, name: str, table: torch.Tensor, shape: tuple, before: tuple, after: tuple,
+                   near: float, far: float, image_id: Optional[int]) -> torch.Tensor:
+    """Allocate the (h*w, 8|9) rows of one image and launch `entry` over them; `table` (the pose or camera record, of
+    `shape`) sits between the entry's own arguments `before` and `after`."""
+    L.require_gpu(table)
+    L.load()
+    if tuple(table.shape) != shape:
+        raise L.HnError(f"{name} must be {shape}")
+    t = table.detach().contiguous().float()
+    cols = 9 if image_id is not None else 8
+    rays = torch.empty(h * w, cols, dtype=torch.float32, device=table.device)
+    L.launch(entry, C.c_int(h), C.c_int(w), *before, L.ptr(t), *after, C.c_float(near), C.c_float(far),
+             C.c_float(float(image_id or 0)), C.c_int(cols), L.ptr(rays), L.stream_handle())
+    return rays
+
+
 def generate_rays(h: int, w: int, focal: float, c2w: torch.Tensor, near: float, far: float, ndc: bool = False,
                   ndc_near: float = 1.0, image_id: Optional[int] = None) -> torch.Tensor:
     """(h*w, 8|9) ray rows [o, d, near, far(, image id)] of one image, generated on the GPU
     (reference: datasets/ray_utils.py get_ray_directions / get_rays / get_ndc_rays, datasets/llff.py:244-264)."""
-    L.require_gpu(c2w)
-    L.load()
-    if tuple(c2w.shape) != (3, 4):
-        raise L.HnError("c2w must be (3, 4)")
-    c = c2w.detach().contiguous().float()
-    cols = 9 if image_id is not None else 8
-    rays = torch.empty(h * w, cols, dtype=torch.float32, device=c2w.device)
-    L.launch("hn_generate_rays", C.c_int(h), C.c_int(w), C.c_float(focal), L.ptr(c), C.c_int(int(ndc)),
-             C.c_float(ndc_near), C.c_float(near), C.c_float(far), C.c_float(float(image_id or 0)), C.c_int(cols),
-             L.ptr(rays), L.stream_handle())
-    return rays
+    return _generate_rays("hn_generate_rays", h, w, "c2w", c2w, (3, 4), (C.c_float(focal),),
+                          (C.c_int(int(ndc)), C.c_float(ndc_near)), near, far, image_id)
 
 
-def _ray_batch(entry: str, channels: int, perm, state, batch, h, w, focal, c2w, px8, rays, rgbs, near, far, ndc,
-               ndc_near, image_ids) -> None:
-    L.require_gpu(perm, state, c2w, px8, rays, rgbs, image_ids)
+def _ray_batch(entry: str, channels: int, table_row: tuple, before: tuple, after: tuple, perm, state, batch, h, w, table,
+               px8, rays, rgbs, near, far, image_ids) -> None:
+    """Validate and launch one gather entry: `table` is the per-image pose or camera table, (n_images, *table_row),
+    between the entry's own arguments `before` and `after`; `px8` the (n_images, h, w, channels) uint8 stack."""
+    L.require_gpu(perm, state, table, px8, rays, rgbs, image_ids)
     L.load()
     cols = rays.shape[1]
     n_img = px8.shape[0]
     ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
-          and c2w.dtype == torch.float32 and c2w.is_contiguous() and tuple(c2w.shape) == (n_img, 3, 4)
+          and table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (n_img,) + table_row
           and px8.dtype == torch.uint8 and px8.is_contiguous() and tuple(px8.shape[1:]) == (h, w, channels)
           and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
           and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
@@ -1141,9 +1150,9 @@ def _ray_batch(entry: str, channels: int, perm, state, batch, h, w, focal, c2w, 
     if not ok:
         raise L.HnError(f"{entry[3:]}: bad shapes / dtypes")
     L.launch(entry, L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
-             C.c_longlong(px8.numel() // channels), C.c_int(h), C.c_int(w), C.c_float(focal), L.ptr(c2w),
-             L.ptr(image_ids if cols == 9 else None), C.c_int(int(ndc)), C.c_float(ndc_near), C.c_float(near),
-             C.c_float(far), C.c_int(cols), L.ptr(px8), L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+             C.c_longlong(px8.numel() // channels), C.c_int(h), C.c_int(w), *before, L.ptr(table),
+             L.ptr(image_ids if cols == 9 else None), *after, C.c_float(near), C.c_float(far), C.c_int(cols),
+             L.ptr(px8), L.ptr(rays), L.ptr(rgbs), L.stream_handle())
 
 
 def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float, c2w: torch.Tensor,
@@ -1155,8 +1164,8 @@ def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: in
     `state` (3 int64 words: cursor, arrival counter, error flag) is advanced by `batch` on the device: no host sync.
     A row whose position lies past the permutation, or whose index lies outside the dataset, is written as NaN and sets
     the error flag."""
-    _ray_batch("hn_ray_batch", 3, perm, state, batch, h, w, focal, c2w, rgb8, rays, rgbs, near, far, ndc, ndc_near,
-               image_ids)
+    _ray_batch("hn_ray_batch", 3, (3, 4), (C.c_float(focal),), (C.c_int(int(ndc)), C.c_float(ndc_near)), perm, state,
+               batch, h, w, c2w, rgb8, rays, rgbs, near, far, image_ids)
 
 
 def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float,
@@ -1165,8 +1174,8 @@ def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, 
                    image_ids: Optional[torch.Tensor] = None) -> None:
     """`ray_batch` over an RGBA stack ((n_images, h, w, 4) uint8, hn_ray_batch_rgba): rgbs[:batch] is each pixel
     blended onto white as `blend_white_u8` computes it, in the same launch."""
-    _ray_batch("hn_ray_batch_rgba", 4, perm, state, batch, h, w, focal, c2w, rgba8, rays, rgbs, near, far, ndc,
-               ndc_near, image_ids)
+    _ray_batch("hn_ray_batch_rgba", 4, (3, 4), (C.c_float(focal),), (C.c_int(int(ndc)), C.c_float(ndc_near)), perm,
+               state, batch, h, w, c2w, rgba8, rays, rgbs, near, far, image_ids)
 
 
 NERFIES_CAM_FLOATS = 24      # hn_kernels.h: orientation 9, position 3, f, aspect, skew, cx, cy, k1 k2 k3, p1 p2, 2 zeros
@@ -1178,16 +1187,8 @@ def generate_rays_nerfies(h: int, w: int, cam: torch.Tensor, near: float, far: f
     (hn_generate_rays_nerfies) from its camera record `cam` ((24,) fp32, datasets.nerfies.camera_record): pixel
     centres at (i + 0.5, j + 0.5), principal point, skew, pixel aspect ratio, and 10 Newton steps that undo the radial
     and tangential distortion."""
-    L.require_gpu(cam)
-    L.load()
-    if tuple(cam.shape) != (NERFIES_CAM_FLOATS,):
-        raise L.HnError(f"cam must be ({NERFIES_CAM_FLOATS},)")
-    c = cam.detach().contiguous().float()
-    cols = 9 if image_id is not None else 8
-    rays = torch.empty(h * w, cols, dtype=torch.float32, device=cam.device)
-    L.launch("hn_generate_rays_nerfies", C.c_int(h), C.c_int(w), L.ptr(c), C.c_float(near), C.c_float(far),
-             C.c_float(float(image_id or 0)), C.c_int(cols), L.ptr(rays), L.stream_handle())
-    return rays
+    return _generate_rays("hn_generate_rays_nerfies", h, w, "cam", cam, (NERFIES_CAM_FLOATS,), (), (), near, far,
+                          image_id)
 
 
 def ray_batch_nerfies(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, cams: torch.Tensor,
@@ -1196,23 +1197,8 @@ def ray_batch_nerfies(perm: torch.Tensor, state: torch.Tensor, batch: int, h: in
     """`ray_batch` over a Nerfies-format capture (hn_ray_batch_nerfies): `cams` is the (n_images, 24) fp32 table of
     camera records and rays[:batch] holds the rows `generate_rays_nerfies` writes for those pixels, bit for bit (one
     device function); perm, state, rgb8, rgbs, image_ids and the NaN rows are `ray_batch`'s."""
-    L.require_gpu(perm, state, cams, rgb8, rays, rgbs, image_ids)
-    L.load()
-    cols = rays.shape[1]
-    n_img = rgb8.shape[0]
-    ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
-          and cams.dtype == torch.float32 and cams.is_contiguous() and tuple(cams.shape) == (n_img, NERFIES_CAM_FLOATS)
-          and rgb8.dtype == torch.uint8 and rgb8.is_contiguous() and tuple(rgb8.shape[1:]) == (h, w, 3)
-          and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
-          and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
-          and rgbs.shape[0] >= batch and 0 < batch and perm.numel() > 0
-          and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
-    if not ok:
-        raise L.HnError("ray_batch_nerfies: bad shapes / dtypes")
-    L.launch("hn_ray_batch_nerfies", L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
-             C.c_longlong(rgb8.numel() // 3), C.c_int(h), C.c_int(w), L.ptr(cams),
-             L.ptr(image_ids if cols == 9 else None), C.c_float(near), C.c_float(far), C.c_int(cols), L.ptr(rgb8),
-             L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+    _ray_batch("hn_ray_batch_nerfies", 3, (NERFIES_CAM_FLOATS,), (), (), perm, state, batch, h, w, cams, rgb8, rays,
+               rgbs, near, far, image_ids)
 
 
 def blend_white_u8(rgba8: torch.Tensor, with_mask: bool = False):
