@@ -8,6 +8,7 @@
                                         radial_distortion [k1, k2, k3], tangential_distortion [p1, p2]
     root_dir/rgb/<image_scale>x/<id>.png
     root_dir/camera-paths/<name>/*.json cameras only, for novel-view rendering (optional)
+    root_dir/points.npy                 (M, 3) static background points of the structure-from-motion run (optional)
 
 Everything is read on the host with the standard library and NumPy (float64).  A camera is loaded as the Nerfies code
 base loads it: scaled by 1 / image_scale (focal length and principal point multiplied, image size rounded; skew, aspect
@@ -20,6 +21,9 @@ of metadata.json; there is no NDC and no white background.  The model is built w
 `NerfModel(near=ds.near, far=ds.far, ...)` and its GLO tables are sized from `ds.num_embeddings`.
 
 Images are not resized on load (Nerfies ships pre-scaled folders): a missing rgb/<image_scale>x is a ValueError.
+
+`background_points` (points.npy in the scene frame, on the device) and `warp_ids` feed `losses.BackgroundLoss`,
+HyperNeRF's background regularization.
 """
 from __future__ import annotations
 
@@ -88,6 +92,21 @@ def camera_record(cam: Dict) -> np.ndarray:
     rec[17:20] = cam['radial_distortion']
     rec[20:22] = cam['tangential_distortion']
     return rec.astype(np.float32)
+
+
+def load_points(path: str, scene_center=(0.0, 0.0, 0.0), scene_scale: float = 1.0) -> np.ndarray:
+    """points.npy -> the (M, 3) background points in the scene frame, (points - center) * scale in float64 as a camera
+    position is moved, then fp32."""
+    try:
+        pts = np.load(path, allow_pickle=False)
+    except FileNotFoundError:
+        raise ValueError(f"{path} is missing") from None
+    except (OSError, ValueError) as e:
+        raise ValueError(f"{path} is not a readable .npy array: {e}") from None
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] == 0 or not np.issubdtype(pts.dtype, np.number):
+        raise ValueError(f"{path}: expected (M, 3) numbers with M >= 1, got {pts.shape} {pts.dtype}")
+    pts = (pts.astype(np.float64) - np.asarray(scene_center, dtype=np.float64).reshape(3)) * float(scene_scale)
+    return pts.astype(np.float32)
 
 
 class NerfiesDataset(GpuRayDataset):
@@ -190,6 +209,26 @@ class NerfiesDataset(GpuRayDataset):
         self.camera_table = np.stack([camera_record(c) for c in self.cameras])
         if self.split == 'train':
             self._load_train_images()
+
+    # ---- background regularization -------------------------------------------------------------------
+    @property
+    def background_points(self) -> torch.Tensor:
+        """(M, 3) fp32 on the dataset's device: root_dir/points.npy in the scene frame (`load_points`), read on first
+        use."""
+        pts = getattr(self, '_background_points', None)
+        if pts is None:
+            host = load_points(os.path.join(self.root_dir, 'points.npy'), self.scene_center, self.scene_scale)
+            pts = self._background_points = torch.from_numpy(host).to(self.device).contiguous()
+        return pts
+
+    @property
+    def warp_ids(self) -> List[int]:
+        """The sorted distinct warp_id values of dataset.json's train_ids."""
+        missing = [i for i in self.train_ids if i not in self.metadata or 'warp_id' not in self.metadata[i]]
+        if missing:
+            raise ValueError(f"{os.path.join(self.root_dir, 'metadata.json')} has no 'warp_id' for id '{missing[0]}' "
+                             "of train_ids")
+        return sorted({int(self.metadata[i]['warp_id']) for i in self.train_ids})
 
     # ---- images ----------------------------------------------------------------------------------
     def _decode(self, path: str) -> torch.Tensor:

@@ -918,6 +918,88 @@ def mse_loss(coarse: torch.Tensor, fine: Optional[torch.Tensor], target: torch.T
 
 
 # --------------------------------------------------------------------------------------------
+# background regularization (csrc/hn_regularizers.hip)
+# --------------------------------------------------------------------------------------------
+BG_MAX_ROWS = 1 << 24         # hn_bg_sample: a 24-bit uniform reaches no further into a table
+
+
+def bg_sample(points: torch.Tensor, ids: torch.Tensor, u: torch.Tensor, nrm: torch.Tensor, noise_std: float):
+    """One launch (hn_bg_sample): points (M, 3) fp32 and ids (K,) int64 tables, u (N, 2) uniforms in [0, 1) and nrm (N, 3)
+    normals (as `random_draws` gives them) -> (out_points (N, 3) fp32, out_ids (N,) int64) with
+    out_points[n] = points[min(int(u[n, 0] * M), M - 1)] + noise_std * nrm[n] and out_ids[n] = ids[min(int(u[n, 1] * K),
+    K - 1)]: a draw with replacement.  Every operation is rounded on its own, so float32 NumPy gives the same bits.
+    No gradient flows through either output."""
+    if points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+        raise ValueError(f"bg_sample: points must be (M, 3) fp32, got {tuple(points.shape)} {points.dtype}")
+    if ids.dim() != 1 or ids.dtype != torch.int64:
+        raise ValueError(f"bg_sample: ids must be (K,) int64, got {tuple(ids.shape)} {ids.dtype}")
+    m, k = points.shape[0], ids.shape[0]
+    if not 0 < m <= BG_MAX_ROWS or not 0 < k <= BG_MAX_ROWS:
+        raise ValueError(f"bg_sample: tables of 1 .. 2^24 rows (a 24-bit uniform reaches no further), got M = {m}, K = {k}")
+    if u.dim() != 2 or u.shape[1] != 2 or nrm.dim() != 2 or nrm.shape[1] != 3 or u.shape[0] != nrm.shape[0] \
+            or u.shape[0] == 0 or u.dtype != torch.float32 or nrm.dtype != torch.float32:
+        raise ValueError(f"bg_sample: u (N, 2) and nrm (N, 3) fp32, got {tuple(u.shape)} and {tuple(nrm.shape)}")
+    if noise_std < 0:
+        raise ValueError(f"bg_sample: noise_std must not be negative, got {noise_std}")
+    L.require_gpu(points, ids, u, nrm)
+    L.load()
+    n = u.shape[0]
+    p, i, u, nrm = points.detach().contiguous(), ids.contiguous(), u.detach().contiguous(), nrm.detach().contiguous()
+    out_points = torch.empty((n, 3), dtype=torch.float32, device=p.device)
+    out_ids = torch.empty(n, dtype=torch.int64, device=p.device)
+    L.launch("hn_bg_sample", L.ptr(p), C.c_int(m), L.ptr(i), C.c_int(k), L.ptr(u), L.ptr(nrm), C.c_int(n),
+             C.c_float(noise_std), L.ptr(out_points), L.ptr(out_ids), L.stream_handle())
+    return out_points, out_ids
+
+
+class _BgLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, warped, points, scale):
+        L.require_gpu(warped, points)
+        L.load()
+        w = warped.detach().contiguous()
+        p = points.detach().contiguous()
+        n = w.shape[0]
+        loss = torch.empty((), dtype=torch.float32, device=w.device)
+        ctx.unit = None
+        if ctx.needs_input_grad[0]:
+            # as _MseFn: the gradient for a root gradient of exactly 1 comes out of the forward launch
+            dw = torch.empty_like(w)
+            L.launch("hn_bg_loss_forward_grad", L.ptr(w), L.ptr(p), C.c_int(n), C.c_float(scale), L.ptr(loss), L.ptr(dw),
+                     L.stream_handle())
+            ctx.unit = dw
+        else:
+            L.launch("hn_bg_loss_forward", L.ptr(w), L.ptr(p), C.c_int(n), C.c_float(scale), L.ptr(loss),
+                     L.stream_handle())
+        ctx.saved = (w, p, n, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        L.load()
+        w, p, n, scale = ctx.saved
+        if ctx.unit is not None and g.data_ptr() in _UNIT_ROOTS:      # the cached device scalar 1.0 of functional.backward
+            return ctx.unit, None, None
+        g = g.contiguous().float()
+        dw = torch.empty_like(w)
+        L.launch("hn_bg_loss_backward", L.ptr(w), L.ptr(p), C.c_int(n), C.c_float(scale), L.ptr(g), L.ptr(dw),
+                 L.stream_handle())
+        return dw, None, None
+
+
+def bg_loss(warped: torch.Tensor, points: torch.Tensor, scale: float) -> torch.Tensor:
+    """mean_n 2 x_n / (x_n + 4), x_n = |warped_n - points_n|^2 / scale^2 (Barron's general loss at alpha = -2,
+    Geman-McClure): warped, points (N, 3) fp32; differentiable in `warped` only."""
+    if warped.dim() != 2 or warped.shape[1] != 3 or warped.shape != points.shape or warped.shape[0] == 0 \
+            or warped.dtype != torch.float32 or points.dtype != torch.float32:
+        raise ValueError(f"bg_loss: warped and points must both be (N, 3) fp32, got {tuple(warped.shape)} and "
+                         f"{tuple(points.shape)}")
+    if not scale > 0:
+        raise ValueError(f"bg_loss: scale must be positive, got {scale}")
+    return _BgLossFn.apply(warped, points, float(scale))
+
+
+# --------------------------------------------------------------------------------------------
 # SSIM (metrics.py:15-20: kornia's ssim loss)
 # --------------------------------------------------------------------------------------------
 SSIM_MAX_WINDOW = 15          # hn_ssim_*: odd windows 3 .. 15

@@ -4,7 +4,11 @@
 functional.mse_loss); the metrics `mse` and `psnr` (logging only, no gradient path in the reference) are torch
 one-liners; `ssim` runs kornia's windowed SSIM in HIP (`hn_ssim_*`, functional.ssim_dssim), differentiable as kornia's;
 `ms_ssim` is the five-level multi-scale SSIM the Nerfies / HyperNeRF tables report (`hn_msssim_*`), a metric only.
+`BackgroundLoss` is HyperNeRF's background regularization, a training term that takes the model instead of rendered
+rays: static points of the capture through the warp field, pulled back to where they were (`hn_bg_*`).
 GPU tensors only, like every op of the package."""
+from typing import Dict, Optional
+
 import torch
 from torch import nn
 
@@ -20,6 +24,73 @@ class MSELoss(nn.Module):
 
 
 loss_dict = {'mse': MSELoss}
+
+
+class BackgroundLoss:
+    """HyperNeRF's background regularization (on by default in its configs): a batch of the capture's static background
+    points (`NerfiesDataset.background_points`) goes through the warp field under randomly chosen warp embeddings and a
+    robust loss pulls warp(p) back to p, so that the photometric loss cannot drag the static background around.  Per call
+
+        i_n, k_n uniform over the M points / the K warp ids     p_n = points[i_n] + noise_std * normal(0, 1)
+        w_n = warp_field(p_n, warp_embed(ids[k_n]))[..., :3]    x_n = |w_n - p_n|^2 / scale^2
+        loss = mean_n 2 x_n / (x_n + 4)                         (Barron's general loss at alpha = -2, Geman-McClure)
+
+    as four launches around the warp field's own: the draws (functional.random_draws), the sampler (hn_bg_sample), the
+    embedding gather, and behind the field the loss head (hn_bg_loss_forward_grad).  Points are drawn WITH replacement
+    (upstream walks a shuffled stream): that is what a draw inside a captured graph gives.  The defaults are upstream's.
+    `TrainStep(..., background_loss=BackgroundLoss(ds.background_points, ds.warp_ids))` adds `weight` times the term to
+    every step."""
+
+    def __init__(self, points: torch.Tensor, warp_ids, batch_size: int = 16384, noise_std: float = 0.001,
+                 scale: float = 0.001, weight: float = 1.0):
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            shape = tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__
+            raise ValueError(f"BackgroundLoss: points must be an (M, 3) tensor, got {shape}")
+        if points.shape[0] == 0:
+            raise ValueError("BackgroundLoss: no background points")
+        if int(batch_size) <= 0:
+            raise ValueError(f"BackgroundLoss: batch_size must be positive, got {batch_size}")
+        if not float(scale) > 0:
+            raise ValueError(f"BackgroundLoss: scale must be positive, got {scale}")
+        if not float(noise_std) >= 0:
+            raise ValueError(f"BackgroundLoss: noise_std must not be negative, got {noise_std}")
+        ids = [int(i) for i in (warp_ids.reshape(-1).tolist() if isinstance(warp_ids, torch.Tensor) else warp_ids)]
+        if not ids:
+            raise ValueError("BackgroundLoss: no warp ids")
+        if len(set(ids)) != len(ids) or min(ids) < 0:
+            raise ValueError("BackgroundLoss: warp_ids must be distinct and non-negative")
+        if points.shape[0] > F.BG_MAX_ROWS or len(ids) > F.BG_MAX_ROWS:
+            raise ValueError(f"BackgroundLoss: at most 2^24 points and warp ids (a 24-bit uniform reaches no further), "
+                             f"got {points.shape[0]} and {len(ids)}")
+        self.points = points.detach().to(torch.float32).contiguous()
+        self.warp_ids = torch.tensor(ids, dtype=torch.int64, device=points.device)
+        self.max_id = max(ids)
+        self.batch_size, self.noise_std, self.scale, self.weight = int(batch_size), float(noise_std), float(scale), float(weight)
+        self.last_sample = None       # (points (N, 3), ids (N,)) of the latest call (graph replays overwrite them in place)
+
+    def __call__(self, model, rng: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """The unweighted loss of one fresh batch.  rng = {'bg_u': (batch_size, 2) uniforms, 'bg_n': (batch_size, 3)
+        normals} replaces the draw launch (parity runs share the draws with the CPU oracle this way)."""
+        if not getattr(model, 'use_warp', False):
+            raise ValueError("BackgroundLoss: the model has no warp field (use_warp=False)")
+        if self.max_id >= model.warp_embed.num_embeddings:
+            raise ValueError(f"BackgroundLoss: warp id {self.max_id} is outside the model's warp embedding table of "
+                             f"{model.warp_embed.num_embeddings} rows")
+        n = self.batch_size
+        if rng is not None:
+            u, nrm = rng['bg_u'], rng['bg_n']
+            if tuple(u.shape) != (n, 2) or tuple(nrm.shape) != (n, 3):
+                raise ValueError(f"BackgroundLoss: rng 'bg_u' ({n}, 2) and 'bg_n' ({n}, 3), got {tuple(u.shape)} and "
+                                 f"{tuple(nrm.shape)}")
+        else:
+            u, nrm = F.random_draws([((n, 2), 'uniform'), ((n, 3), 'normal')], self.points.device)
+        p, ids = F.bg_sample(self.points, self.warp_ids, u, nrm, self.noise_std)
+        self.last_sample = (p, ids)
+        extra = {'nerf_alpha': None, 'warp_alpha': None, 'hyper_alpha': None, 'hyper_sheet_alpha': None}
+        warped = model.warp_field.warp(p, model.warp_embed(ids), extra)
+        if warped.shape[-1] != 3:         # a field that appends further coordinates: the loss is on the spatial ones
+            warped = warped[..., :3]
+        return F.bg_loss(warped, p, self.scale)
 
 
 def mse(image_pred, image_gt, valid_mask=None, reduction='mean'):

@@ -11,7 +11,8 @@ the gradient buffer is SUM-all-reduced in place between the captured forward+bac
 optionally in two buckets, the first in flight while the weight gradients of the second are still being computed
 (dist.GradSync, `overlap_grad_sync=True`) — and the 1/world of the mean is folded into the Adam kernel.
 `step(rays, rgbs)` returns the log the reference's training_step records: {'train/loss', 'train/psnr', 'lr'}
-(device scalars, no host sync).
+(device scalars, no host sync).  `background_loss=losses.BackgroundLoss(...)` adds HyperNeRF's background regularization
+to every step (and 'train/background_loss' to the log); without it the step is launch for launch the one above.
 """
 from __future__ import annotations
 
@@ -38,7 +39,7 @@ class TrainStep:
                  weight_decay: float = 0.0, use_graph: bool = True, group=None, chunk: int = 32 * 1024,
                  decay_step: Optional[Sequence[int]] = None, decay_gamma: float = 0.1, overlap_grad_sync: bool = False,
                  hparams=None, force_dp: bool = False, capture_collective: bool = True, optimizer: str = "adam",
-                 momentum: float = 0.9, batcher=None):
+                 momentum: float = 0.9, batcher=None, background_loss=None):
         # the optimizer of the reference's get_optimizer (utils/__init__.py:23-41): hparams.optimizer (and
         # hparams.momentum for 'sgd') when hparams carries one, the keywords otherwise; lr / eps / weight_decay always
         # from the keywords.  Checked before any device work.
@@ -87,6 +88,9 @@ class TrainStep:
         if hparams is not None and getattr(hparams, "lr_scheduler", None):
             self.scheduler = get_scheduler(hparams, self.optimizer)
         self.loss_fn = MSELoss()
+        # losses.BackgroundLoss or None: a term of its own ahead of the ray chunks (_forward_backward_body)
+        self.background_loss = background_loss
+        self._bg_rng: Optional[Dict[str, torch.Tensor]] = None   # its injected draws, split off `rng` (_split_rng)
         self._graph: Optional[GraphedStep] = None
         self._rays = self._rgbs = None
         self._rng: Optional[Dict[str, torch.Tensor]] = None    # fixed buffers of injected random draws (tests)
@@ -97,6 +101,7 @@ class TrainStep:
         self._batched: Dict[tuple, tuple] = {}
         self._batched_state = None
         self._batched_rng: Dict[int, Dict[str, torch.Tensor]] = {}
+        self._batched_bg_rng: Optional[Dict[str, torch.Tensor]] = None
 
     # ---- the step body (what gets captured) ---------------------------------------------------
     def _forward_backward(self):
@@ -106,6 +111,15 @@ class TrainStep:
     def _forward_backward_body(self):
         b = self._rays.shape[0]
         loss_sum, psnr_in = None, []
+        bg = None
+        if self.background_loss is not None:
+            # a term of its own, handled exactly like a non-last ray chunk: back-propagated at once (its activations are
+            # freed before the first chunk runs) and its held weight-gradient jobs launched now — only the LAST ray
+            # chunk's held jobs overlap the all-reduce
+            loss_bg = self.background_loss(self.model, rng=self._bg_rng)
+            F.backward(loss_bg, self.background_loss.weight)
+            F.flush_held_wgrads()
+            bg = loss_bg.detach()
         # the reference renders `chunk` rays at a time and concatenates the results before the loss
         # (train.py:108-114); mean((rgb-gt)^2) over the batch = sum over chunks of (rays in chunk / B) x chunk mean,
         # so every chunk is back-propagated on its own (its activations are freed before the next chunk runs)
@@ -126,6 +140,8 @@ class TrainStep:
         with torch.no_grad():
             pred = psnr_in[0] if len(psnr_in) == 1 else torch.cat(psnr_in, 0)
             self._log = {'train/loss': loss_sum, 'train/psnr': psnr(pred, self._rgbs)}
+            if bg is not None:
+                self._log['train/background_loss'] = bg          # unweighted
 
     def _whole(self):
         self._forward_backward()
@@ -221,6 +237,7 @@ class TrainStep:
         """rays (B, 8|9), rgbs (B, 3) on the GPU; B must stay the same from call to call when graphs are on.
         `rng` optionally supplies the random draws of NerfModel.forward ('t_rand', 'u', 'noise_coarse', 'noise_fine',
         one row per ray) instead of torch's generator: parity runs against the CPU oracle share the draws this way.
+        With a background loss, `rng` may also carry its draws 'bg_u' (batch_size, 2) and 'bg_n' (batch_size, 3).
         With a batcher, step() takes no rays / rgbs: the next batch of the batcher's epoch is gathered on the device
         (an epoch that ran out starts the next one); `rng` rows then match that batch's size."""
         if self.batcher is not None:
@@ -229,9 +246,12 @@ class TrainStep:
             return self._step_batched(rng)
         if rays is None or rgbs is None:
             raise ValueError("step() needs rays and rgbs (or a TrainStep built with batcher=...)")
-        if self._rays is None or self._rays.shape != rays.shape or (rng is None) != (self._rng is None):
+        rng, bg_rng = self._split_rng(rng)
+        if (self._rays is None or self._rays.shape != rays.shape or (rng is None) != (self._rng is None)
+                or (bg_rng is None) != (self._bg_rng is None)):
             self._rays, self._rgbs = rays.clone(), rgbs.clone()
             self._rng = None if rng is None else {k: v.clone() for k, v in rng.items()}
+            self._bg_rng = None if bg_rng is None else {k: v.clone() for k, v in bg_rng.items()}
             self._graph = None
         else:
             self._rays.copy_(rays)
@@ -239,6 +259,9 @@ class TrainStep:
             if rng is not None:
                 for k, v in rng.items():
                     self._rng[k].copy_(v)
+            if bg_rng is not None:
+                for k, v in bg_rng.items():
+                    self._bg_rng[k].copy_(v)
         # what a captured graph froze besides the shapes: the precision mode and whether the model trains / evaluates
         state = (F.get_precision(), self.model.training)
         if getattr(self, "_graph_state", None) != state:
@@ -271,6 +294,20 @@ class TrainStep:
         log = {k: v.clone() for k, v in self._log.items()}     # graph outputs are overwritten by the next replay
         log['lr'] = self.optimizer.param_groups[0]['lr']
         return log
+
+    _BG_KEYS = ('bg_u', 'bg_n')
+
+    def _split_rng(self, rng):
+        """`rng` of step() -> (the per-ray draws of NerfModel.forward or None, the background loss's draws or None): the
+        second never reaches the model and is never sliced per chunk."""
+        if rng is None or not any(k in rng for k in self._BG_KEYS):
+            return rng, None
+        if self.background_loss is None:
+            raise ValueError("step(rng=...): 'bg_u' / 'bg_n' given to a TrainStep without background_loss")
+        if not all(k in rng for k in self._BG_KEYS):
+            raise ValueError("step(rng=...): 'bg_u' and 'bg_n' come together")
+        rest = {k: v for k, v in rng.items() if k not in self._BG_KEYS}
+        return (rest or None), {k: rng[k] for k in self._BG_KEYS}
 
     def epoch_end(self):
         """Advance the LR schedule by one epoch (Lightning steps the scheduler of configure_optimizers per epoch); with
@@ -305,6 +342,16 @@ class TrainStep:
         b = self.batcher
         rows = b.next_rows()              # host bookkeeping only; the cursor itself lives on the device
         self._rays, self._rgbs = b.views(rows)
+        rng, bg_rng = self._split_rng(rng)
+        if bg_rng is None:
+            self._bg_rng = None
+        else:
+            if self._batched_bg_rng is None:      # one pair of buffers for every batch size (batch_size rows)
+                self._batched_bg_rng = {k: v.clone() for k, v in bg_rng.items()}
+            else:
+                for k, v in bg_rng.items():
+                    self._batched_bg_rng[k].copy_(v)
+            self._bg_rng = self._batched_bg_rng
         if rng is None:
             self._rng = None
         else:
@@ -312,6 +359,7 @@ class TrainStep:
             if bufs is None or set(bufs) != set(rng):
                 bufs = self._batched_rng[rows] = {k: v.clone() for k, v in rng.items()}
                 self._batched.pop((rows, True), None)
+                self._batched.pop((rows, True, True), None)
             else:
                 for k, v in rng.items():
                     bufs[k].copy_(v)
@@ -321,7 +369,7 @@ class TrainStep:
             self._batched_state = state
             self._batched = {}
         self.optimizer.sync_hyper()
-        key = (rows, rng is not None)
+        key = (rows, rng is not None) if bg_rng is None else (rows, rng is not None, True)
         if not self.use_graph:
             b.launch(rows)
             self._forward_backward()

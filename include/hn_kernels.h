@@ -605,6 +605,34 @@ int hn_msssim_forward(const float* pred, const int64_t* pred_strides, const floa
                       int c, int h, int w, const float* taps_host, const int* sizes_host, float c1, float c2,
                       float* levels_out, void* workspace, hnStream_t stream);
 
+/* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
+ * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
+ *
+ * hn_bg_sample draws the batch: with i = min(int(u[n][0] * m), m - 1) and j = min(int(u[n][1] * k), k - 1),
+ *   out_points[n] = points[i] + noise_std * nrm[n]   (fp32; the product u * m in fp32, every multiply and add rounded on
+ *                                                      its own: a float32 restatement is bit-exact)
+ *   out_ids[n]    = ids[j]                           (int64)
+ * points (m, 3) fp32, ids (k,) int64, u (n, 2) uniforms in [0, 1) and nrm (n, 3) normals as hn_random_fill writes them
+ * (the sampler has no generator of its own).  The indices are clamped to their tables whatever u holds.  m and k at
+ * most 2^24 (a 24-bit uniform reaches no further).
+ *
+ * hn_bg_loss_*: warped, points (n, 3) contiguous fp32; x_n = |warped_n - points_n|^2 / scale^2;
+ *   loss = mean_n 2 x_n / (x_n + 4)                  (Barron's general loss at alpha = -2, Geman-McClure)
+ *   d_warped_n = g 16 (warped_n - points_n) / (scale^2 (x_n + 4)^2 n);  `points` carries no gradient.
+ * A zero residual gives loss 0 and gradient 0.  loss_out: ONE device float, written by one workgroup that adds in a fixed
+ * order (no float atomics: bit-reproducible).  hn_bg_loss_forward_grad also writes the d_warped hn_bg_loss_backward
+ * would write for g = 1, bit for bit; hn_bg_loss_backward reads g from g_loss (ONE device float).
+ *
+ * Status: -2 for every refused argument (a NULL pointer, n, m, k <= 0, m or k above 2^24, scale <= 0), checked on the
+ * host before any launch. */
+int hn_bg_sample(const float* points, int m, const int64_t* ids, int k, const float* u, const float* nrm, int n,
+                 float noise_std, float* out_points, int64_t* out_ids, hnStream_t stream);
+int hn_bg_loss_forward(const float* warped, const float* points, int n, float scale, float* loss_out, hnStream_t stream);
+int hn_bg_loss_forward_grad(const float* warped, const float* points, int n, float scale, float* loss_out,
+                            float* d_warped, hnStream_t stream);
+int hn_bg_loss_backward(const float* warped, const float* points, int n, float scale, const float* g_loss,
+                        float* d_warped, hnStream_t stream);
+
 /* torch.optim.Adam (the reference's default optimizer, utils/__init__.py get_optimizer) over ONE flat fp32 buffer
  * (ParamArena): p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps), m,v updated first, L2 weight decay added to the
  * gradient.  `hyper_dev`: 8 floats ON THE DEVICE, [lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0] — read by the
