@@ -174,6 +174,7 @@ EXPORTS = ["hn_version", "hn_abi_sizes", "hn_build_config", "hn_mlp_wgrad_reduce
            "hn_mlp_wgrad_batched", "hn_mlp_wgrad_batched_t", "hn_mlp_wgrad_reduce", "hn_mlp_workspace_bytes",
            "hn_sample_along_rays", "hn_sample_legacy", "hn_posenc", "hn_composite_forward", "hn_composite_backward", "hn_sample_pdf", "hn_sample_pdf_split", "hn_composite_sample_pdf",
            "hn_embed_gather", "hn_embed_backward", "hn_se3_apply_forward", "hn_se3_apply_backward", "hn_se3_warp_forward", "hn_se3_warp_backward", "hn_generate_rays", "hn_ray_batch", "hn_ray_batch_rgba", "hn_generate_rays_nerfies", "hn_ray_batch_nerfies", "hn_blend_white_u8", "hn_premultiply_u8", "hn_resample_u8", "hn_adam_step", "hn_sgd_step", "hn_radam_step",
+           "hn_grad_norm", "hn_grad_scale",
            "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad",
            "hn_ssim_workspace_bytes", "hn_ssim_forward", "hn_ssim_backward", "hn_msssim_workspace_bytes", "hn_msssim_forward",
            "hn_bg_sample", "hn_bg_loss_forward", "hn_bg_loss_forward_grad", "hn_bg_loss_backward",
@@ -191,6 +192,8 @@ ARGTYPES = {
     "hn_bg_loss_forward": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p],
     "hn_bg_loss_forward_grad": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
     "hn_bg_loss_backward": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_grad_norm": [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_grad_scale": [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_void_p, C.c_void_p],
 }
 
 _lib = None

@@ -282,3 +282,153 @@ extern "C" int hn_radam_step(float* params, float* grads, float* exp_avg, float*
   HN_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Gradient clipping over the flat gradient buffer, ahead of any *_step launch: torch.nn.utils.clip_grad_value_ and then
+// clip_grad_norm_ (norm_type 2, error_if_nonfinite False) of the gradient that counts, s*g (s = grad_scale, which the
+// step kernels apply themselves later).  clamp(s*g, +-v) = s*clamp(g, +-v/s), so both kernels work on the raw buffer with
+// the threshold v' = fp32(v/s):  total_norm = s*sqrt(sum clamp(g, +-v')^2),  coef = min(max_norm / (total_norm + 1e-6), 1)
+// (a NaN stays NaN, as torch.clamp(max=1.0) leaves it),  g <- clamp(g, +-v') * coef.
+// Two launches on the step kernels' grid.  hn_grad_norm: per-thread fp32 sums of squares, a wave64 butterfly, the four
+// wave sums added in order, ONE partial per block; the block that arrives LAST adds the partials in index order in fp64
+// and publishes [total_norm, coef].  No float atomics: the same input gives the same bits on every run and replay.
+// hn_grad_scale: every block reads coef and returns at once when nothing can change (coef == 1, no value clip).
+// ------------------------------------------------------------------------------------------------
+// written with comparisons: a NaN gradient stays NaN as in torch (fminf / fmaxf would drop it); v = +inf changes nothing
+HN_DEV float hn_clip_value(float g, float v) { return g > v ? v : (g < -v ? -v : g); }
+
+HN_DEV float hn_clip_wave_sum(float v) {      // lane 0 of a 64-lane wave ends up with the sum, in a fixed order
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+#define HN_CLIP_PARTIALS 256      // floats of `work` ahead of the ticket word: the largest grid of hn_step_blocks
+
+__global__ __launch_bounds__(256) void hn_grad_norm_kernel(const float* g, long long n, float vp, float gscale,
+                                                            float max_norm, float* work, float* out) {
+  // ONE LDS array: [0, 256) the partials for the last block, [256, 260) the wave sums, [260] "this block arrived last"
+  __shared__ float sh[HN_CLIP_PARTIALS + 8];
+  float s = 0.0f;
+  const long long stride = (long long)gridDim.x * blockDim.x * 4;
+  // four grid strides per trip, their loads issued together (one load per trip leaves the pass latency bound); the terms
+  // are still added in the order of a one-stride loop
+  for (long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i0 < n; i0 += 4 * stride) {
+    f32x4 gg[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = i0 + u * stride;
+      gg[u] = i + 4 <= n ? *reinterpret_cast<const f32x4*>(g + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = i0 + u * stride;
+      if (i + 4 <= n) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float c = hn_clip_value(gg[u][e], vp);
+          s += c * c;
+        }
+      } else {
+        for (long long j = i; j < n; ++j) {      // the scalar tail: at most three elements, one thread of the grid
+          const float c = hn_clip_value(g[j], vp);
+          s += c * c;
+        }
+      }
+    }
+  }
+  s = hn_clip_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[HN_CLIP_PARTIALS + (threadIdx.x >> 6)] = s;
+  __syncthreads();
+  unsigned* ticket = reinterpret_cast<unsigned*>(work + HN_CLIP_PARTIALS);
+  if (threadIdx.x == 0) {
+    const float part = ((sh[HN_CLIP_PARTIALS] + sh[HN_CLIP_PARTIALS + 1]) + sh[HN_CLIP_PARTIALS + 2]) +
+                       sh[HN_CLIP_PARTIALS + 3];
+    // publish the partial to whichever block arrives last, on any XCD: the store (write-through), drained, an
+    // agent-scope release, drained again, THEN the ticket; the last arriver acquires at agent scope before any block of
+    // it reads a partial
+    __hip_atomic_store(work + blockIdx.x, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    sh[HN_CLIP_PARTIALS + 4] = last ? 1.0f : 0.0f;
+  }
+  __syncthreads();
+  if (sh[HN_CLIP_PARTIALS + 4] == 0.0f) return;      // uniform over the block
+  sh[threadIdx.x] = threadIdx.x < gridDim.x
+                        ? __hip_atomic_load(work + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                        : 0.0f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double acc = 0.0;
+    for (unsigned b = 0; b < gridDim.x; ++b) acc += (double)sh[b];
+    const float total = (float)((double)gscale * sqrt(acc));
+    const float coef = (float)((double)max_norm / ((double)total + 1e-6));
+    out[0] = total;
+    out[1] = coef > 1.0f ? 1.0f : coef;      // NaN > 1 is false: a NaN stays NaN
+    // every block has drawn its ticket: re-arm it for the next launch or replay
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+__global__ __launch_bounds__(256) void hn_grad_scale_kernel(float* g, long long n, float vp, int value_clip,
+                                                             const float* out) {
+  const float coef = out != nullptr ? out[1] : 1.0f;
+  if (coef == 1.0f && !value_clip) return;      // the common case; bit-identical to multiplying by 1
+  const long long stride = (long long)gridDim.x * blockDim.x * 4;
+  for (long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i0 < n; i0 += 4 * stride) {
+    f32x4 gg[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {      // as hn_grad_norm_kernel: the loads of four grid strides in flight together
+      const long long i = i0 + u * stride;
+      if (i + 4 <= n) gg[u] = *reinterpret_cast<f32x4*>(g + i);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long i = i0 + u * stride;
+      if (i + 4 <= n) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gg[u][e] = hn_clip_value(gg[u][e], vp) * coef;
+        *reinterpret_cast<f32x4*>(g + i) = gg[u];
+      } else {
+        for (long long j = i; j < n; ++j) g[j] = hn_clip_value(g[j], vp) * coef;
+      }
+    }
+  }
+}
+
+// refused before any launch: -2 n <= 0, or a grad_scale / clip_value / max_norm that is not positive (NaN included)
+static int hn_clip_check(long long n, float grad_scale, float clip_value, float max_norm) {
+  return (n <= 0 || !(grad_scale > 0.0f) || !(clip_value > 0.0f) || !(max_norm > 0.0f)) ? -2 : 0;
+}
+// v' = fp32(v / s), the division in double (+inf stays +inf: no value clip)
+static float hn_clip_threshold(float clip_value, float grad_scale) {
+  return (float)((double)clip_value / (double)grad_scale);
+}
+
+extern "C" int hn_grad_norm(const float* grad, long long n, float grad_scale, float clip_value, float max_norm,
+                            float* work, float* out, hnStream_t stream) {
+  if (hn_clip_check(n, grad_scale, clip_value, max_norm) != 0) return -2;
+  if (grad == nullptr || work == nullptr || out == nullptr) return -3;
+  if ((((uintptr_t)grad | (uintptr_t)work) & 15) != 0 || ((uintptr_t)out & 3) != 0) return -4;
+  hipLaunchKernelGGL(hn_grad_norm_kernel, dim3(hn_step_blocks(n)), dim3(256), 0, (hipStream_t)stream, grad, n,
+                     hn_clip_threshold(clip_value, grad_scale), grad_scale, max_norm, work, out);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int hn_grad_scale(float* grad, long long n, float grad_scale, float clip_value, const float* out,
+                             hnStream_t stream) {
+  if (hn_clip_check(n, grad_scale, clip_value, 1.0f) != 0) return -2;
+  if (grad == nullptr) return -3;
+  if (((uintptr_t)grad & 15) != 0 || ((uintptr_t)out & 3) != 0) return -4;
+  hipLaunchKernelGGL(hn_grad_scale_kernel, dim3(hn_step_blocks(n)), dim3(256), 0, (hipStream_t)stream, grad, n,
+                     hn_clip_threshold(clip_value, grad_scale), (int)!(clip_value == INFINITY), out);
+  HN_CHECK_LAUNCH();
+  return 0;
+}

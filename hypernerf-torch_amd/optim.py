@@ -487,6 +487,69 @@ class ArenaRanger(ArenaRAdam):
         return int(self.param_groups[0]["k"])
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# gradient clipping on the arena (hn_grad_norm / hn_grad_scale, csrc/hn_optim.hip): what Lightning's Trainer does with
+# gradient_clip_val / gradient_clip_algorithm and the Nerfies / HyperNeRF trainers do by hand (value, then global norm),
+# as two launches over `arena.grad` between backward and the optimizer's launch.
+# ------------------------------------------------------------------------------------------------------------------
+def check_clip_args(max_norm, clip_value, who: str = "GradClip"):
+    """The host-side refusals of GradClip (and of TrainStep's clip_grad_norm / clip_grad_value), before any device work:
+    returns (max_norm, clip_value) as floats or None."""
+    if max_norm is None and clip_value is None:
+        raise ValueError(f"{who}: give max_norm, clip_value or both")
+    out = []
+    for name, v in (("max_norm", max_norm), ("clip_value", clip_value)):
+        if v is not None:
+            v = float(v)
+            if not v > 0.0:                 # NaN included
+                raise ValueError(f"{who}: {name} must be positive, got {v}")
+        out.append(v)
+    return tuple(out)
+
+
+class GradClip:
+    """torch.nn.utils.clip_grad_value_(clip_value) and then torch.nn.utils.clip_grad_norm_(max_norm) (2-norm,
+    error_if_nonfinite=False) over a ParamArena's gradient buffer, of the gradient that counts: grad_scale * arena.grad
+    (grad_scale = 1 / world when the buffer arrives SUM-all-reduced; the optimizer's launch applies it afterwards).
+    `max_norm=float('inf')` measures only.  `apply()` goes between backward and `optimizer.step()`: at most two launches,
+    capturable, never a host sync; `total_norm` (before the norm clip, what clip_grad_norm_ returns) and `coef` (the
+    factor applied, at most 1) are 0-dim device views the launches overwrite.  The thresholds are launch arguments,
+    frozen into a captured graph: fixed at construction."""
+
+    _WORK_FLOATS = 256 + 4          # one partial per block of the largest grid, the ticket word, padding to 16 bytes
+
+    def __init__(self, arena: ParamArena, max_norm=None, clip_value=None, grad_scale: float = 1.0):
+        self._max_norm, self._clip_value = check_clip_args(max_norm, clip_value)
+        self._grad_scale = float(grad_scale)
+        if not self._grad_scale > 0.0:
+            raise ValueError(f"GradClip: grad_scale must be positive, got {grad_scale}")
+        L.require_gpu(arena.data)
+        self.arena = arena
+        dev = arena.data.device
+        self._work = torch.zeros(self._WORK_FLOATS, dtype=torch.float32, device=dev)    # zeroed once: the ticket re-arms itself
+        self._out = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._out[1] = 1.0
+        self.total_norm, self.coef = self._out[0], self._out[1]
+
+    max_norm = property(lambda self: self._max_norm)
+    clip_value = property(lambda self: self._clip_value)
+    grad_scale = property(lambda self: self._grad_scale)
+
+    @torch.no_grad()
+    def apply(self):
+        L.load()
+        from . import machine
+        machine.flush_pending_reduce(self.arena.grad)       # a held-back reduce launch: the buffer must be complete
+        a, inf = self.arena, float("inf")
+        value = C.c_float(inf if self._clip_value is None else self._clip_value)
+        if self._max_norm is not None:
+            L.launch("hn_grad_norm", L.ptr(a.grad), C.c_longlong(a.numel), C.c_float(self._grad_scale), value,
+                     C.c_float(self._max_norm), L.ptr(self._work), L.ptr(self._out), L.stream_handle())
+        if (self._clip_value is not None and self._clip_value != inf) or (self._max_norm is not None and self._max_norm != inf):
+            L.launch("hn_grad_scale", L.ptr(a.grad), C.c_longlong(a.numel), C.c_float(self._grad_scale), value,
+                     L.ptr(self._out if self._max_norm is not None else None), L.stream_handle())
+
+
 OPTIMIZERS = ("sgd", "adam", "radam", "ranger")
 
 

@@ -13,6 +13,9 @@ optionally in two buckets, the first in flight while the weight gradients of the
 `step(rays, rgbs)` returns the log the reference's training_step records: {'train/loss', 'train/psnr', 'lr'}
 (device scalars, no host sync).  `background_loss=losses.BackgroundLoss(...)` adds HyperNeRF's background regularization
 to every step (and 'train/background_loss' to the log); without it the step is launch for launch the one above.
+`clip_grad_norm=` / `clip_grad_value=` clip the gradient buffer in two HIP launches right before every optimizer launch
+(optim.GradClip: by value, then by global norm; Lightning's gradient_clip_val / gradient_clip_algorithm) and
+`clip_grad_norm` adds 'train/grad_norm' (the norm before clipping) to the log; without them nothing is allocated or launched.
 """
 from __future__ import annotations
 
@@ -29,7 +32,7 @@ from .dist import GradSync, collective_capturable
 from .graphs import GraphedStep
 from .hypernerf import model_utils
 from .losses import MSELoss, psnr
-from .optim import OPTIMIZERS, ArenaAdam, MultiStepLR, get_scheduler, make_optimizer
+from .optim import OPTIMIZERS, ArenaAdam, GradClip, MultiStepLR, check_clip_args, get_scheduler, make_optimizer
 
 _EXTRA = {'nerf_alpha': None, 'warp_alpha': None, 'hyper_alpha': None, 'hyper_sheet_alpha': None}
 
@@ -39,7 +42,8 @@ class TrainStep:
                  weight_decay: float = 0.0, use_graph: bool = True, group=None, chunk: int = 32 * 1024,
                  decay_step: Optional[Sequence[int]] = None, decay_gamma: float = 0.1, overlap_grad_sync: bool = False,
                  hparams=None, force_dp: bool = False, capture_collective: bool = True, optimizer: str = "adam",
-                 momentum: float = 0.9, batcher=None, background_loss=None):
+                 momentum: float = 0.9, batcher=None, background_loss=None, clip_grad_norm: Optional[float] = None,
+                 clip_grad_value: Optional[float] = None):
         # the optimizer of the reference's get_optimizer (utils/__init__.py:23-41): hparams.optimizer (and
         # hparams.momentum for 'sgd') when hparams carries one, the keywords otherwise; lr / eps / weight_decay always
         # from the keywords.  Checked before any device work.
@@ -48,6 +52,9 @@ class TrainStep:
             momentum = getattr(hparams, "momentum", momentum)
         if optimizer not in OPTIMIZERS:
             raise ValueError('optimizer not recognized!')
+        clipping = clip_grad_norm is not None or clip_grad_value is not None
+        if clipping:
+            check_clip_args(clip_grad_norm, clip_grad_value, "TrainStep(clip_grad_norm=, clip_grad_value=)")
         self.model = model
         self.arena = ParamArena(model.parameters())
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -75,12 +82,18 @@ class TrainStep:
         from . import optim as _optim
         if optimizer == "adam":
             self.optimizer = ArenaAdam(self.arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, zero_grad=True,
-                                       grad_scale=1.0 / self.world, fuse_reduce=(not self.dp) and _optim.FUSE_REDUCE)
+                                       grad_scale=1.0 / self.world,
+                                       fuse_reduce=(not self.dp) and _optim.FUSE_REDUCE and not clipping)
         else:
             # SGD / RAdam / Ranger: one launch of their own after the gradient is complete (no fused reduce); betas at
             # the class defaults, as get_optimizer passes none
             self.optimizer = make_optimizer(optimizer, self.arena, lr=lr, eps=eps, weight_decay=weight_decay,
                                             momentum=momentum, zero_grad=True, grad_scale=1.0 / self.world)
+        # optim.GradClip or None: value clip, then global-norm clip of the (all-reduced) gradient buffer, right before
+        # every optimizer launch (_optimizer_step).  The fused reduce + Adam launch never materialises the gradient, so
+        # a clipped step always takes the two-launch form (fuse_reduce above)
+        self.clip = (GradClip(self.arena, max_norm=clip_grad_norm, clip_value=clip_grad_value,
+                              grad_scale=1.0 / self.world) if clipping else None)
         # 'steplr' of the reference (utils/__init__.py:43-46): stepped once per epoch by the caller (`epoch_end`)
         self.scheduler = MultiStepLR(self.optimizer, decay_step, decay_gamma) if decay_step else None
         # any scheduler of the reference's get_scheduler (utils/__init__.py:43-59): `hparams` carries lr_scheduler
@@ -143,9 +156,21 @@ class TrainStep:
             if bg is not None:
                 self._log['train/background_loss'] = bg          # unweighted
 
+    def _optimizer_step(self):
+        if self.clip is not None:
+            self.clip.apply()
+        self.optimizer.step()
+
+    def _with_grad_norm(self, log):
+        """'train/grad_norm': the norm before clipping, what clip_grad_norm_ returns (a device scalar the clip's launch
+        overwrites every step: cloned with the rest of the log)."""
+        if self.clip is not None and self.clip.max_norm is not None:
+            log['train/grad_norm'] = self.clip.total_norm.clone()
+        return log
+
     def _whole(self):
         self._forward_backward()
-        self.optimizer.step()
+        self._optimizer_step()
 
     def _whole_dp(self):
         """forward + backward | ONE in-place SUM all-reduce of the gradient buffer | Adam, as one capturable program
@@ -155,7 +180,7 @@ class TrainStep:
         self._forward_backward()
         F.flush_held_wgrads()
         self.arena.all_reduce_sum(self.group, force=True)
-        self.optimizer.step()
+        self._optimizer_step()
 
     def _state(self):
         """Parameters, gradient buffer and every tensor of the optimizer's state (step counter, moments, momentum /
@@ -272,7 +297,7 @@ class TrainStep:
             self._forward_backward()
             if self.dp:
                 self.sync.reduce(F.flush_held_wgrads, force=True)
-            self.optimizer.step()
+            self._optimizer_step()
         elif not self.dp:
             if self._graph is None:
                 self._graph = self._capture(self._whole)
@@ -286,12 +311,12 @@ class TrainStep:
                 fwd_bwd, held = self._graph
                 fwd_bwd()
                 self.sync.reduce(held, force=True)   # all-reduce(bucket 0) || held weight gradients, then all-reduce(bucket 1)
-                self.optimizer.step()
+                self._optimizer_step()
         # a replay updates the parameters without running any Python: tell the weight packers (an eval forward
         # after this must repack — see machine.MlpRunner.pack)
         self.arena.bump()
         machine.note_parameters_changed()
-        log = {k: v.clone() for k, v in self._log.items()}     # graph outputs are overwritten by the next replay
+        log = self._with_grad_norm({k: v.clone() for k, v in self._log.items()})     # graph outputs are overwritten by the next replay
         log['lr'] = self.optimizer.param_groups[0]['lr']
         return log
 
@@ -375,7 +400,7 @@ class TrainStep:
             self._forward_backward()
             if self.dp:
                 self.sync.reduce(F.flush_held_wgrads, force=True)
-            self.optimizer.step()
+            self._optimizer_step()
             log = self._log
         elif not self.dp:
             prog = self._batched.get(key)
@@ -398,10 +423,10 @@ class TrainStep:
                 fwd_bwd, held = g
                 fwd_bwd()
                 self.sync.reduce(held, force=True)
-                self.optimizer.step()
+                self._optimizer_step()
             log = prog[1]
         self.arena.bump()
         machine.note_parameters_changed()
-        out = {k: v.clone() for k, v in log.items()}
+        out = self._with_grad_norm({k: v.clone() for k, v in log.items()})
         out['lr'] = self.optimizer.param_groups[0]['lr']
         return out

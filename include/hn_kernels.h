@@ -665,6 +665,30 @@ int hn_sgd_step(float* params_dev, float* grads_dev, float* momentum_buf_dev, lo
 int hn_radam_step(float* params_dev, float* grads_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* slow_dev,
                   long long n, int k, const double* hyper_dev, float* step_dev, int zero_grad, hnStream_t stream);
 
+/* Gradient clipping over ONE flat fp32 gradient buffer (ParamArena.grad), ahead of a *_step launch:
+ * torch.nn.utils.clip_grad_value_ and then torch.nn.utils.clip_grad_norm_ (norm_type 2, error_if_nonfinite False) of the
+ * gradient that counts, s * g with s = grad_scale > 0 (1 / world after a SUM all-reduce; the step launches apply s
+ * themselves later).  clamp(s*g, +-v) = s * clamp(g, +-v/s), so both launches work on the raw buffer with the
+ * threshold v' = fp32(clip_value / grad_scale), the division in double:
+ *   total_norm = s * sqrt(sum clamp(g, +-v')^2)       coef = min(max_norm / (total_norm + 1e-6), 1)  (a NaN stays NaN)
+ *   grad <- clamp(g, +-v') * coef                     (the clamp by comparisons: a NaN gradient stays NaN)
+ * +inf for clip_value or max_norm means "off".
+ *
+ * hn_grad_norm: one launch on the step kernels' grid (at most 256 blocks x 256 threads).  fp32 sums of squares per
+ * thread, wave and block in a fixed order, one partial per block in work[block]; the block that arrives last adds the
+ * partials in index order in fp64 and writes out[0] = total_norm, out[1] = coef.  No float atomics: the same input
+ * gives the same bits on every run and every graph replay.  `work`: 256 floats + 1 ticket word, 16-byte aligned, zeroed
+ * ONCE by its owner (the launch leaves the ticket at zero).  `out`: 2 floats.  `grad` is only read.
+ * hn_grad_scale: the same grid; every thread reads out[1] and the launch returns without touching `grad` when
+ * coef == 1 and clip_value is +inf; otherwise one in-place pass.  out == NULL: value clipping only (coef 1).
+ *
+ * Status, checked before any launch: -2 n <= 0, or grad_scale / clip_value / max_norm not positive (NaN included);
+ * -3 a NULL pointer that must not be; -4 grad or work not 16-byte aligned, out not 4-byte aligned. */
+int hn_grad_norm(const float* grad_dev, long long n, float grad_scale, float clip_value, float max_norm,
+                 float* work_dev, float* out_dev, hnStream_t stream);
+int hn_grad_scale(float* grad_dev, long long n, float grad_scale, float clip_value, const float* out_dev,
+                  hnStream_t stream);
+
 /* All rays of one H x W image on the device: get_ray_directions + get_rays (+ get_ndc_rays when `ndc`)
  * (datasets/ray_utils.py:5-93) and the ray-row layout of datasets/llff.py:244-264:
  * rays[(j*W + i)] = [origin(3), direction(3), near, far(, image_id)], row_floats = 8 or 9.
