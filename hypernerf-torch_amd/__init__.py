@@ -7,6 +7,7 @@ Drop-in module layout (same import paths as the reference, under this package):
     hypernerf_torch_amd.hypernerf.model_utils.*
     hypernerf_torch_amd.models.rendering.render_rays        <- models/rendering.py (nerf_pl signature)
     hypernerf_torch_amd.models.nerf.{Embedding,NeRF}        <- models/nerf.py
+Beside the reference's surface: hypernerf_torch_amd.geometry (density lattice of a frame, isosurface mesh, PLY files).
 
 All device arithmetic runs in hand-written HIP kernels behind the C ABI in include/hn_kernels.h
 (csrc/libhn_hip.so).  There is no CPU execution path: ops raise on CPU tensors or a missing library.
@@ -15,6 +16,8 @@ from . import _lib
 from .arena import ParamArena
 from .optim import ArenaAdam, ArenaRAdam, ArenaRanger, ArenaSGD, GradClip
 from .functional import get_precision, set_precision
+from . import geometry
+from .geometry import density_grid, extract_isosurface, extract_mesh, read_ply, write_ply
 
 __version__ = "0.1.0"
 

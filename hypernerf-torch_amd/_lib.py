@@ -20,7 +20,7 @@ PRODUCT_LIB_PATH = os.path.join(CSRC, "libhn_hip.so")
 # the product library); build() / needs_build() only ever write the product path
 LIB_PATH = os.environ.get("HN_LIB_PATH") or PRODUCT_LIB_PATH
 SOURCES = ["hn_mlp.hip", "hn_render.hip", "hn_data.hip", "hn_calib.hip", "hn_optim.hip", "hn_metrics.hip", "hn_msssim.hip",
-           "hn_regularizers.hip"]
+           "hn_geometry.hip", "hn_regularizers.hip"]
 CSRC_HEADERS = ["hn_common.h", "hn_pack.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hn_kernels.h")
 BUILD_MACROS = ("HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT")     # build-time tuning knobs (A/B experiments)
@@ -177,6 +177,7 @@ EXPORTS = ["hn_version", "hn_abi_sizes", "hn_build_config", "hn_mlp_wgrad_reduce
            "hn_grad_norm", "hn_grad_scale",
            "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad",
            "hn_ssim_workspace_bytes", "hn_ssim_forward", "hn_ssim_backward", "hn_msssim_workspace_bytes", "hn_msssim_forward",
+           "hn_grid_points", "hn_density_activate", "hn_iso_mark", "hn_iso_vertices", "hn_iso_faces",
            "hn_bg_sample", "hn_bg_loss_forward", "hn_bg_loss_forward_grad", "hn_bg_loss_backward",
            "hn_depth_index", "hn_random_fill",
            "hn_probe_mfma", "hn_calib_mfma", "hn_calib_stream", "hn_calib_stream_pattern", "hn_calib_ring"]
@@ -187,6 +188,14 @@ ARGTYPES = {
     "hn_msssim_forward": [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int,
                           C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                           C.c_void_p],
+    "hn_grid_points": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p],
+    "hn_density_activate": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p,
+                            C.c_void_p],
+    "hn_iso_mark": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_iso_vertices": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p,
+                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_iso_faces": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                     C.c_void_p],
     "hn_bg_sample": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
                      C.c_void_p, C.c_void_p],
     "hn_bg_loss_forward": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p],

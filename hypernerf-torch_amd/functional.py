@@ -1188,6 +1188,135 @@ def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) ->
 
 
 # --------------------------------------------------------------------------------------------
+# geometry out of a trained field (csrc/hn_geometry.hip)
+# --------------------------------------------------------------------------------------------
+ISO_BLOCK = 256               # lattice points (cells) per workgroup of the hn_iso_* passes
+INT32_MAX = 2 ** 31 - 1
+
+
+def check_lattice(shape, bounds, what: str):
+    """(nx, ny, nz) and the six bounds of a lattice as the hn_geometry entry points accept them, or ValueError."""
+    try:
+        nx, ny, nz = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the lattice must have three sides, got {shape!r}") from None
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"{what}: every side of the lattice needs at least 2 points, got {(nx, ny, nz)}")
+    if 7 * nx * ny * nz > INT32_MAX:
+        raise ValueError(f"{what}: 7 * {nx} * {ny} * {nz} = {7 * nx * ny * nz} edge slots exceed the int32 limit "
+                         f"2**31 - 1 = {INT32_MAX} of the mesh indices")
+    try:
+        bounds = tuple(float(v) for v in bounds)
+    except (TypeError, ValueError):
+        bounds = ()
+    if len(bounds) != 6:
+        raise ValueError(f"{what}: bounds must be (xmin, xmax, ymin, ymax, zmin, zmax), got {bounds!r}")
+    if not all(hi > lo for lo, hi in zip(bounds[0::2], bounds[1::2])):
+        raise ValueError(f"{what}: bounds need hi > lo on every axis, got {bounds}")
+    return (nx, ny, nz), bounds
+
+
+@torch.no_grad()
+def grid_points(shape, bounds, start: int, count: int, device) -> torch.Tensor:
+    """(count, 3) fp32: lattice points start .. start + count - 1 of the (nx, ny, nz) lattice over `bounds`
+    (hn_grid_points), p = (i*ny + j)*nz + k at lo + (i, j, k) * (hi - lo)/(n - 1); indices past the lattice repeat its last
+    point.  float32 NumPy gives the same bits."""
+    (nx, ny, nz), bounds = check_lattice(shape, bounds, "grid_points")
+    if not 0 <= start < nx * ny * nz or not 0 < count <= INT32_MAX:
+        raise ValueError(f"grid_points: start {start} / count {count} outside the lattice of {nx * ny * nz} points")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.HnError("hypernerf_torch_amd runs on MI355X only: grid_points needs a GPU device")
+    L.load()
+    out = torch.empty((count, 3), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        L.launch("hn_grid_points", nx, ny, nz, (C.c_float * 6)(*bounds), start, count, out.data_ptr(),
+                 torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+@torch.no_grad()
+def density_activate(raw: torch.Tensor, points: torch.Tensor, render_opts=None) -> torch.Tensor:
+    """Raw densities (...,) of points (..., 3) -> Softplus, then filter_sigma (dust threshold, bounding box) exactly as the
+    compositing kernel applies them (hn_density_activate), as fp32 of raw's shape."""
+    L.require_gpu(raw, points)
+    L.load()
+    raw = raw.detach().float().contiguous()
+    has_dust, dust, box = 0, 0.0, None
+    if render_opts is not None:
+        if 'dust_threshold' in render_opts:
+            has_dust, dust = 1, float(render_opts.get('dust_threshold', 0.0))
+        if 'bounding_box' in render_opts:
+            box = (C.c_float * 6)(*(float(v) for v in render_opts['bounding_box']))
+            points = points.detach().float().contiguous()
+            if points.shape != raw.shape + (3,):
+                raise ValueError(f"density_activate: points {tuple(points.shape)} do not match raw {tuple(raw.shape)}")
+    out = torch.empty_like(raw)
+    if raw.numel():
+        L.launch("hn_density_activate", raw.data_ptr(), points.data_ptr() if box is not None else None, raw.numel(),
+                 has_dust, dust, box, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+@torch.no_grad()
+def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torch.Tensor]:
+    """Indexed triangle mesh of the surface grid = iso by marching tetrahedra (hn_iso_*): grid (nx, ny, nz) fp32,
+    C-contiguous, on the GPU, its points spread over bounds (xmin, xmax, ymin, ymax, zmin, zmax) ->
+    {'vertices': (V, 3) fp32, 'normals': (V, 3) fp32 unit (from inside, grid >= iso, to outside), 'faces': (F, 3) int32}.
+    Vertices ascend with their edge slot, faces with cell, tetrahedron, triangle: the same grid gives the same arrays on
+    every run.  An empty surface gives zero-length tensors.  Working memory: 28 bytes of edge slots + 1 of marks per
+    lattice point.  Two host synchronisations (the vertex and the face count size the outputs)."""
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+        raise ValueError("extract_isosurface: grid must be a (nx, ny, nz) tensor")
+    (nx, ny, nz), bounds = check_lattice(grid.shape, bounds, "extract_isosurface")
+    if grid.dtype != torch.float32:
+        raise ValueError(f"extract_isosurface: grid must be float32, got {grid.dtype}")
+    if not grid.is_contiguous():
+        raise ValueError("extract_isosurface: grid must be C-contiguous")
+    if not grid.is_cuda:
+        raise ValueError("extract_isosurface: grid must live on the GPU (there is no CPU fallback)")
+    L.load()
+    f = grid.detach()
+    dev = f.device
+    empty = {'vertices': torch.zeros((0, 3), dtype=torch.float32, device=dev),
+             'normals': torch.zeros((0, 3), dtype=torch.float32, device=dev),
+             'faces': torch.zeros((0, 3), dtype=torch.int32, device=dev)}
+    n = nx * ny * nz
+    iso = float(iso)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        # pass A: marks and per-workgroup counts; the scan of the counts is torch's
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        counts = torch.empty((n + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
+        L.launch("hn_iso_mark", f.data_ptr(), nx, ny, nz, iso, mask.data_ptr(), counts.data_ptr(), stream)
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        n_vertices = int(ends[-1])
+        if n_vertices == 0:
+            return empty
+        # pass B
+        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+        slots = torch.empty(7 * n, dtype=torch.int32, device=dev)
+        offsets = ends - counts
+        L.launch("hn_iso_vertices", f.data_ptr(), nx, ny, nz, (C.c_float * 6)(*bounds), iso, mask.data_ptr(),
+                 offsets.data_ptr(), vertices.data_ptr(), normals.data_ptr(), slots.data_ptr(), stream)
+        # pass C: count, scan, emit
+        n_cells = (nx - 1) * (ny - 1) * (nz - 1)
+        fcounts = torch.empty((n_cells + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
+        L.launch("hn_iso_faces", f.data_ptr(), nx, ny, nz, iso, None, None, fcounts.data_ptr(), None, stream)
+        fends = torch.cumsum(fcounts, 0, dtype=torch.int64)
+        n_faces = int(fends[-1])
+        if n_faces > INT32_MAX:
+            raise ValueError(f"extract_isosurface: {n_faces} faces exceed the int32 limit 2**31 - 1 = {INT32_MAX}")
+        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+        if n_faces:
+            foffsets = fends - fcounts
+            L.launch("hn_iso_faces", f.data_ptr(), nx, ny, nz, iso, slots.data_ptr(), foffsets.data_ptr(), None,
+                     faces.data_ptr(), stream)
+    return {'vertices': vertices, 'normals': normals, 'faces': faces}
+
+
+# --------------------------------------------------------------------------------------------
 # on-device ray generation
 # --------------------------------------------------------------------------------------------
 def _generate_rays(entry: str, h: int, w: int, name: str, table: torch.Tensor, shape: tuple, before: tuple, after: tuple,

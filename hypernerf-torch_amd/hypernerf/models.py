@@ -503,6 +503,17 @@ class NerfModel(nn.Module):
                         & (points[..., 1] <= ymax) & (points[..., 2] >= zmin) & (points[..., 2] <= zmax)).float()
         b, s = points.shape[0], points.shape[1]
         out = {'points': points}
+        warped, rgb, alpha = self._level_fields(level, points, viewdirs, metadata, extra_params, use_warp,
+                                                metadata_encoded, return_warp_jacobian)
+        return self._composite_level(out, warped, rgb, alpha, z_vals, directions, noise, use_sample_at_infinity,
+                                     dust, keep, b, s, points.device, level)
+
+    def _level_fields(self, level, points, viewdirs, metadata, extra_params, use_warp, metadata_encoded,
+                      return_warp_jacobian):
+        """The networks of one level on `points` (B,S,3), everything render_samples computes before it composites:
+        (warped points (B,S,3+H), rgb (B*S,3), raw density (B*S,1)) on whichever path the model takes — the fused level
+        program, a gathered template with the warp outside, or network by network."""
+        b, s = points.shape[0], points.shape[1]
         if self._can_fuse_level(use_warp, metadata_encoded, metadata):
             if return_warp_jacobian:
                 raise NotImplementedError
@@ -514,8 +525,7 @@ class NerfModel(nn.Module):
                                                       self.warp_embed.embed.weight, None], s, self.precision,
                                                gather_idx=idx)
             warped = warped.view(b, s, -1)
-            return self._composite_level(out, warped, rgb, alpha, z_vals, directions, noise, use_sample_at_infinity,
-                                         dust, keep, b, s, points.device, level)
+            return warped, rgb, alpha
         tab = None
         if (self.FUSE_LEVELS and not metadata_encoded and metadata.get('hyper_point') is None
                 and not return_warp_jacobian and not (use_warp and self.hyper_slice_method == 'bendy_sheet')):
@@ -549,8 +559,7 @@ class NerfModel(nn.Module):
             warped = self._warped_of(xyz, warped_rows, from_table, emb_mod, idx, b, s)
             if use_warp:        # what a fine level re-using these samples needs (REUSE_COARSE)
                 self._level_state = {'level': level, 'xyz': xyz, 'rows': warped_rows is not None, 'tab': tab}
-            return self._composite_level(out, warped, rgb, alpha, z_vals, directions, noise, use_sample_at_infinity,
-                                         dust, keep, b, s, points.device, level)
+            return warped, rgb, alpha
         if use_warp:
             warp_embed = metadata['encoded_warp'] if metadata_encoded else self.warp_embed(metadata[self.warp_embed_key])
         else:
@@ -573,8 +582,40 @@ class NerfModel(nn.Module):
         call = self._template_call(level, n_ch, ge, ge and n_ch > 3)
         rgb, alpha = F.run_program(call, [warped.reshape(b * s, n_ch), viewdirs if self.use_viewdirs else None,
                                           nerf_embed], s, self.precision)
-        return self._composite_level(out, warped, rgb, alpha, z_vals, directions, noise, use_sample_at_infinity,
-                                     dust, keep, b, s, points.device, level)
+        return warped, rgb, alpha
+
+    def query_points(self, points, metadata, level='fine', viewdirs=None, use_warp=True, extra_params=None,
+                     render_opts=None):
+        """The field at observation-space points, without compositing (reference: map_points + query_template,
+        models.py:447-581, as render_samples chains them): points (B,S,3), `metadata` as forward() takes it (ids per
+        row, (B,) or (B,1)), viewdirs (B,3) -> {'warped_points': (B,S,3+H), 'rgb': (B,S,3), 'sigma': (B,S)}.
+        sigma is the activated density render_samples integrates: Softplus, then filter_sigma when `render_opts` is
+        given; no noise is added whatever `noise_std` is.  Without `viewdirs` every row looks along +z (sigma does not
+        depend on it).  Runs the programs of whichever path render_samples takes for this model.
+        Inference only: it runs under torch.no_grad(), also when called in grad mode, and returns no graph."""
+        L.require_gpu(points, viewdirs)
+        if points.dim() != 3 or points.shape[-1] != 3:
+            raise ValueError(f"query_points: points must be (B, S, 3), got {tuple(points.shape)}")
+        if level not in ('coarse', 'fine'):
+            raise ValueError(f"query_points: level must be 'coarse' or 'fine', got {level!r}")
+        with torch.no_grad():
+            use_warp = self.use_warp and use_warp
+            points = points.detach().float().contiguous()
+            b, s = points.shape[0], points.shape[1]
+            if b == 0 or s == 0:
+                hyper = self._empty_result(points, use_warp)['coarse']['warped_points'].shape[-1] - 3
+                return {'warped_points': points.new_zeros((b, s, 3 + hyper)), 'rgb': points.new_zeros((b, s, 3)),
+                        'sigma': points.new_zeros((b, s))}
+            if viewdirs is None:
+                viewdirs = points.new_tensor([0.0, 0.0, 1.0]).expand(b, 3).contiguous()
+            state = getattr(self, '_level_state', None)     # (a forward pass in flight keeps its coarse level's state)
+            try:
+                warped, rgb, alpha = self._level_fields(level, points, viewdirs, metadata, extra_params or {}, use_warp,
+                                                        False, False)
+            finally:
+                self._level_state = state
+            sigma = F.density_activate(alpha.view(b, s), points, render_opts)
+            return {'warped_points': warped.reshape(b, s, -1), 'rgb': rgb.view(b, s, 3), 'sigma': sigma}
 
     def _warp_outside(self, points, metadata, idx, emb_mod, from_table, use_warp, extra_params):
         """The warp of a level whose warp field runs as its own program (SE3Field, or a TranslationField next to a

@@ -605,6 +605,51 @@ int hn_msssim_forward(const float* pred, const int64_t* pred_strides, const floa
                       int c, int h, int w, const float* taps_host, const int* sizes_host, float c1, float c2,
                       float* levels_out, void* workspace, hnStream_t stream);
 
+/* Geometry out of a trained field (csrc/hn_geometry.hip; no reference counterpart).
+ *
+ * Lattice: (nx, ny, nz) points, each side >= 2 and 7*nx*ny*nz <= 2^31 - 1, over bounds_host = HOST array
+ * (xmin, xmax, ymin, ymax, zmin, zmax) with hi > lo.  Point index p = (i*ny + j)*nz + k, position
+ * lo + (i, j, k) * step, step = (hi - lo) / (n - 1) in fp32 on the host, product and sum rounded on their own.
+ *
+ * hn_grid_points: out[r] = position of lattice point min(start + r, N - 1) for r < count — `count` points of the
+ * lattice as (count, 3) fp32; indices past the lattice (the padding of a last chunk) repeat its last point.
+ *
+ * hn_density_activate: sigma[r] = softplus(raw[r]) (beta 1, threshold 20: as the compositing kernel takes it), then
+ * filter_sigma: 0 where sigma < dust_threshold (has_dust != 0) or points[r] (n, 3) lies outside box_host = HOST array
+ * (xmin, xmax, ymin, ymax, zmin, zmax), borders inside (box_host may be NULL: no box, points unused).
+ *
+ * Isosurface of the C-contiguous fp32 grid f[nx][ny][nz] at `iso` by marching tetrahedra; inside = f >= iso, NaN is
+ * outside.  Cells are split into the six Kuhn tetrahedra around the main diagonal (q-th permutation pi of the axes in
+ * lexicographic order: v0 = origin, v1 = v0 + e_pi0, v2 = v1 + e_pi1, v3 = v0 + (1,1,1)).  A vertex lies on a
+ * tetrahedron edge and is named by the edge slot e = 7*p + d of the edge's LOWER lattice point p, d = the class of its
+ * direction: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1).  Workgroups are 256 points (or cells) each:
+ * every *_blocks array has ceil(points / 256) (hn_iso_faces: ceil(cells / 256)) entries.
+ *   hn_iso_mark      mask[p] = bit d set when the owned edge d exists and its ends differ in `inside`;
+ *                    block_counts[b] = set bits of workgroup b.
+ *   hn_iso_vertices  block_offsets = the exclusive scan of those counts (int64).  Vertex ids ascend with the edge slot.
+ *                    For a = p, b = its neighbour, t = (iso - fa) / (fb - fa): vertices[id] = pos(a) + t*(pos(b) - pos(a)),
+ *                    normals[id] = -g/|g|, g = ga + t*(gb - ga), ga / gb central differences of f at the two ends
+ *                    (one-sided on the lattice boundary), (0,0,0) when |g| is 0 or NaN; every operation fp32, unfused.
+ *                    slots[7*p + d] = id, or -1 for an edge without a vertex (all 7*N entries are written).
+ *   hn_iso_faces     faces_dev == NULL: block_counts[b] = triangles of the cells of workgroup b (0, 1 or 2 per
+ *                    tetrahedron).  Otherwise block_offsets = their exclusive scan (int64) and faces (F, 3) int32 is
+ *                    written: by cell c = (i*(ny-1) + j)*(nz-1) + k, tetrahedron, triangle; vertex ids read from slots.
+ *                    The winding comes from the inside mask and the sign of an integer determinant of lattice vectors:
+ *                    normals point from inside to outside (towards lower f).
+ * No atomics: the same grid gives the same arrays on every run.  Status: -2 for every refused argument (a NULL pointer
+ * that must not be, a side < 2, 7*N above 2^31 - 1, hi <= lo, start / count outside the lattice), before any launch. */
+int hn_grid_points(int nx, int ny, int nz, const float* bounds_host, long long start, long long count, float* out_dev,
+                   hnStream_t stream);
+int hn_density_activate(const float* raw_dev, const float* points_dev, long long n, int has_dust, float dust_threshold,
+                        const float* box_host, float* sigma_dev, hnStream_t stream);
+int hn_iso_mark(const float* grid_dev, int nx, int ny, int nz, float iso, uint8_t* mask_dev, int32_t* block_counts_dev,
+                hnStream_t stream);
+int hn_iso_vertices(const float* grid_dev, int nx, int ny, int nz, const float* bounds_host, float iso,
+                    const uint8_t* mask_dev, const int64_t* block_offsets_dev, float* vertices_dev, float* normals_dev,
+                    int32_t* slots_dev, hnStream_t stream);
+int hn_iso_faces(const float* grid_dev, int nx, int ny, int nz, float iso, const int32_t* slots_dev,
+                 const int64_t* block_offsets_dev, int32_t* block_counts_dev, int32_t* faces_dev, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *
