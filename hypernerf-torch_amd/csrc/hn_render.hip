@@ -1129,11 +1129,18 @@ extern "C" int hn_mse_loss_backward(const float* coarse, const float* fine, cons
 
 // ------------------------------------------------------------------------------------------------
 // SE(3) exponential-map warp (warping.SE3Field.warp, hypernerf/warping.py:226-238; rigid_body.py:24-83)
-//   theta = |w| ; a = w/theta ; b = v/theta
-//   R = I + sin(theta) [a] + (1 - cos(theta)) [a]^2            (Modern Robotics 3.51)
-//   t = (theta I + (1 - cos(theta)) [a] + (theta - sin(theta)) [a]^2) b      (3.88)
-//   y = R p + t
-// one thread per point; fp32, the same operation order in forward and backward
+//   theta = |w| ; R = I + sin(theta) [w/theta] + (1 - cos(theta)) [w/theta]^2                  (Modern Robotics 3.51)
+//   t = (theta I + (1 - cos(theta)) [w/theta] + (theta - sin(theta)) [w/theta]^2) v/theta      (3.88) ;  y = R p + t
+// written without the division by theta (t2 = theta^2 = w . w):
+//   y = p + A (w x p) + B (w x (w x p)) + v + B (w x v) + C (w x (w x v))
+//   A = sin(theta)/theta, B = (1 - cos(theta))/theta^2, C = (theta - sin(theta))/theta^3 and, for the gradient,
+//   A1 = A'/theta, B1 = B'/theta, C1 = C'/theta: even, entire functions of theta.  Below theta = 1 each is its Taylor
+//   series in t2 (7 terms, Horner); above, the closed forms through sin and cos of theta/2, which subtract no two
+//   nearly equal numbers there.  w/theta, 1 - cosf(theta) and theta - sinf(theta) lose every digit as theta -> 0 (with
+//   them the gradient w.r.t. w is rounding noise wherever |w| << |v|, and NaN at theta = 0); this form is good to a few
+//   fp32 units at every theta, and theta = 0 (also a w . w that underflows) is the pure translation y = p + v with
+//   d w = p x g + (v x g)/2.  tests/se3_restated.py restates it operation by operation.
+// one thread per point; fp32, the same coefficients and the same operation order in forward and backward
 // ------------------------------------------------------------------------------------------------
 struct HnV3 { float x, y, z; };
 HN_DEV HnV3 hn_v3(float x, float y, float z) { HnV3 r = {x, y, z}; return r; }
@@ -1147,6 +1154,37 @@ HN_DEV void hn_store3(float* p, size_t i, HnV3 v) { p[3 * i] = v.x; p[3 * i + 1]
 HN_DEV HnV3 hn_load3s(const float* p, size_t i, int ld) { return hn_v3(p[i * ld], p[i * ld + 1], p[i * ld + 2]); }
 HN_DEV void hn_store3s(float* p, size_t i, int ld, HnV3 v) { p[i * ld] = v.x; p[i * ld + 1] = v.y; p[i * ld + 2] = v.z; }
 
+constexpr double hn_factorial(int n) { return n <= 1 ? 1.0 : n * hn_factorial(n - 1); }
+// coefficient k of the series in (-t2): 1/(2k+j)! for A, B, C (j = 1, 2, 3), -2(k+1)/(2k+2+j)! for A1, B1, C1
+template <int j, bool kDeriv, int k> struct HnSe3Term {
+  static constexpr float v = (float)(kDeriv ? -2.0 * (k + 1) / hn_factorial(2 * k + 2 + j) : 1.0 / hn_factorial(2 * k + j));
+};
+template <int j, bool kDeriv> HN_DEV float hn_se3_series(float t2) {
+  float acc = HnSe3Term<j, kDeriv, 6>::v;
+  acc = HnSe3Term<j, kDeriv, 5>::v - acc * t2;
+  acc = HnSe3Term<j, kDeriv, 4>::v - acc * t2;
+  acc = HnSe3Term<j, kDeriv, 3>::v - acc * t2;
+  acc = HnSe3Term<j, kDeriv, 2>::v - acc * t2;
+  acc = HnSe3Term<j, kDeriv, 1>::v - acc * t2;
+  return HnSe3Term<j, kDeriv, 0>::v - acc * t2;
+}
+struct HnSe3Coef { float A, B, C, A1, B1, C1; };
+template <bool kGrad> HN_DEV HnSe3Coef hn_se3_coef(float t2) {
+  HnSe3Coef k = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (t2 < 1.0f) {
+    k.A = hn_se3_series<1, false>(t2); k.B = hn_se3_series<2, false>(t2); k.C = hn_se3_series<3, false>(t2);
+    if (kGrad) { k.A1 = hn_se3_series<1, true>(t2); k.B1 = hn_se3_series<2, true>(t2); k.C1 = hn_se3_series<3, true>(t2); }
+  } else {                                           // also a NaN or inf t2: they propagate
+    const float th = sqrtf(t2);
+    float sh, ch;
+    sincosf(0.5f * th, &sh, &ch);
+    const float sn = 2.0f * sh * ch, hv = 2.0f * sh * sh;     // sin(theta), 1 - cos(theta)
+    k.A = sn / th; k.B = hv / t2; k.C = (th - sn) / (t2 * th);
+    if (kGrad) { k.A1 = ((1.0f - hv) - k.A) / t2; k.B1 = (k.A - 2.0f * k.B) / t2; k.C1 = (k.B - 3.0f * k.C) / t2; }
+  }
+  return k;
+}
+
 // every operand with its own row stride (w and v are the two halves of the field's (P, 6) head output: no slicing
 // copies); `rows_out` (optional, (P, 3 + H) with stride rows_ld) = [y | table[idx[ray]]]: the `warped_points` tensor of
 // an axis-aligned-plane level (models.py:533-534, 578) written by the same launch — no index_select, no cat
@@ -1156,12 +1194,10 @@ __global__ void hn_se3_forward_kernel(const float* w, int w_ld, const float* v, 
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const HnV3 wv = hn_load3s(w, i, w_ld), vv = hn_load3s(v, i, v_ld), p = hn_load3s(pts, i, p_ld);
-  const float theta = sqrtf(hn_dot(wv, wv));
-  const HnV3 a = hn_scale(1.0f / theta, wv), b = hn_scale(1.0f / theta, vv);
-  const float s = sinf(theta), c = 1.0f - cosf(theta), d = theta - s;
-  const HnV3 q = hn_cross(a, p), r = hn_cross(a, q), m = hn_cross(a, b), nn = hn_cross(a, m);
-  HnV3 y = hn_add(p, hn_add(hn_scale(s, q), hn_scale(c, r)));
-  y = hn_add(y, hn_add(hn_scale(theta, b), hn_add(hn_scale(c, m), hn_scale(d, nn))));
+  const HnSe3Coef co = hn_se3_coef<false>(hn_dot(wv, wv));
+  const HnV3 q = hn_cross(wv, p), r = hn_cross(wv, q), m = hn_cross(wv, vv), nn = hn_cross(wv, m);
+  HnV3 y = hn_add(p, hn_add(hn_scale(co.A, q), hn_scale(co.B, r)));
+  y = hn_add(y, hn_add(vv, hn_add(hn_scale(co.B, m), hn_scale(co.C, nn))));
   if (out != nullptr) hn_store3(out, i, y);
   if (rows_out != nullptr) {
     float* dst = rows_out + (size_t)i * rows_ld;
@@ -1181,25 +1217,20 @@ __global__ void hn_se3_backward_kernel(const float* w, int w_ld, const float* v,
   if (i >= n) return;
   const HnV3 wv = hn_load3s(w, i, w_ld), vv = hn_load3s(v, i, v_ld), p = hn_load3s(pts, i, p_ld);
   const HnV3 g = hn_load3s(gout, i, g_ld);
-  const float theta = sqrtf(hn_dot(wv, wv)), inv = 1.0f / theta;
-  const HnV3 a = hn_scale(inv, wv), b = hn_scale(inv, vv);
-  const float sn = sinf(theta), cs = cosf(theta), c = 1.0f - cs, d = theta - sn;
-  const HnV3 q = hn_cross(a, p), r = hn_cross(a, q), m = hn_cross(a, b), nn = hn_cross(a, m);
-  const HnV3 ga = hn_cross(g, a);                  // g x a
-  const HnV3 gaa = hn_cross(ga, a);                // (g x a) x a
-  // y = p + s q + c r + theta b + c m + d n
-  const HnV3 g_p = hn_add(g, hn_add(hn_scale(sn, ga), hn_scale(c, gaa)));
-  const HnV3 g_b = hn_add(hn_scale(theta, g), hn_add(hn_scale(c, ga), hn_scale(d, gaa)));
-  HnV3 g_a = hn_scale(sn, hn_cross(p, g));
-  g_a = hn_add(g_a, hn_scale(c, hn_add(hn_cross(q, g), hn_cross(p, ga))));
-  g_a = hn_add(g_a, hn_scale(c, hn_cross(b, g)));
-  g_a = hn_add(g_a, hn_scale(d, hn_add(hn_cross(m, g), hn_cross(b, ga))));
-  // ds = cos, dc = sin, dd = 1 - cos = c ; the explicit theta of `theta b`
-  float g_theta = cs * hn_dot(q, g) + sn * hn_dot(r, g) + hn_dot(b, g) + sn * hn_dot(m, g) + c * hn_dot(nn, g);
-  // a = w / theta, b = v / theta
-  g_theta -= inv * (hn_dot(g_a, a) + hn_dot(g_b, b));
-  const HnV3 g_w = hn_add(hn_scale(inv, g_a), hn_scale(g_theta, a));   // d theta / d w = a
-  const HnV3 g_v = hn_scale(inv, g_b);
+  const HnSe3Coef co = hn_se3_coef<true>(hn_dot(wv, wv));
+  const HnV3 q = hn_cross(wv, p), r = hn_cross(wv, q), m = hn_cross(wv, vv), nn = hn_cross(wv, m);
+  const HnV3 ga = hn_cross(g, wv);                 // g x w
+  const HnV3 gaa = hn_cross(ga, wv);               // (g x w) x w
+  // y = p + A q + B r + v + B m + C n
+  const HnV3 g_p = hn_add(g, hn_add(hn_scale(co.A, ga), hn_scale(co.B, gaa)));
+  const HnV3 g_v = hn_add(g, hn_add(hn_scale(co.B, ga), hn_scale(co.C, gaa)));
+  // through q, r, m, n with the coefficients held ...
+  HnV3 g_w = hn_scale(co.A, hn_cross(p, g));
+  g_w = hn_add(g_w, hn_scale(co.B, hn_add(hn_add(hn_cross(q, g), hn_cross(p, ga)), hn_cross(vv, g))));
+  g_w = hn_add(g_w, hn_scale(co.C, hn_add(hn_cross(m, g), hn_cross(vv, ga))));
+  // ... and through the coefficients: d X / d w = X1 w
+  const float sc = co.A1 * hn_dot(q, g) + co.B1 * (hn_dot(r, g) + hn_dot(m, g)) + co.C1 * hn_dot(nn, g);
+  g_w = hn_add(g_w, hn_scale(sc, wv));
   if (dw != nullptr) hn_store3s(dw, i, dw_ld, g_w);
   if (dv != nullptr) hn_store3s(dv, i, dv_ld, g_v);
   if (dp != nullptr) hn_store3(dp, i, g_p);

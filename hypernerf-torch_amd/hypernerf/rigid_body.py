@@ -74,8 +74,8 @@ def _rigid(w: torch.Tensor, v: torch.Tensor, theta: torch.Tensor):
     """(R (N,3,3), t (N,3)) of exp([S] theta) for N screw axes through hn_se3_apply_forward: the kernel takes the
     exponential coordinates (w theta, v theta) and a point.  The origin with the twist's v gives t; the three basis vectors
     with v = 0 give the columns of R directly (no (R e_i + t) - t cancellation when |t| is large).  Rows with w theta = 0
-    (the kernel divides by |w theta|, as SE3Field does: warping.py:226-232) are the pure translation R = I, t = v theta,
-    selected by a device-side mask — no host sync."""
+    are the pure translation R = I, t = v theta, selected by a device-side mask — no host sync (the kernel's own result at
+    theta = 0 is the same translation; the mask makes R the identity bit for bit)."""
     n = w.shape[0]
     th = theta.reshape(n, 1).float()
     wt, vt = (w.float() * th).contiguous(), (v.float() * th).contiguous()

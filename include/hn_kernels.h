@@ -804,7 +804,9 @@ int hn_resample_u8(const uint8_t* in_dev, int rows, int cols, int channels, int 
 
 /* SE(3) exponential-map warp of warping.SE3Field.warp (hypernerf/warping.py:226-238 with rigid_body.exp_se3,
  * rigid_body.py:55-83, applied per point): theta = |w|, a = w/theta, b = v/theta,
- * y = p + sin(theta) a x p + (1-cos(theta)) a x (a x p) + theta b + (1-cos(theta)) a x b + (theta-sin(theta)) a x (a x b).
+ * y = p + sin(theta) a x p + (1-cos(theta)) a x (a x p) + theta b + (1-cos(theta)) a x b + (theta-sin(theta)) a x (a x b),
+ * evaluated without the division by theta (smooth coefficients of w x ., w x (w x .)): accurate to a few fp32 units at
+ * every theta, and theta = 0 is the pure translation y = p + v with finite gradients (d w = p x g + (v x g)/2).
  * w, v, points, out: (n_points, 3) fp32 row-major.  The backward writes the gradients w.r.t. w, v and points
  * (each may be NULL). */
 int hn_se3_apply_forward(const float* w, const float* v, const float* points, int n_points, float* out,
