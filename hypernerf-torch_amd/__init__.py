@@ -17,7 +17,8 @@ from .arena import ParamArena
 from .optim import ArenaAdam, ArenaRAdam, ArenaRanger, ArenaSGD, GradClip
 from .functional import get_precision, set_precision
 from . import geometry
-from .geometry import density_grid, extract_isosurface, extract_mesh, read_ply, write_ply
+from .geometry import (component_sizes, density_grid, extract_isosurface, extract_mesh, filter_mesh, mesh_components, read_ply,
+                       vertex_colors, write_ply)
 
 __version__ = "0.1.0"
 

@@ -178,6 +178,8 @@ EXPORTS = ["hn_version", "hn_abi_sizes", "hn_build_config", "hn_mlp_wgrad_reduce
            "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad",
            "hn_ssim_workspace_bytes", "hn_ssim_forward", "hn_ssim_backward", "hn_msssim_workspace_bytes", "hn_msssim_forward",
            "hn_grid_points", "hn_density_activate", "hn_iso_mark", "hn_iso_vertices", "hn_iso_faces",
+           "hn_cc_init", "hn_cc_round", "hn_cc_sizes", "hn_mesh_keep", "hn_mesh_compact", "hn_gather_rows",
+           "hn_vertex_viewdirs",
            "hn_bg_sample", "hn_bg_loss_forward", "hn_bg_loss_forward_grad", "hn_bg_loss_backward",
            "hn_depth_index", "hn_random_fill",
            "hn_probe_mfma", "hn_calib_mfma", "hn_calib_stream", "hn_calib_stream_pattern", "hn_calib_ring"]
@@ -196,6 +198,15 @@ ARGTYPES = {
                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "hn_iso_faces": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                      C.c_void_p],
+    "hn_cc_init": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p],
+    "hn_cc_round": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p],
+    "hn_cc_sizes": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_mesh_keep": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_mesh_compact": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
+                        C.c_void_p, C.c_void_p, C.c_void_p],
+    "hn_gather_rows": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p],
+    "hn_vertex_viewdirs": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_float),
+                           C.c_void_p, C.c_void_p],
     "hn_bg_sample": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
                      C.c_void_p, C.c_void_p],
     "hn_bg_loss_forward": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p],

@@ -1,5 +1,6 @@
 // Geometry out of a trained field, for gfx950: lattice points for density queries, the density activation of a point
-// query, and an indexed triangle mesh of an isosurface by marching tetrahedra.
+// query, an indexed triangle mesh of an isosurface by marching tetrahedra, and what follows on that mesh: connected
+// components, filtering by component, view directions for vertex colours (further down, each with its own header).
 //
 // Lattice: (nx, ny, nz) points over bounds (xmin, xmax, ymin, ymax, zmin, zmax), point index p = (i*ny + j)*nz + k at
 // lo + (i, j, k) * step, step = (hi - lo) / (n - 1) taken once on the host; product and sum are rounded on their own
@@ -416,6 +417,328 @@ extern "C" int hn_iso_faces(const float* grid_dev, int nx, int ny, int nz, float
   else
     hipLaunchKernelGGL(hn_iso_faces_kernel<false>, grid, dim3(HN_ISO_BLOCK), 0, (hipStream_t)stream, grid_dev, nx, ny, nz,
                        iso, slots_dev, block_offsets_dev, block_counts_dev, faces_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Connected components of an indexed mesh.  Two vertices are connected when a face holds both; the label of a vertex is
+// the SMALLEST vertex id of its component.  parent[] (int32, V entries) starts as the identity and only ever goes down:
+//   invariant  parent[v] <= v, and parent[v] is a vertex of v's component.
+// One round = two launches:
+//   hook   per face (a, b, c): m = min(parent[a], parent[b], parent[c]); atomicMin(parent[x], m) for x in a, b, c and for
+//          their three parents — a round of min-label propagation over the faces plus the hooking of the old roots;
+//   jump   per vertex: follow parent at most HN_CC_HOPS times (ids strictly decrease along the way, nobody is waited
+//          for) and store where it got to.
+// A launch that lowers an entry stores the round number into flags[1]; the host stops after the first round that leaves
+// it untouched.  At that point every face sees one value and parent[parent[v]] == parent[v]: every component is a star
+// around one root r <= all its members that is itself a member, hence its smallest id.
+// Rounds needed: plain min-label propagation L[v] <- min over the faces of v reaches the fixed point in at most V - 1
+// rounds (the smallest id travels one face per round, a path has at most V - 1 edges) and every parent[v] here is, by
+// induction over the rounds, <= that L[v] (the hook does at least that step on values that are already lower, the jump
+// only lowers) and >= the component's smallest id: V - 1 rounds that change something at most, one more that does not.
+// The caller's cap is V + 1.  In practice the jump makes it logarithmic (DESIGN.md 3.9 has the measured counts).
+// Out-of-range ids: hn_cc_init reports them in flags[0]; hook and size launches skip such faces, so nothing is ever
+// written outside parent[0 .. V).
+// ------------------------------------------------------------------------------------------------
+#define HN_CC_HOPS 16
+
+__global__ __launch_bounds__(256) void hn_cc_init_kernel(const int32_t* __restrict__ faces, long long n_faces,
+                                                         int32_t* __restrict__ parent, long long n_vertices,
+                                                         int32_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) flags[1] = 0;
+  if (i < n_vertices) parent[i] = (int32_t)i;
+  if (i < n_faces) {
+    const int32_t a = faces[3 * i], b = faces[3 * i + 1], c = faces[3 * i + 2];
+    // every thread that sees a bad id stores the same 1: no ordering to depend on
+    if (a < 0 || b < 0 || c < 0 || a >= n_vertices || b >= n_vertices || c >= n_vertices) flags[0] = 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void hn_cc_hook_kernel(const int32_t* __restrict__ faces, long long n_faces,
+                                                         int32_t* parent, long long n_vertices, int round,
+                                                         int32_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_faces) return;
+  const int32_t v[3] = {faces[3 * i], faces[3 * i + 1], faces[3 * i + 2]};
+  if (v[0] < 0 || v[1] < 0 || v[2] < 0 || v[0] >= n_vertices || v[1] >= n_vertices || v[2] >= n_vertices) return;
+  // relaxed loads of words that other threads lower meanwhile: any value read is a member of the component that is <= the
+  // value at the start of the round, which is all the argument above needs
+  const int32_t p[3] = {__hip_atomic_load(parent + v[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                        __hip_atomic_load(parent + v[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                        __hip_atomic_load(parent + v[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)};
+  const int32_t m = min(p[0], min(p[1], p[2]));
+  bool lowered = false;
+  // integer atomicMin: the entry ends up as the minimum of everything offered to it, whatever the order of arrival, and
+  // the fixed point (the smallest id of the component) does not depend on scheduling at all — only the number of rounds may
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    if (p[s] > m) {
+      lowered |= atomicMin(parent + v[s], m) > m;
+      lowered |= atomicMin(parent + p[s], m) > m;       // p[s] is a vertex id in [0, V): the invariant
+    }
+  }
+  if (lowered) flags[1] = round;
+}
+
+__global__ __launch_bounds__(256) void hn_cc_jump_kernel(int32_t* parent, long long n_vertices, int round,
+                                                         int32_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_vertices) return;
+  const int32_t first = __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  int32_t p = first;
+  for (int hop = 0; hop < HN_CC_HOPS; ++hop) {
+    const int32_t q = __hip_atomic_load(parent + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (q == p) break;
+    p = q;                                              // q < p: the walk ends, with or without the hop limit
+  }
+  if (p < first) {
+    atomicMin(parent + i, p);                           // never raises what a concurrent walk already stored
+    flags[1] = round;
+  }
+}
+
+extern "C" int hn_cc_init(const int32_t* faces_dev, long long n_faces, int32_t* parent_dev, long long n_vertices,
+                          int32_t* flags_dev, hnStream_t stream) {
+  if (n_faces < 0 || n_vertices < 0 || n_faces > 2147483647ll || n_vertices > 2147483647ll) return -2;
+  if (flags_dev == nullptr || (n_faces > 0 && faces_dev == nullptr) || (n_vertices > 0 && parent_dev == nullptr)) return -2;
+  const long long n = n_faces > n_vertices ? n_faces : n_vertices;
+  hipLaunchKernelGGL(hn_cc_init_kernel, dim3((unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1)), dim3(256), 0,
+                     (hipStream_t)stream, faces_dev, n_faces, parent_dev, n_vertices, flags_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int hn_cc_round(const int32_t* faces_dev, long long n_faces, int32_t* parent_dev, long long n_vertices,
+                           int round, int32_t* flags_dev, hnStream_t stream) {
+  if (n_faces <= 0 || n_vertices <= 0 || n_faces > 2147483647ll || n_vertices > 2147483647ll || round < 1) return -2;
+  if (faces_dev == nullptr || parent_dev == nullptr || flags_dev == nullptr) return -2;
+  hipLaunchKernelGGL(hn_cc_hook_kernel, dim3((unsigned)((n_faces + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     faces_dev, n_faces, parent_dev, n_vertices, round, flags_dev);
+  HN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(hn_cc_jump_kernel, dim3((unsigned)((n_vertices + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     parent_dev, n_vertices, round, flags_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// hn_cc_sizes: sizes[label] += 1 per face, label = labels[first vertex of the face]; sizes (V) zeroed by the caller.
+// Integer sums do not depend on the order of arrival.  Nearly every face of an extracted mesh carries the label of the one
+// large component, so the adds are folded before they reach memory: a workgroup takes HN_CC_SIZES_TILE faces, counts those
+// that carry the label of its first face in registers, then LDS, and sends ONE add for them; the lanes of a wave that
+// hold any other label send one add per distinct label.  A face with an id, or a label, outside [0, V) is skipped and
+// reported in flags[0].
+// ------------------------------------------------------------------------------------------------
+#define HN_CC_SIZES_PER_THREAD 8
+#define HN_CC_SIZES_TILE (256 * HN_CC_SIZES_PER_THREAD)
+
+HN_DEV int32_t hn_cc_face_label(const int32_t* __restrict__ labels, const int32_t* __restrict__ faces, long long i,
+                                long long n_vertices, int32_t* __restrict__ flags) {
+  const int32_t a = faces[3 * i];
+  int32_t label = -1;
+  if (a >= 0 && a < n_vertices) label = labels[a];
+  if (label < 0 || label >= n_vertices) {
+    label = -1;
+    flags[0] = 1;
+  }
+  return label;
+}
+
+__global__ __launch_bounds__(256) void hn_cc_sizes_kernel(const int32_t* __restrict__ labels,
+                                                          const int32_t* __restrict__ faces, long long n_faces,
+                                                          long long n_vertices, int32_t* __restrict__ sizes,
+                                                          int32_t* __restrict__ flags) {
+  __shared__ int block_count;
+  const long long base = (long long)blockIdx.x * HN_CC_SIZES_TILE;
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x == 0) block_count = 0;
+  __syncthreads();
+  const int32_t common = hn_cc_face_label(labels, faces, base, n_vertices, flags);     // base < n_faces: the grid's size
+  int mine = 0;
+  for (int j = 0; j < HN_CC_SIZES_PER_THREAD; ++j) {
+    const long long i = base + (long long)j * 256 + threadIdx.x;
+    int32_t label = i < n_faces ? hn_cc_face_label(labels, faces, i, n_vertices, flags) : -1;
+    if (label >= 0 && label == common) {
+      ++mine;
+      label = -1;
+    }
+    unsigned long long todo = __ballot(label >= 0);
+    while (todo != 0ull) {                               // wave-uniform: `todo` is the same in every lane
+      const int leader = __ffsll((long long)todo) - 1;
+      const int32_t lead = __shfl(label, leader, 64);
+      const unsigned long long same = __ballot(label == lead) & todo;
+      if (lane == leader) atomicAdd(sizes + lead, (int32_t)__popcll(same));
+      todo &= ~same;
+    }
+  }
+  if (mine != 0) atomicAdd(&block_count, mine);
+  __syncthreads();
+  if (threadIdx.x == 0 && block_count != 0) atomicAdd(sizes + common, (int32_t)block_count);
+}
+
+extern "C" int hn_cc_sizes(const int32_t* labels_dev, const int32_t* faces_dev, long long n_faces, long long n_vertices,
+                           int32_t* sizes_dev, int32_t* flags_dev, hnStream_t stream) {
+  if (n_faces <= 0 || n_vertices <= 0 || n_faces > 2147483647ll || n_vertices > 2147483647ll) return -2;
+  if (labels_dev == nullptr || faces_dev == nullptr || sizes_dev == nullptr || flags_dev == nullptr) return -2;
+  hipLaunchKernelGGL(hn_cc_sizes_kernel, dim3((unsigned)((n_faces + HN_CC_SIZES_TILE - 1) / HN_CC_SIZES_TILE)), dim3(256), 0,
+                     (hipStream_t)stream, labels_dev, faces_dev, n_faces, n_vertices, sizes_dev, flags_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Filtering.  keep_comp[label] (one byte per vertex id, non-zero = the component stays) ->
+//   hn_mesh_keep     vkeep[v] = keep_comp[labels[v]], fkeep[f] = keep_comp[labels[first vertex of f]] (int32 0 / 1, ready
+//                    for an inclusive scan; a face with an id outside [0, V) is dropped)
+//   hn_mesh_compact  vscan / fscan = the inclusive scans: vertex_index[vscan[v] - 1] = v for a kept v, and a kept face goes
+//                    to row fscan[f] - 1 with every id replaced by vscan[id] - 1 — relative orders kept, no atomics
+//   hn_gather_rows   dst[r] = src[index[r]] for rows of row_bytes bytes (words when everything is 4-byte aligned)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_mesh_keep_kernel(const int32_t* __restrict__ labels,
+                                                           const int32_t* __restrict__ faces,
+                                                           const uint8_t* __restrict__ keep_comp, long long n_vertices,
+                                                           long long n_faces, int32_t* __restrict__ vkeep,
+                                                           int32_t* __restrict__ fkeep) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_vertices) {
+    const int32_t l = labels[i];
+    vkeep[i] = (l >= 0 && l < n_vertices && keep_comp[l] != 0) ? 1 : 0;
+  }
+  if (i < n_faces) {
+    const int32_t a = faces[3 * i], b = faces[3 * i + 1], c = faces[3 * i + 2];
+    int32_t k = 0;
+    if (a >= 0 && b >= 0 && c >= 0 && a < n_vertices && b < n_vertices && c < n_vertices) {
+      const int32_t l = labels[a];
+      k = (l >= 0 && l < n_vertices && keep_comp[l] != 0) ? 1 : 0;
+    }
+    fkeep[i] = k;
+  }
+}
+
+extern "C" int hn_mesh_keep(const int32_t* labels_dev, const int32_t* faces_dev, const uint8_t* keep_comp_dev,
+                            long long n_vertices, long long n_faces, int32_t* vkeep_dev, int32_t* fkeep_dev,
+                            hnStream_t stream) {
+  if (n_vertices <= 0 || n_faces < 0 || n_faces > 2147483647ll || n_vertices > 2147483647ll) return -2;
+  if (labels_dev == nullptr || keep_comp_dev == nullptr || vkeep_dev == nullptr) return -2;
+  if (n_faces > 0 && (faces_dev == nullptr || fkeep_dev == nullptr)) return -2;
+  const long long n = n_faces > n_vertices ? n_faces : n_vertices;
+  hipLaunchKernelGGL(hn_mesh_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, labels_dev,
+                     faces_dev, keep_comp_dev, n_vertices, n_faces, vkeep_dev, fkeep_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void hn_mesh_compact_kernel(const int32_t* __restrict__ faces,
+                                                              const int32_t* __restrict__ vscan,
+                                                              const int32_t* __restrict__ fscan, long long n_vertices,
+                                                              long long n_faces, long long n_vertices_out,
+                                                              long long n_faces_out, int32_t* __restrict__ vertex_index,
+                                                              int32_t* __restrict__ faces_out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_vertices) {
+    const int32_t s = vscan[i], before = i > 0 ? vscan[i - 1] : 0;
+    if (s != before && s >= 1 && s <= n_vertices_out) vertex_index[s - 1] = (int32_t)i;
+  }
+  if (i < n_faces) {
+    const int32_t s = fscan[i], before = i > 0 ? fscan[i - 1] : 0;
+    if (s != before && s >= 1 && s <= n_faces_out) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int32_t id = faces[3 * i + c];                // a kept face has its ids in range (hn_mesh_keep)
+        faces_out[3 * (size_t)(s - 1) + c] = (id >= 0 && id < n_vertices) ? vscan[id] - 1 : -1;
+      }
+    }
+  }
+}
+
+extern "C" int hn_mesh_compact(const int32_t* faces_dev, const int32_t* vscan_dev, const int32_t* fscan_dev,
+                               long long n_vertices, long long n_faces, long long n_vertices_out, long long n_faces_out,
+                               int32_t* vertex_index_dev, int32_t* faces_out_dev, hnStream_t stream) {
+  if (n_vertices <= 0 || n_faces < 0 || n_faces > 2147483647ll || n_vertices > 2147483647ll) return -2;
+  if (n_vertices_out < 0 || n_vertices_out > n_vertices || n_faces_out < 0 || n_faces_out > n_faces) return -2;
+  if (vscan_dev == nullptr || (n_vertices_out > 0 && vertex_index_dev == nullptr)) return -2;
+  if (n_faces > 0 && (faces_dev == nullptr || fscan_dev == nullptr)) return -2;
+  if (n_faces_out > 0 && faces_out_dev == nullptr) return -2;
+  const long long n = n_faces > n_vertices ? n_faces : n_vertices;
+  hipLaunchKernelGGL(hn_mesh_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces_dev,
+                     vscan_dev, fscan_dev, n_vertices, n_faces, n_vertices_out, n_faces_out, vertex_index_dev,
+                     faces_out_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void hn_gather_rows_kernel(const T* __restrict__ src, long long n_src,
+                                                             const int32_t* __restrict__ index, long long n_rows,
+                                                             int row_items, T* __restrict__ dst) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_rows * row_items) return;
+  const long long r = i / row_items;
+  const int c = (int)(i - r * row_items);
+  const int32_t s = index[r];
+  dst[i] = (s >= 0 && s < n_src) ? src[(size_t)s * row_items + c] : T(0);
+}
+
+extern "C" int hn_gather_rows(const void* src_dev, long long n_src, const int32_t* index_dev, long long n_rows,
+                              long long row_bytes, void* dst_dev, hnStream_t stream) {
+  if (n_src <= 0 || n_rows <= 0 || row_bytes <= 0 || n_src > 2147483647ll || n_rows > 2147483647ll || row_bytes > 65536) return -2;
+  if (src_dev == nullptr || index_dev == nullptr || dst_dev == nullptr) return -2;
+  const bool words = row_bytes % 4 == 0 && (uintptr_t)src_dev % 4 == 0 && (uintptr_t)dst_dev % 4 == 0;
+  const long long items = words ? row_bytes / 4 : row_bytes;
+  const long long blocks = (n_rows * items + 255) / 256;
+  if (blocks > 2147483647ll) return -2;
+  if (words)
+    hipLaunchKernelGGL(hn_gather_rows_kernel<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t*)src_dev, n_src, index_dev, n_rows, (int)items, (uint32_t*)dst_dev);
+  else
+    hipLaunchKernelGGL(hn_gather_rows_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)src_dev, n_src, index_dev, n_rows, (int)items, (uint8_t*)dst_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// hn_vertex_viewdirs: out[r] = the direction a colour query looks along at vertex i = min(start + r, V - 1), r < count
+// (rows past the mesh, the padding of a last chunk, repeat the last vertex).  u = -normal[i] (cam_host == NULL: head-on
+// from outside) or vertex[i] - c; out = u / |u| with |u| = sqrt((ux*ux + uy*uy) + uz*uz), every operation fp32 and
+// rounded on its own; |u| = 0 (or NaN) gives (0, 0, 1), the direction query_points itself defaults to.
+// ------------------------------------------------------------------------------------------------
+struct HnVec3 { float v[3]; };
+
+__global__ __launch_bounds__(256) void hn_vertex_viewdirs_kernel(const float* __restrict__ vertices,
+                                                                 const float* __restrict__ normals, long long n_vertices,
+                                                                 long long start, long long count, int has_cam,
+                                                                 HnVec3 cam, float* __restrict__ out) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= count) return;
+  long long i = start + r;
+  if (i > n_vertices - 1) i = n_vertices - 1;
+  float u[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    u[c] = has_cam != 0 ? __fsub_rn(vertices[3 * (size_t)i + c], cam.v[c]) : -normals[3 * (size_t)i + c];
+  const float len = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(u[0], u[0]), __fmul_rn(u[1], u[1])), __fmul_rn(u[2], u[2])));
+  const bool ok = len > 0.0f;
+  float* o = out + 3 * (size_t)r;
+  o[0] = ok ? __fdiv_rn(u[0], len) : 0.0f;
+  o[1] = ok ? __fdiv_rn(u[1], len) : 0.0f;
+  o[2] = ok ? __fdiv_rn(u[2], len) : 1.0f;
+}
+
+extern "C" int hn_vertex_viewdirs(const float* vertices_dev, const float* normals_dev, long long n_vertices,
+                                  long long start, long long count, const float* cam_host, float* out_dev,
+                                  hnStream_t stream) {
+  if (n_vertices <= 0 || n_vertices > 2147483647ll || start < 0 || start >= n_vertices || count <= 0 ||
+      count > 2147483647ll)
+    return -2;
+  if (out_dev == nullptr || (cam_host != nullptr ? vertices_dev == nullptr : normals_dev == nullptr)) return -2;
+  HnVec3 cam = {{0.f, 0.f, 0.f}};
+  if (cam_host != nullptr)
+    for (int c = 0; c < 3; ++c) cam.v[c] = cam_host[c];
+  hipLaunchKernelGGL(hn_vertex_viewdirs_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     vertices_dev, normals_dev, n_vertices, start, count, cam_host != nullptr ? 1 : 0, cam, out_dev);
   HN_CHECK_LAUNCH();
   return 0;
 }

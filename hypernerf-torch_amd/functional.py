@@ -1316,6 +1316,154 @@ def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torc
     return {'vertices': vertices, 'normals': normals, 'faces': faces}
 
 
+def _check_faces(faces, num_vertices, what: str):
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be a (F, 3) tensor")
+    if faces.dtype != torch.int32:
+        raise ValueError(f"{what}: faces must be int32, got {faces.dtype}")
+    v = int(num_vertices)
+    if v < 0 or v > INT32_MAX or faces.shape[0] > INT32_MAX:
+        raise ValueError(f"{what}: {v} vertices / {faces.shape[0]} faces outside 0 .. 2**31 - 1 = {INT32_MAX}")
+    if not faces.is_cuda:
+        raise ValueError(f"{what}: faces must live on the GPU (there is no CPU fallback)")
+    return faces.detach().contiguous(), v
+
+
+@torch.no_grad()
+def mesh_components(faces: torch.Tensor, num_vertices: int, out: Optional[torch.Tensor] = None,
+                    return_rounds: bool = False):
+    """labels (V,) int32 of the mesh faces (F, 3) int32 over V vertices: the SMALLEST vertex id of the vertex's connected
+    component (two vertices are connected when a face holds both; an unreferenced vertex is its own component) — a
+    definition that no scheduling can change, so two runs give the same bits (hn_cc_init / hn_cc_round: hook and
+    pointer-jump rounds with integer atomicMin).  One host read of two ints per round; the loop is capped at V + 1 rounds
+    (min-label propagation needs at most V - 1 that change something, every round here does at least its step) and a
+    RuntimeError names the cap if it is ever exceeded.  A vertex id outside [0, V) is a ValueError; nothing is written
+    outside the label array.  `out`: a contiguous (V,) int32 tensor to label in place.  `return_rounds`: (labels, rounds
+    run, the last one included that changed nothing)."""
+    faces, v = _check_faces(faces, num_vertices, "mesh_components")
+    dev = faces.device
+    if out is None:
+        out = torch.empty(v, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.shape != (v,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"mesh_components: out must be a contiguous ({v},) int32 tensor on {dev}")
+    n_faces = faces.shape[0]
+    rounds = 0
+    if v == 0 and n_faces == 0:
+        return (out, rounds) if return_rounds else out
+    L.load()
+    cap = v + 1
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        L.launch("hn_cc_init", faces.data_ptr() if n_faces else None, n_faces, out.data_ptr() if v else None, v,
+                 flags.data_ptr(), stream)
+        if n_faces == 0:
+            return (out, rounds) if return_rounds else out
+        if v == 0:
+            raise ValueError("mesh_components: faces hold a vertex id outside [0, 0)")
+        while True:
+            rounds += 1
+            if rounds > cap:
+                raise RuntimeError(f"mesh_components: no fixed point after the cap of V + 1 = {cap} rounds")
+            L.launch("hn_cc_round", faces.data_ptr(), n_faces, out.data_ptr(), v, rounds, flags.data_ptr(), stream)
+            err, changed = flags.tolist()
+            if err:
+                raise ValueError(f"mesh_components: faces hold a vertex id outside [0, {v})")
+            if changed != rounds:
+                break
+    return (out, rounds) if return_rounds else out
+
+
+@torch.no_grad()
+def component_sizes(labels: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """(V,) int32: the number of faces of every component at index = its label (mesh_components), zero elsewhere
+    (hn_cc_sizes: integer atomic adds, whose sum does not depend on their order).  No host synchronisation: an id or a
+    label outside [0, V) is skipped (mesh_components refuses such faces first)."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype != torch.int32:
+        raise ValueError("component_sizes: labels must be a (V,) int32 tensor")
+    faces, v = _check_faces(faces, labels.shape[0], "component_sizes")
+    L.require_gpu(labels)
+    sizes = torch.zeros(v, dtype=torch.int32, device=faces.device)
+    if v and faces.shape[0]:
+        L.load()
+        with torch.cuda.device(faces.device):
+            flags = torch.zeros(2, dtype=torch.int32, device=faces.device)
+            L.launch("hn_cc_sizes", labels.detach().contiguous().data_ptr(), faces.data_ptr(), faces.shape[0], v,
+                     sizes.data_ptr(), flags.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    return sizes
+
+
+@torch.no_grad()
+def gather_rows(src: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """src[index] along the first dimension for an int32 index (hn_gather_rows): any dtype, any trailing shape."""
+    L.require_gpu(src, index)
+    src = src.detach().contiguous()
+    n = index.shape[0]
+    out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if out.numel():
+        L.load()
+        row_bytes = out.numel() // n * out.element_size()
+        with torch.cuda.device(src.device):
+            L.launch("hn_gather_rows", src.data_ptr(), src.shape[0], index.data_ptr(), n, row_bytes, out.data_ptr(),
+                     torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+@torch.no_grad()
+def compact_mesh(faces: torch.Tensor, labels: torch.Tensor, keep_comp: torch.Tensor):
+    """(vertex_index (V',) int32, faces (F', 3) int32): the vertices whose component is kept (keep_comp: (V,) bool or
+    uint8 indexed by label) in their old order, and the faces of those components in their old order, re-indexed
+    (hn_mesh_keep, two torch.cumsum scans, hn_mesh_compact).  One host read (both counts at once) sizes the outputs."""
+    faces, v = _check_faces(faces, labels.shape[0], "compact_mesh")
+    dev = faces.device
+    n_faces = faces.shape[0]
+    if v == 0:
+        return torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
+    L.load()
+    keep_comp = keep_comp.to(torch.uint8).contiguous()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        vkeep = torch.empty(v, dtype=torch.int32, device=dev)
+        fkeep = torch.empty(max(n_faces, 1), dtype=torch.int32, device=dev)
+        if n_faces == 0:
+            fkeep.zero_()
+        L.launch("hn_mesh_keep", labels.contiguous().data_ptr(), faces.data_ptr() if n_faces else None, keep_comp.data_ptr(),
+                 v, n_faces, vkeep.data_ptr(), fkeep.data_ptr(), stream)
+        vscan = torch.cumsum(vkeep, 0, dtype=torch.int32)
+        fscan = torch.cumsum(fkeep, 0, dtype=torch.int32)
+        n_v, n_f = torch.stack([vscan[-1], fscan[-1]]).tolist()
+        vertex_index = torch.empty(n_v, dtype=torch.int32, device=dev)
+        faces_out = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
+        if n_v:
+            L.launch("hn_mesh_compact", faces.data_ptr() if n_faces else None, vscan.data_ptr(), fscan.data_ptr(), v, n_faces,
+                     n_v, n_f, vertex_index.data_ptr(), faces_out.data_ptr() if n_f else None, stream)
+    return vertex_index, faces_out
+
+
+@torch.no_grad()
+def vertex_viewdirs(vertices: torch.Tensor, normals: Optional[torch.Tensor], start: int, count: int,
+                    camera=None) -> torch.Tensor:
+    """(count, 3) fp32 unit directions for vertices start .. start + count - 1 (hn_vertex_viewdirs; rows past the mesh
+    repeat its last vertex): -normal/|normal| when `camera` is None, else (v - camera)/|v - camera| for the three host
+    floats `camera`; a zero length gives (0, 0, 1).  float32 NumPy gives the same values to a few roundings."""
+    L.require_gpu(vertices, normals)
+    ref = vertices if camera is not None else normals
+    if ref is None or ref.dim() != 2 or ref.shape[1] != 3 or ref.dtype != torch.float32:
+        raise ValueError("vertex_viewdirs: vertices / normals must be (V, 3) float32")
+    v = ref.shape[0]
+    if not 0 <= start < v or not 0 < count <= INT32_MAX:
+        raise ValueError(f"vertex_viewdirs: start {start} / count {count} outside the mesh of {v} vertices")
+    L.load()
+    ref = ref.detach().contiguous()
+    out = torch.empty((count, 3), dtype=torch.float32, device=ref.device)
+    cam = None if camera is None else (C.c_float * 3)(*(float(x) for x in camera))
+    with torch.cuda.device(ref.device):
+        L.launch("hn_vertex_viewdirs", ref.data_ptr() if camera is not None else None,
+                 ref.data_ptr() if camera is None else None, v, start, count, cam, out.data_ptr(),
+                 torch.cuda.current_stream().cuda_stream)
+    return out
+
+
 # --------------------------------------------------------------------------------------------
 # on-device ray generation
 # --------------------------------------------------------------------------------------------

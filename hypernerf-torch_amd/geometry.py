@@ -2,17 +2,28 @@
 
     grid = density_grid(model, bounds, 256, frame_id=12)            # (256, 256, 256) fp32 on the model's device
     mesh = extract_isosurface(grid, iso=10.0, bounds=bounds)         # {'vertices', 'normals', 'faces'}
-    write_ply("frame12.ply", mesh['vertices'], mesh['faces'], mesh['normals'])
+    mesh = filter_mesh(mesh, keep_largest=1)                         # drop the floaters; + 'vertex_index'
+    mesh['colors'] = vertex_colors(model, mesh['vertices'], mesh['normals'], frame_id=12)    # (V, 3) uint8
+    write_ply("frame12.ply", mesh['vertices'], mesh['faces'], mesh['normals'], mesh['colors'])
 
 The lattice points are observation-space points of frame `frame_id`: they go through that frame's warp and hyper slice
 into the template (NerfModel.query_points), so the mesh is the surface of the deforming scene at that frame.  Lattice
 points are written chunk by chunk by a kernel (hn_grid_points) and never exist as one (N, 3) tensor; the isosurface is
-marching tetrahedra in HIP (csrc/hn_geometry.hip).  Vertex colours are not produced: a colour needs a view direction
-per point, which a lattice does not have.
+marching tetrahedra in HIP (csrc/hn_geometry.hip).
+
+Floaters: `mesh_components` labels every vertex with the smallest vertex id of its connected component (two vertices are
+connected when a face holds both; hook and pointer-jump rounds with integer atomicMin, a definition no scheduling can
+change), `component_sizes` counts the faces per label, and `filter_mesh` keeps the components with at least `min_faces`
+faces and / or the `keep_largest` ones with the most faces (ties to the smaller label), orders kept, faces re-indexed.
+
+Colours: a lattice has no view direction, but a mesh vertex has a normal and a frame has a camera.  `vertex_colors`
+looks at every vertex along -normal (head-on from outside) or from a camera position, (v - c)/|v - c| — a zero length
+gives (0, 0, 1) — and takes the field's `rgb` at the vertex (rows of one point through NerfModel.query_points, the
+directions written chunk by chunk by hn_vertex_viewdirs), as float32 or as (rgb * 255) truncated to uint8.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -63,9 +74,111 @@ def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torc
     return F.extract_isosurface(grid, iso, bounds)
 
 
-def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, **kw) -> Dict[str, torch.Tensor]:
-    """extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds)."""
-    return extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds)
+def mesh_components(faces: torch.Tensor, num_vertices: int) -> torch.Tensor:
+    """labels (V,) int32: the smallest vertex id of every vertex's connected component (functional.mesh_components)."""
+    return F.mesh_components(faces, num_vertices)
+
+
+def component_sizes(labels: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """(V,) int32: faces per component at index = label, zero elsewhere (functional.component_sizes)."""
+    return F.component_sizes(labels, faces)
+
+
+@torch.no_grad()
+def filter_mesh(mesh: Dict[str, torch.Tensor], min_faces: Optional[int] = None,
+                keep_largest: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """The mesh without its small components.  A component (mesh_components) stays when it has at least `min_faces` faces
+    and, if `keep_largest` = k is given, is among the k components with the most faces, ties going to the smaller label.
+    A component without a face (an unreferenced vertex) never stays.  Kept vertices and faces keep their relative order,
+    faces are re-indexed, every tensor of the dict whose first dimension is V ('vertices', 'normals', 'colors', ...) is
+    compacted alike, and the result gains 'vertex_index' (V',) int32: the id every kept vertex had in `mesh`.  An empty result
+    gives zero-length tensors.  With both arguments None the SAME dict comes back.
+    Host synchronisations: one read of two ints per labelling round (mesh_components), then ONE read of the vertex and
+    the face count, which size the outputs; which components stay is decided on the device (topk, cumsum)."""
+    if min_faces is None and keep_largest is None:
+        return mesh
+    faces, vertices = mesh['faces'], mesh['vertices']
+    v = vertices.shape[0]
+    dev = faces.device
+    per_vertex = [k for k, t in mesh.items() if k not in ('faces', 'vertex_index') and isinstance(t, torch.Tensor)
+                  and t.dim() >= 1 and t.shape[0] == v]
+    labels = F.mesh_components(faces, v)
+    sizes = F.component_sizes(labels, faces)
+    keep = sizes >= max(int(min_faces or 0), 1)
+    if keep_largest is not None:
+        k = int(keep_largest)
+        if k <= 0:
+            keep = torch.zeros_like(keep)
+        elif k < v:
+            # the k-th largest size t: everything above it stays, and of the components AT t the first (k - #above) by label
+            t = torch.topk(sizes, k).values[-1]
+            above, at = sizes > t, sizes == t
+            keep &= above | (at & (torch.cumsum(at, 0) <= k - above.sum()))
+    vertex_index, new_faces = F.compact_mesh(faces, labels, keep)
+    out = dict(mesh)
+    for name in per_vertex:
+        out[name] = F.gather_rows(mesh[name], vertex_index)
+    out['faces'] = new_faces
+    out['vertex_index'] = vertex_index
+    return out
+
+
+@torch.no_grad()
+def vertex_colors(model, vertices: torch.Tensor, normals: Optional[torch.Tensor], frame_id: int,
+                  view: Union[str, Sequence[float], torch.Tensor] = 'normal', level: str = 'fine', chunk: int = 1 << 20,
+                  render_opts=None, dtype=torch.uint8) -> torch.Tensor:
+    """(V, 3) colours of mesh vertices at frame `frame_id`: the field's `rgb` (NerfModel.query_points) at the vertex
+    position, seen along -normal/|normal| (`view='normal'`: head-on from outside) or from the camera position `view` =
+    (cx, cy, cz), along (v - c)/|v - c|; a zero normal or v == c looks along (0, 0, 1).  The id fills every metadata key,
+    as in density_grid.  `chunk` vertices at a time, as rows of ONE point with their own direction (hn_vertex_viewdirs
+    writes a chunk of directions; the full direction tensor never exists); the values do not depend on `chunk`.
+    dtype float32: that rgb; uint8: (rgb * 255) truncated on the device, the convention of inference.evaluate_images.
+    A model with use_viewdirs=False ignores the direction.  Inference only; model._level_state is left as found."""
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"vertex_colors: dtype must be torch.uint8 or torch.float32, got {dtype}")
+    if int(chunk) < 1:
+        raise ValueError(f"vertex_colors: chunk must be positive, got {chunk}")
+    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertex_colors: vertices must be a (V, 3) tensor")
+    camera = None
+    if not (isinstance(view, str) and view == 'normal'):
+        if isinstance(view, str):
+            raise ValueError(f"vertex_colors: view must be 'normal' or a camera position (cx, cy, cz), got {view!r}")
+        camera = [float(x) for x in (view.detach().cpu().reshape(-1).tolist() if isinstance(view, torch.Tensor) else view)]
+        if len(camera) != 3:
+            raise ValueError(f"vertex_colors: a camera position has three components, got {len(camera)}")
+    elif normals is None or normals.shape != vertices.shape:
+        raise ValueError("vertex_colors: view='normal' needs normals of the vertices' shape")
+    device = next(model.parameters()).device
+    vertices = vertices.detach().to(device=device, dtype=torch.float32).contiguous()
+    if camera is None:
+        normals = normals.detach().to(device=device, dtype=torch.float32).contiguous()
+    v = vertices.shape[0]
+    out = torch.empty((v, 3), dtype=dtype, device=device)
+    chunk = min(int(chunk), max(v, 1))
+    ids = torch.full((chunk,), int(frame_id), dtype=torch.int64, device=device)
+    for start in range(0, v, chunk):
+        n = min(chunk, v - start)
+        dirs = F.vertex_viewdirs(vertices, normals, start, n, camera)
+        metadata = {k: ids[:n] for k in ('warp', 'camera', 'appearance', 'time')}
+        rgb = model.query_points(vertices[start:start + n].view(n, 1, 3), metadata, level=level, viewdirs=dirs,
+                                 render_opts=render_opts)['rgb'].view(n, 3)
+        out[start:start + n] = rgb if dtype == torch.float32 else (rgb * 255).to(torch.uint8)
+    return out
+
+
+def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, colors=None, min_faces: Optional[int] = None,
+                 keep_largest: Optional[int] = None, **kw) -> Dict[str, torch.Tensor]:
+    """extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds), then
+    filter_mesh(min_faces, keep_largest) when either is given, then — only on what survived — 'colors' (V, 3) uint8 =
+    vertex_colors(view=colors) when `colors` is 'normal' or a camera position, with density_grid's level / chunk /
+    render_opts."""
+    mesh = extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds)
+    mesh = filter_mesh(mesh, min_faces=min_faces, keep_largest=keep_largest)
+    if colors is not None:
+        mesh = dict(mesh)
+        mesh['colors'] = vertex_colors(model, mesh['vertices'], mesh['normals'], frame_id, view=colors, **kw)
+    return mesh
 
 
 def _host(a, dtype):
@@ -74,9 +187,10 @@ def _host(a, dtype):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
-def write_ply(path, vertices, faces, normals=None) -> None:
-    """Binary little-endian PLY: vertices (V, 3) as float x y z (+ nx ny nz when `normals` (V, 3) is given), faces
-    (F, 3) as `list uchar int vertex_indices`.  Tensors or arrays."""
+def write_ply(path, vertices, faces, normals=None, colors=None) -> None:
+    """Binary little-endian PLY: vertices (V, 3) as float x y z (+ nx ny nz when `normals` (V, 3) is given, + uchar
+    red green blue when `colors` (V, 3) uint8 is given), faces (F, 3) as `list uchar int vertex_indices`.  Tensors or
+    arrays."""
     v = _host(vertices, "<f4").reshape(-1, 3)
     f = _host(faces, "<i4").reshape(-1, 3)
     cols = [v]
@@ -89,18 +203,34 @@ def write_ply(path, vertices, faces, normals=None) -> None:
         names += ["nx", "ny", "nz"]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}"]
     header += [f"property float {n}" for n in names]
+    table = np.concatenate(cols, axis=1).astype("<f4")
+    if colors is not None:
+        if isinstance(colors, torch.Tensor):
+            colors = colors.detach().cpu().numpy()
+        colors = np.asarray(colors)
+        if colors.dtype != np.uint8:
+            raise ValueError(f"write_ply: colors must be uint8, got {colors.dtype}")
+        colors = colors.reshape(-1, 3)
+        if colors.shape != v.shape:
+            raise ValueError(f"write_ply: {colors.shape[0]} colors for {v.shape[0]} vertices")
+        header += [f"property uchar {n}" for n in ("red", "green", "blue")]
+        vrec = np.empty(v.shape[0], dtype=[("f", "<f4", (table.shape[1],)), ("c", "u1", (3,))])     # packed: no padding
+        vrec["f"] = table
+        vrec["c"] = colors
+        table = vrec
     header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
     rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     rec["n"] = 3
     rec["idx"] = f
     with open(path, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))
-        fh.write(np.concatenate(cols, axis=1).astype("<f4").tobytes())
+        fh.write(table.tobytes())
         fh.write(rec.tobytes())
 
 
 def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
-    """What write_ply wrote: {'vertices': (V, 3) float32, 'normals': (V, 3) float32 | None, 'faces': (F, 3) int32}."""
+    """What write_ply wrote: {'vertices': (V, 3) float32, 'normals': (V, 3) float32 | None, 'faces': (F, 3) int32,
+    'colors': (V, 3) uint8 | None}."""
     with open(path, "rb") as fh:
         blob = fh.read()
     end = blob.index(b"end_header\n") + len(b"end_header\n")
@@ -116,16 +246,22 @@ def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
             props[cur] = []
         elif w[:1] == ["property"]:
             props[cur].append(w[1:])
-    names = [p[-1] for p in props.get("vertex", [])]
-    if any(p[0] != "float" for p in props.get("vertex", [])) or names[:3] != ["x", "y", "z"] \
+    vprops = props.get("vertex", [])
+    has_colors = vprops[-3:] == [["uchar", "red"], ["uchar", "green"], ["uchar", "blue"]]
+    fprops = vprops[:-3] if has_colors else vprops
+    names = [p[-1] for p in fprops]
+    if any(p[0] != "float" for p in fprops) or names[:3] != ["x", "y", "z"] \
             or props.get("face") != [["list", "uchar", "int", "vertex_indices"]]:
         raise ValueError(f"read_ply: {path} has a layout write_ply does not write")
     nv, nf, width = counts["vertex"], counts["face"], len(names)
-    table = np.frombuffer(blob, dtype="<f4", count=nv * width, offset=end).reshape(nv, width)
-    rec = np.frombuffer(blob, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=end + 4 * nv * width)
+    stride = 4 * width + (3 if has_colors else 0)
+    vrec = np.frombuffer(blob, dtype=[("f", "<f4", (width,)), ("c", "u1", (3 if has_colors else 0,))], count=nv, offset=end)
+    table = vrec["f"].reshape(nv, width)
+    rec = np.frombuffer(blob, dtype=[("n", "u1"), ("idx", "<i4", (3,))], count=nf, offset=end + stride * nv)
     if nf and not (rec["n"] == 3).all():
         raise ValueError(f"read_ply: {path} has faces that are not triangles")
-    if len(blob) != end + 4 * nv * width + 13 * nf:
-        raise ValueError(f"read_ply: {path} has {len(blob)} bytes, its header describes {end + 4 * nv * width + 13 * nf}")
+    if len(blob) != end + stride * nv + 13 * nf:
+        raise ValueError(f"read_ply: {path} has {len(blob)} bytes, its header describes {end + stride * nv + 13 * nf}")
     normals = table[:, 3:6].copy() if names[3:6] == ["nx", "ny", "nz"] else None
-    return {"vertices": table[:, :3].copy(), "normals": normals, "faces": rec["idx"].astype(np.int32).reshape(nf, 3)}
+    return {"vertices": table[:, :3].copy(), "normals": normals, "faces": rec["idx"].astype(np.int32).reshape(nf, 3),
+            "colors": vrec["c"].reshape(nv, 3).copy() if has_colors else None}

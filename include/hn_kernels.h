@@ -650,6 +650,55 @@ int hn_iso_vertices(const float* grid_dev, int nx, int ny, int nz, const float* 
 int hn_iso_faces(const float* grid_dev, int nx, int ny, int nz, float iso, const int32_t* slots_dev,
                  const int64_t* block_offsets_dev, int32_t* block_counts_dev, int32_t* faces_dev, hnStream_t stream);
 
+/* Connected components of an indexed triangle mesh, filtering by component, view directions for vertex colours
+ * (csrc/hn_geometry.hip; no reference counterpart).  faces (F, 3) int32, V vertices, F and V at most 2^31 - 1.
+ *
+ * Two vertices are connected when a face holds both; the label of a vertex is the SMALLEST vertex id of its component (a
+ * vertex no face references is its own component).  parent (V) int32 is the working array and, once a round changes
+ * nothing, the labels.  flags: two device int32, [0] = error (a vertex id or label outside [0, V) was met; such a face is
+ * skipped, nothing is written out of bounds), [1] = the number of the last round that lowered an entry of parent.
+ *   hn_cc_init   parent[v] = v, flags[1] = 0, flags[0] = 1 when a face holds an id outside [0, V) (flags[0] is only ever
+ *                set: the caller zeroes it).  F = 0 or V = 0 allowed (their pointers may then be NULL).
+ *   hn_cc_round  round `round` >= 1, two launches.  hook: per face m = min of the parents of its three vertices,
+ *                atomicMin(parent[x], m) for the three vertices and their three parents.  jump: per vertex follow parent
+ *                for at most 16 hops (ids strictly decrease) and atomicMin the entry with where that got to.  Whatever
+ *                lowered an entry stores `round` into flags[1]; the caller reads the flags after every round and stops at
+ *                the first round r with flags[1] != r.  Invariant: parent[v] <= v and parent[v] lies in v's component, so
+ *                the fixed point (every face sees one value, every parent is a root) is the smallest id whatever the
+ *                scheduling; only integer atomicMin is used.  At most V - 1 rounds change something (each does at least a
+ *                step of min-label propagation), one more reports none: the caller's cap is V + 1.
+ *   hn_cc_sizes  sizes[labels[first vertex of f]] += 1 per face (sizes (V) int32, zeroed by the caller; integer
+ *                atomicAdd: a workgroup of 2048 faces sends one add for the faces that carry the label of its first
+ *                face, the lanes of a wave one add per other distinct label).
+ *   hn_mesh_keep vkeep[v] = keep_comp[labels[v]] != 0, fkeep[f] = keep_comp[labels[first vertex of f]] != 0 as int32 0 / 1
+ *                (keep_comp: V bytes indexed by label); a face with an id outside [0, V) is dropped.
+ *   hn_mesh_compact  vscan / fscan = the inclusive scans (int32) of vkeep / fkeep, n_*_out their last entries:
+ *                vertex_index[vscan[v] - 1] = v for a kept vertex; a kept face goes to row fscan[f] - 1 with every id
+ *                replaced by vscan[id] - 1.  Relative orders are kept; no atomics.
+ *   hn_gather_rows   dst[r] = src[index[r]] for r < n_rows, rows of row_bytes (<= 65536) bytes, index int32 in [0, n_src)
+ *                (an index outside gives a zero row).
+ *   hn_vertex_viewdirs  out[r] (count, 3) fp32 = u / |u| at vertex i = min(start + r, V - 1) (rows past the mesh, the
+ *                padding of a last chunk, repeat the last vertex): u = -normals[i] when cam_host == NULL, else
+ *                vertices[i] - cam_host[0..2] (HOST array); |u| = sqrt((ux*ux + uy*uy) + uz*uz), every operation fp32,
+ *                unfused; |u| = 0 or NaN gives (0, 0, 1).
+ * Status: -2 for every refused argument (a NULL pointer that must not be, a negative count, F or V above 2^31 - 1,
+ * round < 1, start outside the mesh, count <= 0, n_*_out above its input), before any launch. */
+int hn_cc_init(const int32_t* faces_dev, long long n_faces, int32_t* parent_dev, long long n_vertices, int32_t* flags_dev,
+               hnStream_t stream);
+int hn_cc_round(const int32_t* faces_dev, long long n_faces, int32_t* parent_dev, long long n_vertices, int round,
+                int32_t* flags_dev, hnStream_t stream);
+int hn_cc_sizes(const int32_t* labels_dev, const int32_t* faces_dev, long long n_faces, long long n_vertices,
+                int32_t* sizes_dev, int32_t* flags_dev, hnStream_t stream);
+int hn_mesh_keep(const int32_t* labels_dev, const int32_t* faces_dev, const uint8_t* keep_comp_dev, long long n_vertices,
+                 long long n_faces, int32_t* vkeep_dev, int32_t* fkeep_dev, hnStream_t stream);
+int hn_mesh_compact(const int32_t* faces_dev, const int32_t* vscan_dev, const int32_t* fscan_dev, long long n_vertices,
+                    long long n_faces, long long n_vertices_out, long long n_faces_out, int32_t* vertex_index_dev,
+                    int32_t* faces_out_dev, hnStream_t stream);
+int hn_gather_rows(const void* src_dev, long long n_src, const int32_t* index_dev, long long n_rows, long long row_bytes,
+                   void* dst_dev, hnStream_t stream);
+int hn_vertex_viewdirs(const float* vertices_dev, const float* normals_dev, long long n_vertices, long long start,
+                       long long count, const float* cam_host, float* out_dev, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *

@@ -13,7 +13,18 @@ time per pass.  `bytes` is what each isosurface pass must move (N lattice points
   hn_iso_vertices   1 N read + 28 N written (edge slots) + 24 V written (positions, normals)
   hn_iso_faces      count: 4 N read;  emit: 4 N read + 12 F gathered from the slots + 12 F written
 and `floor_ms` is those bytes over the HBM rate given with --hbm-tbs (default 8.0, the MI355X's HBM3E peak; a float4 copy
-reaches about 6.3)."""
+reaches about 6.3).
+
+Then, on that mesh, the post-processing stages, timed the same way (V' / F' = what keep_largest=1 leaves, R = rounds):
+  mesh_components   hn_cc_init 12 F read + 4 V written; per round hook 12 F read + 12 F of parents gathered, jump 4 V
+                    read + 4 V gathered: 12 F + 4 V + R (24 F + 8 V); `rounds` counts the last one, which changes nothing
+  component_sizes   12 F read + 4 F of labels gathered + 4 V zeroed
+  filter_mesh(keep_largest=1), whole call (labelling and sizes included) and, as `filter_rest`, what it adds to them:
+                    keep 4 V + 12 F read, 4 V + 4 F written; two scans 8 V + 8 F; compact 4 V + 16 F read, 4 V' + 12 F'
+                    written, 12 F' gathered; vertices and normals 2 x (12 V' gathered + 12 V' written)
+  vertex_colors(view='normal')   12 V normals + 12 V positions read, 3 V of uint8 written (the directions and the float
+                    colours live one chunk at a time); its time is the level program's, so `points_per_s` is the figure to
+                    hold against density_grid's."""
 import argparse
 import json
 import os
@@ -60,6 +71,7 @@ def main():
     import hypernerf_torch_amd as HN
     from gpu_common import EMB, load_hash
     from hypernerf_torch_amd import _lib as L
+    from hypernerf_torch_amd import functional as FN
     from hypernerf_torch_amd.hypernerf.models import NerfModel
     if not torch.cuda.is_available():
         raise SystemExit("mesh_bench.py measures on the GPU; none is visible")
@@ -83,10 +95,35 @@ def main():
             if name in passes:
                 passes[name]["bytes"] = b
                 passes[name]["floor_ms"] = b / (a.hbm_tbs * 1e12) * 1e3
-        rows.append({"resolution": res, "points": n, "density_grid_ms": grid_ms, "points_per_s": n / grid_ms * 1e3,
-                     "extract_isosurface_ms": iso_ms, "vertices": v, "faces": f, "iso": iso,
-                     "isosurface_passes": passes, "density_grid_launches": query})
-        del grid, mesh
+        row = {"resolution": res, "points": n, "density_grid_ms": grid_ms, "points_per_s": n / grid_ms * 1e3,
+               "extract_isosurface_ms": iso_ms, "vertices": v, "faces": f, "iso": iso,
+               "isosurface_passes": passes, "density_grid_launches": query}
+        del grid
+        floor = lambda b: b / (a.hbm_tbs * 1e12) * 1e3
+        label_ms, (labels, rounds) = timed(lambda: FN.mesh_components(mesh["faces"], v, return_rounds=True), a.repeats)
+        sizes_ms, sizes = timed(lambda: HN.component_sizes(labels, mesh["faces"]), a.repeats)
+        filter_ms, kept = timed(lambda: HN.filter_mesh(mesh, keep_largest=1), a.repeats)
+        v1, f1 = int(kept["vertices"].shape[0]), int(kept["faces"].shape[0])
+        stages = per_launch(lambda: HN.filter_mesh(mesh, keep_largest=1))
+        label_b = 12 * f + 4 * v + rounds * (24 * f + 8 * v)
+        sizes_b = 16 * f + 4 * v
+        rest_b = (8 * v + 16 * f) + 8 * (v + f) + (4 * v + 16 * f + 4 * v1 + 24 * f1) + 48 * v1
+        row["mesh_components"] = {"ms": label_ms, "rounds": rounds, "cap": v + 1, "bytes": label_b, "floor_ms": floor(label_b),
+                                  "components": int((sizes > 0).sum())}
+        row["component_sizes"] = {"ms": sizes_ms, "bytes": sizes_b, "floor_ms": floor(sizes_b)}
+        row["filter_mesh_keep_largest_1"] = {"ms": filter_ms, "vertices": v1, "faces": f1, "launches": stages,
+                                             "filter_rest": {"ms": filter_ms - label_ms - sizes_ms, "bytes": rest_b,
+                                                             "floor_ms": floor(rest_b)},
+                                             "fraction_of_density_grid": filter_ms / grid_ms}
+        del kept, labels, sizes
+        color_ms, colors = timed(lambda: HN.vertex_colors(m, mesh["vertices"], mesh["normals"], 7, chunk=a.chunk), a.repeats)
+        color_b = 27 * v
+        row["vertex_colors_normal"] = {"ms": color_ms, "points_per_s": v / color_ms * 1e3, "bytes": color_b,
+                                       "floor_ms": floor(color_b),
+                                       "launches": per_launch(lambda: HN.vertex_colors(m, mesh["vertices"], mesh["normals"], 7,
+                                                                                       chunk=a.chunk))}
+        rows.append(row)
+        del mesh, colors
     print(json.dumps({"tool": "mesh_bench", "precision": a.precision, "chunk": a.chunk, "repeats": a.repeats,
                       "hbm_tbs": a.hbm_tbs, "build": L.build_id(),
                       "workload": "NerfModel use_warp bendy_sheet nerf_embed+alpha_cond (config 2), fine level", "results": rows}))
