@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -26,6 +27,12 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "hn_kernels.h")
 BUILD_MACROS = ("HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT")     # build-time tuning knobs (A/B experiments)
 
 HN_MODE_F32, HN_MODE_BF16, HN_MODE_BF16_S8 = 0, 1, 2
+
+
+class HnError(RuntimeError):
+    pass
+
+
 BUILD_CONFIG_KEYS = ("WGRAD_STAGES", "WGRAD_MAXSLOT", "WGRAD_BIAS_MFMA", "CHUNK_UNITS", "WGRAD_BLOCK", "WSTREAM_ASYM",
                      "BF16_WAVES", "WGRAD_AUX")
 
@@ -35,7 +42,6 @@ def _read_build_config(path: str):
     Read from the marker string the library carries (`hn_build_config_text`) WITHOUT dlopen-ing it: this runs at import
     time, and a library that was dlopen-ed once stays mapped under its path — a rebuild that follows (build(force=True))
     would then never be seen by load().  load() cross-checks the text against hn_build_config() of the mapped code."""
-    import re
     try:
         with open(path, "rb") as f:
             blob = f.read()
@@ -170,57 +176,38 @@ class HnAdamFuse(C.Structure):
                 ("n_rest", C.c_int32), ("zero_grad", C.c_int32)]
 
 
-EXPORTS = ["hn_version", "hn_abi_sizes", "hn_build_config", "hn_mlp_wgrad_reduce_adam", "hn_render_prologue", "hn_pack_units", "hn_pack_units_multi", "hn_mlp_forward", "hn_mlp_backward", "hn_mlp_wgrad",
-           "hn_mlp_wgrad_batched", "hn_mlp_wgrad_batched_t", "hn_mlp_wgrad_reduce", "hn_mlp_workspace_bytes",
-           "hn_sample_along_rays", "hn_sample_legacy", "hn_posenc", "hn_composite_forward", "hn_composite_backward", "hn_sample_pdf", "hn_sample_pdf_split", "hn_composite_sample_pdf",
-           "hn_embed_gather", "hn_embed_backward", "hn_se3_apply_forward", "hn_se3_apply_backward", "hn_se3_warp_forward", "hn_se3_warp_backward", "hn_generate_rays", "hn_ray_batch", "hn_ray_batch_rgba", "hn_generate_rays_nerfies", "hn_ray_batch_nerfies", "hn_blend_white_u8", "hn_premultiply_u8", "hn_resample_u8", "hn_adam_step", "hn_sgd_step", "hn_radam_step",
-           "hn_grad_norm", "hn_grad_scale",
-           "hn_mse_loss_forward", "hn_mse_loss_backward", "hn_mse_loss_forward_grad",
-           "hn_ssim_workspace_bytes", "hn_ssim_forward", "hn_ssim_backward", "hn_msssim_workspace_bytes", "hn_msssim_forward",
-           "hn_grid_points", "hn_density_activate", "hn_iso_mark", "hn_iso_vertices", "hn_iso_faces",
-           "hn_cc_init", "hn_cc_round", "hn_cc_sizes", "hn_mesh_keep", "hn_mesh_compact", "hn_gather_rows",
-           "hn_vertex_viewdirs",
-           "hn_bg_sample", "hn_bg_loss_forward", "hn_bg_loss_forward_grad", "hn_bg_loss_backward",
-           "hn_depth_index", "hn_random_fill",
-           "hn_probe_mfma", "hn_calib_mfma", "hn_calib_stream", "hn_calib_stream_pattern", "hn_calib_ring"]
+_SCALARS = {"int": C.c_int, "float": C.c_float, "int64_t": C.c_int64, "long long": C.c_longlong}
 
-# argument types of the entry points that declare them (the others are called with ctypes values built at the call site)
-ARGTYPES = {
-    "hn_msssim_workspace_bytes": [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)],
-    "hn_msssim_forward": [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int,
-                          C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                          C.c_void_p],
-    "hn_grid_points": [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p],
-    "hn_density_activate": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p,
-                            C.c_void_p],
-    "hn_iso_mark": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_iso_vertices": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p,
-                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_iso_faces": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                     C.c_void_p],
-    "hn_cc_init": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p],
-    "hn_cc_round": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p],
-    "hn_cc_sizes": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_mesh_keep": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_mesh_compact": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong,
-                        C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_gather_rows": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p],
-    "hn_vertex_viewdirs": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_float),
-                           C.c_void_p, C.c_void_p],
-    "hn_bg_sample": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p,
-                     C.c_void_p, C.c_void_p],
-    "hn_bg_loss_forward": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p],
-    "hn_bg_loss_forward_grad": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_bg_loss_backward": [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_grad_norm": [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p],
-    "hn_grad_scale": [C.c_void_p, C.c_longlong, C.c_float, C.c_float, C.c_void_p, C.c_void_p],
-}
+
+def parse_prototypes(text: str) -> dict:
+    """{entry point: argtypes}, in declaration order, of every `int hn_*(...);` prototype in `text`.  Not a C parser: it
+    knows the parameter shapes include/hn_kernels.h uses (pointers and hnStream_t -> c_void_p, the four scalar kinds, a
+    `(void)` list) and raises on anything else instead of guessing."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    out = {}
+    for start in re.finditer(r"^int (hn_\w+)\(", text, flags=re.M):
+        name, rest = start.group(1), re.compile(r"([^()]*)\);").match(text, start.end())
+        if rest is None:
+            raise HnError(f"{name}: the prototype is not a plain parameter list closed by ');'")
+        params = rest.group(1)
+        out[name] = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            ctype = " ".join(param.split()[:-1])          # drop the parameter's name
+            if "*" in param or ctype == "hnStream_t":
+                out[name].append(C.c_void_p)
+            elif ctype in _SCALARS:
+                out[name].append(_SCALARS[ctype])
+            else:
+                raise HnError(f"{name}: parameter '{' '.join(param.split())}' has a type the binding does not know")
+    return out
+
+
+# names and signatures of the entry points come from the header the library is compiled against: nothing to mirror here
+with open(HEADER) as _f:
+    ARGTYPES = parse_prototypes(_f.read())
+EXPORTS = list(ARGTYPES)
 
 _lib = None
-
-
-class HnError(RuntimeError):
-    pass
 
 
 def hipcc_path() -> str:
@@ -294,8 +281,7 @@ def load():
         if not hasattr(lib, name):
             raise HnError(f"{LIB_PATH} does not export {name}")
         getattr(lib, name).restype = C.c_int
-        if name in ARGTYPES:
-            getattr(lib, name).argtypes = ARGTYPES[name]
+        getattr(lib, name).argtypes = ARGTYPES[name]
     # the host tables in use were cut for the mirrors above: a library built with other knobs must not run under them
     # (e.g. job stages cut for another ring depth or LDS-DMA slot count: garbage gradients, no error)
     buf = (C.c_int32 * len(BUILD_CONFIG_KEYS))()
@@ -395,7 +381,7 @@ def require_gpu(*tensors):
 
 
 def ptr(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
+    return None if t is None else t.data_ptr()
 
 
 def to_device_bytes(arr: np.ndarray, device) -> torch.Tensor:

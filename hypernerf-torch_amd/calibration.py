@@ -6,7 +6,6 @@ can be compared with a line from another box (value / probe), one that does not 
 nothing here is on the render path."""
 from __future__ import annotations
 
-import ctypes as C
 import glob
 import os
 import threading
@@ -32,7 +31,7 @@ def mfma_probe(device, target_ms: float = 50.0) -> Dict[str, float]:
 
     def run(iters: int):
         t = torch.zeros(16, dtype=torch.int64, device=device)
-        L.launch("hn_calib_mfma", C.c_int(iters), L.ptr(sink), L.ptr(t), L.stream_handle())
+        L.launch("hn_calib_mfma", iters, L.ptr(sink), L.ptr(t), L.stream_handle())
         v = _ticks(t)
         return v[4] * L.TIMELINE_TICK_S, v[8], v[9]
     run(2000)                                        # wake the clocks
@@ -53,7 +52,7 @@ def stream_probe(device, gib: float = 4.0, target_ms: float = 40.0, pattern: int
     sink = torch.zeros(4, dtype=torch.float32, device=device)
     t = torch.zeros(16, dtype=torch.int64, device=device)
     def go():
-        L.launch("hn_calib_stream_pattern", L.ptr(buf), C.c_longlong(n), C.c_int(pattern), L.ptr(sink), L.ptr(t),
+        L.launch("hn_calib_stream_pattern", L.ptr(buf), n, pattern, L.ptr(sink), L.ptr(t),
                  L.stream_handle())
     go()
     first = _ticks(t)[4] * L.TIMELINE_TICK_S

@@ -203,8 +203,8 @@ class _ProgramFn(torch.autograd.Function):
                     width = shp[-1]
                     n_rays = ctx.n_points // ctx.spr
                     rows = sum_samples(dsrc, gather_cols, n_rays, ctx.spr, width)
-                    L.launch("hn_embed_backward", L.ptr(rows), C.c_int(width), C.c_int(0), L.ptr(ctx.flat_srcs[gs][2]),
-                             C.c_int(n_rays), C.c_int(1), C.c_int(width), C.c_int(shp[0]), L.ptr(d_table),
+                    L.launch("hn_embed_backward", L.ptr(rows), width, 0, L.ptr(ctx.flat_srcs[gs][2]), n_rays, 1, width,
+                             shp[0], L.ptr(d_table),
                              L.stream_handle())
                 src_grads.append(table_ret)
                 continue
@@ -411,8 +411,8 @@ def sum_samples(d_points: torch.Tensor, cols: Dict[int, int], n_rays: int, n_sam
             j += 1
         c0, s0, run = items[i][0], items[i][1], j - i + 1
         tmp = torch.zeros(n_rays, run, dtype=torch.float32, device=d_points.device)
-        L.launch("hn_embed_backward", L.ptr(d_points), C.c_int(d_points.shape[1]), C.c_int(s0), L.ptr(idx),
-                 C.c_int(n_rays), C.c_int(n_samples), C.c_int(run), C.c_int(n_rays), L.ptr(tmp), L.stream_handle())
+        L.launch("hn_embed_backward", L.ptr(d_points), d_points.shape[1], s0, L.ptr(idx), n_rays, n_samples, run, n_rays,
+                 L.ptr(tmp), L.stream_handle())
         if run == width:
             return tmp
         if out is None:
@@ -433,8 +433,8 @@ class _EmbedFn(torch.autograd.Function):
         idx = idx.reshape(-1).to(torch.int64).contiguous()
         n, dim = idx.numel(), table.shape[1]
         out = torch.empty(n, dim, dtype=torch.float32, device=table.device)
-        L.launch("hn_embed_gather", L.ptr(table.detach().contiguous()), L.ptr(idx), C.c_int(n), C.c_int(dim),
-                                    C.c_int(table.shape[0]), L.ptr(out), L.stream_handle())
+        L.launch("hn_embed_gather", L.ptr(table.detach().contiguous()), L.ptr(idx), n, dim, table.shape[0], L.ptr(out),
+                 L.stream_handle())
         ctx.idx, ctx.shape, ctx.table = idx, table.shape, table
         return out
 
@@ -448,8 +448,8 @@ class _EmbedFn(torch.autograd.Function):
         else:
             d_table = ret = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
         n, dim = g.shape
-        L.launch("hn_embed_backward", L.ptr(g), C.c_int(dim), C.c_int(0), L.ptr(ctx.idx), C.c_int(n), C.c_int(1),
-                                      C.c_int(dim), C.c_int(ctx.shape[0]), L.ptr(d_table), L.stream_handle())
+        L.launch("hn_embed_backward", L.ptr(g), dim, 0, L.ptr(ctx.idx), n, 1, dim, ctx.shape[0], L.ptr(d_table),
+                 L.stream_handle())
         return ret, None
 
 
@@ -475,8 +475,8 @@ def _scatter_embed_grad(tag, d_points, cols, n_rays, n_samples, width) -> bool:
         return False
     if any(c != k or s != items[0][1] + k for k, (c, s) in enumerate(items)):
         return False
-    L.launch("hn_embed_backward", L.ptr(d_points), C.c_int(d_points.shape[1]), C.c_int(items[0][1]), L.ptr(idx),
-             C.c_int(n_rays), C.c_int(n_samples), C.c_int(width), C.c_int(table.shape[0]), L.ptr(table.grad),
+    L.launch("hn_embed_backward", L.ptr(d_points), d_points.shape[1], items[0][1], L.ptr(idx), n_rays, n_samples, width,
+             table.shape[0], L.ptr(table.grad),
              L.stream_handle())
     return True
 
@@ -497,10 +497,8 @@ def sample_along_rays(origins, directions, lower, upper, t_rand, scale: float = 
     lower = lower.contiguous()
     upper = upper.contiguous() if upper is not None else None
     t_rand = t_rand.contiguous() if t_rand is not None else None
-    L.launch("hn_sample_along_rays", L.ptr(origins), L.ptr(directions), C.c_int(origins.stride(0)), L.ptr(lower),
-                                     L.ptr(upper), C.c_int(1 if lower.dim() == 2 else 0), L.ptr(t_rand),
-                                     C.c_float(scale), C.c_int(b), C.c_int(n), L.ptr(z), L.ptr(pts),
-                                     L.stream_handle())
+    L.launch("hn_sample_along_rays", L.ptr(origins), L.ptr(directions), origins.stride(0), L.ptr(lower), L.ptr(upper),
+             1 if lower.dim() == 2 else 0, L.ptr(t_rand), scale, b, n, L.ptr(z), L.ptr(pts), L.stream_handle())
     return z, pts
 
 
@@ -540,7 +538,7 @@ def sample_pdf(weights, z, u, origins=None, directions=None, want_points=True, b
     if bins is None:
         b, nc = z.shape
         nb = nc - 2
-        w_ptr = C.c_void_p(weights.data_ptr() + 4)
+        w_ptr = weights.data_ptr() + 4
     else:
         b, nb = weights.shape
         bins = bins.detach().contiguous()
@@ -561,15 +559,14 @@ def sample_pdf(weights, z, u, origins=None, directions=None, want_points=True, b
             raise L.HnError("sample_pdf(split=True) needs the merge (z) and the rays (origins, directions)")
         perm = torch.empty(b, nc + nf, dtype=torch.int32, device=dev)
         pts_new = torch.empty(b, nf, 3, dtype=torch.float32, device=dev)
-        L.launch("hn_sample_pdf_split", w_ptr, C.c_int(weights.stride(0)), L.ptr(bins), C.c_int(nb), L.ptr(z), C.c_int(nc),
-                 L.ptr(u.contiguous()), L.ptr(origins), L.ptr(directions), C.c_int(origins.stride(0)), C.c_int(b),
-                 C.c_int(nf), L.ptr(z_all), L.ptr(pts), L.ptr(inds), L.ptr(zs), L.ptr(perm), L.ptr(pts_new),
-                 L.stream_handle())
+        L.launch("hn_sample_pdf_split", w_ptr, weights.stride(0), L.ptr(bins), nb, L.ptr(z), nc, L.ptr(u.contiguous()),
+                 L.ptr(origins), L.ptr(directions), origins.stride(0), b, nf, L.ptr(z_all), L.ptr(pts), L.ptr(inds),
+                 L.ptr(zs), L.ptr(perm), L.ptr(pts_new), L.stream_handle())
         return z_all, pts, inds, zs, perm, pts_new
-    L.launch("hn_sample_pdf", w_ptr, C.c_int(weights.stride(0)), L.ptr(bins), C.c_int(nb),
-                              L.ptr(z if (do_merge or bins is None) else None), C.c_int(nc), L.ptr(u.contiguous()),
+    L.launch("hn_sample_pdf", w_ptr, weights.stride(0), L.ptr(bins), nb,
+                              L.ptr(z if (do_merge or bins is None) else None), nc, L.ptr(u.contiguous()),
                               L.ptr(origins if want_points else None), L.ptr(directions if want_points else None),
-                              C.c_int(origins.stride(0) if want_points else 0), C.c_int(b), C.c_int(nf),
+                              origins.stride(0) if want_points else 0, b, nf,
                               L.ptr(z_all), L.ptr(pts), L.ptr(inds), L.ptr(zs), L.stream_handle())
     return z_all, pts, inds, zs
 
@@ -627,7 +624,7 @@ def random_draws(specs: Sequence[Tuple[Tuple[int, ...], str]], device) -> List[t
     device = torch.device(device)
     st = _draw_state(device)
     outs, arr = _draw_table(specs, device)
-    L.launch("hn_random_fill", arr, C.c_int(len(specs)), L.ptr(st), L.stream_handle())
+    L.launch("hn_random_fill", arr, len(specs), L.ptr(st), L.stream_handle())
     return outs
 
 
@@ -674,7 +671,7 @@ def render_prologue(device, mode: int, pack_groups, specs: Sequence[Tuple[Tuple[
         tag = "+".join(r.prog.name for r, *_ in grp)
     else:
         m, jobs, grp, tag = mode, None, [], ""
-    L.launch("hn_render_prologue", C.c_int(m), jobs, C.c_int(len(grp)), arr if specs else None, C.c_int(len(specs)),
+    L.launch("hn_render_prologue", m, jobs, len(grp), arr if specs else None, len(specs),
              L.ptr(st), C.byref(p), L.stream_handle(), tag=tag)
     if grp:
         _M.mark_packed(grp)
@@ -762,8 +759,8 @@ class _CompositeFn(torch.autograd.Function):
             if then_pdf.get("split"):
                 perm_o = torch.empty(b, s + nf, dtype=torch.int32, device=dev)
                 pts_new = torch.empty(b, nf, 3, dtype=torch.float32, device=dev)
-            L.launch("hn_composite_sample_pdf", C.byref(a), L.ptr(u_c), L.ptr(o_), L.ptr(d_), C.c_int(o_.stride(0)),
-                     C.c_int(nf), L.ptr(z_all), L.ptr(pts_all), L.ptr(inds), L.ptr(zs), L.ptr(perm_o), L.ptr(pts_new),
+            L.launch("hn_composite_sample_pdf", C.byref(a), L.ptr(u_c), L.ptr(o_), L.ptr(d_), o_.stride(0), nf, L.ptr(z_all),
+                     L.ptr(pts_all), L.ptr(inds), L.ptr(zs), L.ptr(perm_o), L.ptr(pts_new),
                      L.stream_handle())
             pdf_out = [z_all, pts_all, inds, zs] + ([perm_o, pts_new] if perm_o is not None else [])
         else:
@@ -870,11 +867,11 @@ class _MseFn(torch.autograd.Function):
             # passes: the loss of a training step IS the root); any other incoming gradient takes the backward kernel
             dc = torch.empty_like(c)
             df = torch.empty_like(f) if f is not None else None
-            L.launch("hn_mse_loss_forward_grad", L.ptr(c), L.ptr(f), L.ptr(t), C.c_int64(c.numel()), L.ptr(loss), L.ptr(dc),
+            L.launch("hn_mse_loss_forward_grad", L.ptr(c), L.ptr(f), L.ptr(t), c.numel(), L.ptr(loss), L.ptr(dc),
                      L.ptr(df), L.stream_handle())
             ctx.unit = (dc, df)
         else:
-            L.launch("hn_mse_loss_forward", L.ptr(c), L.ptr(f), L.ptr(t), C.c_int64(c.numel()), L.ptr(loss),
+            L.launch("hn_mse_loss_forward", L.ptr(c), L.ptr(f), L.ptr(t), c.numel(), L.ptr(loss),
                      L.stream_handle())
         ctx.saved = (c, f, t)
         return loss
@@ -888,7 +885,7 @@ class _MseFn(torch.autograd.Function):
         g = g.contiguous().float()
         dc = torch.empty_like(c)
         df = torch.empty_like(f) if f is not None else None
-        L.launch("hn_mse_loss_backward", L.ptr(c), L.ptr(f), L.ptr(t), C.c_int64(c.numel()), L.ptr(g), L.ptr(dc),
+        L.launch("hn_mse_loss_backward", L.ptr(c), L.ptr(f), L.ptr(t), c.numel(), L.ptr(g), L.ptr(dc),
                  L.ptr(df), L.stream_handle())
         return dc, df, None
 
@@ -947,8 +944,8 @@ def bg_sample(points: torch.Tensor, ids: torch.Tensor, u: torch.Tensor, nrm: tor
     p, i, u, nrm = points.detach().contiguous(), ids.contiguous(), u.detach().contiguous(), nrm.detach().contiguous()
     out_points = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     out_ids = torch.empty(n, dtype=torch.int64, device=p.device)
-    L.launch("hn_bg_sample", L.ptr(p), C.c_int(m), L.ptr(i), C.c_int(k), L.ptr(u), L.ptr(nrm), C.c_int(n),
-             C.c_float(noise_std), L.ptr(out_points), L.ptr(out_ids), L.stream_handle())
+    L.launch("hn_bg_sample", L.ptr(p), m, L.ptr(i), k, L.ptr(u), L.ptr(nrm), n, noise_std, L.ptr(out_points),
+             L.ptr(out_ids), L.stream_handle())
     return out_points, out_ids
 
 
@@ -965,11 +962,11 @@ class _BgLossFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # as _MseFn: the gradient for a root gradient of exactly 1 comes out of the forward launch
             dw = torch.empty_like(w)
-            L.launch("hn_bg_loss_forward_grad", L.ptr(w), L.ptr(p), C.c_int(n), C.c_float(scale), L.ptr(loss), L.ptr(dw),
+            L.launch("hn_bg_loss_forward_grad", L.ptr(w), L.ptr(p), n, scale, L.ptr(loss), L.ptr(dw),
                      L.stream_handle())
             ctx.unit = dw
         else:
-            L.launch("hn_bg_loss_forward", L.ptr(w), L.ptr(p), C.c_int(n), C.c_float(scale), L.ptr(loss),
+            L.launch("hn_bg_loss_forward", L.ptr(w), L.ptr(p), n, scale, L.ptr(loss),
                      L.stream_handle())
         ctx.saved = (w, p, n, scale)
         return loss
@@ -982,7 +979,7 @@ class _BgLossFn(torch.autograd.Function):
             return ctx.unit, None, None
         g = g.contiguous().float()
         dw = torch.empty_like(w)
-        L.launch("hn_bg_loss_backward", L.ptr(w), L.ptr(p), C.c_int(n), C.c_float(scale), L.ptr(g), L.ptr(dw),
+        L.launch("hn_bg_loss_backward", L.ptr(w), L.ptr(p), n, scale, L.ptr(g), L.ptr(dw),
                  L.stream_handle())
         return dw, None, None
 
@@ -1054,7 +1051,7 @@ class _SsimFn(torch.autograd.Function):
         x, y = pred.detach(), gt.detach()
         n, c, h, w = x.shape
         args = (L.ptr(x), (C.c_int64 * 4)(*x.stride()), L.ptr(y), (C.c_int64 * 4)(*y.stride()), n, c, h, w,
-                _ssim_window_host(window_size), window_size, C.c_float(c1), C.c_float(c2), C.c_float(eps))
+                _ssim_window_host(window_size), window_size, c1, c2, eps)
         if want_map:
             out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
             L.launch("hn_ssim_forward", *args, L.ptr(out), None, None, L.stream_handle())
@@ -1082,7 +1079,7 @@ class _SsimFn(torch.autograd.Function):
         d_first = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
         d_second = torch.empty_like(d_first) if (need_x and need_y) else None
         L.launch("hn_ssim_backward", L.ptr(x), (C.c_int64 * 4)(*x.stride()), L.ptr(y), (C.c_int64 * 4)(*y.stride()),
-                 n, c, h, w, _ssim_window_host(window_size), window_size, C.c_float(c1), C.c_float(c2), C.c_float(eps),
+                 n, c, h, w, _ssim_window_host(window_size), window_size, c1, c2, eps,
                  None if want_map else L.ptr(g), L.ptr(g) if want_map else None, L.ptr(d_first), L.ptr(d_second),
                  L.stream_handle())
         if need_x:
@@ -1181,9 +1178,9 @@ def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) ->
     taps, sizes, ws_floats = _msssim_plan(n, c, h, w)
     ws = torch.empty(ws_floats, dtype=torch.float32, device=x.device)
     out = torch.empty((n, MSSSIM_LEVELS, 2), dtype=torch.float32, device=x.device)
-    L.launch("hn_msssim_forward", x.data_ptr(), (C.c_int64 * 4)(*x.stride()), y.data_ptr(), (C.c_int64 * 4)(*y.stride()),
-             n, c, h, w, taps, sizes, (0.01 * max_val) ** 2, (0.03 * max_val) ** 2, out.data_ptr(), ws.data_ptr(),
-             torch.cuda.current_stream().cuda_stream)
+    L.launch("hn_msssim_forward", L.ptr(x), (C.c_int64 * 4)(*x.stride()), L.ptr(y), (C.c_int64 * 4)(*y.stride()),
+             n, c, h, w, taps, sizes, (0.01 * max_val) ** 2, (0.03 * max_val) ** 2, L.ptr(out), L.ptr(ws),
+             L.stream_handle())
     return out
 
 
@@ -1230,8 +1227,8 @@ def grid_points(shape, bounds, start: int, count: int, device) -> torch.Tensor:
     L.load()
     out = torch.empty((count, 3), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        L.launch("hn_grid_points", nx, ny, nz, (C.c_float * 6)(*bounds), start, count, out.data_ptr(),
-                 torch.cuda.current_stream().cuda_stream)
+        L.launch("hn_grid_points", nx, ny, nz, (C.c_float * 6)(*bounds), start, count, L.ptr(out),
+                 L.stream_handle())
     return out
 
 
@@ -1253,8 +1250,8 @@ def density_activate(raw: torch.Tensor, points: torch.Tensor, render_opts=None) 
                 raise ValueError(f"density_activate: points {tuple(points.shape)} do not match raw {tuple(raw.shape)}")
     out = torch.empty_like(raw)
     if raw.numel():
-        L.launch("hn_density_activate", raw.data_ptr(), points.data_ptr() if box is not None else None, raw.numel(),
-                 has_dust, dust, box, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        L.launch("hn_density_activate", L.ptr(raw), L.ptr(points) if box is not None else None, raw.numel(),
+                 has_dust, dust, box, L.ptr(out), L.stream_handle())
     return out
 
 
@@ -1284,11 +1281,11 @@ def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torc
     n = nx * ny * nz
     iso = float(iso)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = L.stream_handle()
         # pass A: marks and per-workgroup counts; the scan of the counts is torch's
         mask = torch.empty(n, dtype=torch.uint8, device=dev)
         counts = torch.empty((n + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
-        L.launch("hn_iso_mark", f.data_ptr(), nx, ny, nz, iso, mask.data_ptr(), counts.data_ptr(), stream)
+        L.launch("hn_iso_mark", L.ptr(f), nx, ny, nz, iso, L.ptr(mask), L.ptr(counts), stream)
         ends = torch.cumsum(counts, 0, dtype=torch.int64)
         n_vertices = int(ends[-1])
         if n_vertices == 0:
@@ -1298,12 +1295,12 @@ def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torc
         normals = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
         slots = torch.empty(7 * n, dtype=torch.int32, device=dev)
         offsets = ends - counts
-        L.launch("hn_iso_vertices", f.data_ptr(), nx, ny, nz, (C.c_float * 6)(*bounds), iso, mask.data_ptr(),
-                 offsets.data_ptr(), vertices.data_ptr(), normals.data_ptr(), slots.data_ptr(), stream)
+        L.launch("hn_iso_vertices", L.ptr(f), nx, ny, nz, (C.c_float * 6)(*bounds), iso, L.ptr(mask),
+                 L.ptr(offsets), L.ptr(vertices), L.ptr(normals), L.ptr(slots), stream)
         # pass C: count, scan, emit
         n_cells = (nx - 1) * (ny - 1) * (nz - 1)
         fcounts = torch.empty((n_cells + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
-        L.launch("hn_iso_faces", f.data_ptr(), nx, ny, nz, iso, None, None, fcounts.data_ptr(), None, stream)
+        L.launch("hn_iso_faces", L.ptr(f), nx, ny, nz, iso, None, None, L.ptr(fcounts), None, stream)
         fends = torch.cumsum(fcounts, 0, dtype=torch.int64)
         n_faces = int(fends[-1])
         if n_faces > INT32_MAX:
@@ -1311,8 +1308,8 @@ def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torc
         faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
         if n_faces:
             foffsets = fends - fcounts
-            L.launch("hn_iso_faces", f.data_ptr(), nx, ny, nz, iso, slots.data_ptr(), foffsets.data_ptr(), None,
-                     faces.data_ptr(), stream)
+            L.launch("hn_iso_faces", L.ptr(f), nx, ny, nz, iso, L.ptr(slots), L.ptr(foffsets), None,
+                     L.ptr(faces), stream)
     return {'vertices': vertices, 'normals': normals, 'faces': faces}
 
 
@@ -1353,10 +1350,10 @@ def mesh_components(faces: torch.Tensor, num_vertices: int, out: Optional[torch.
     L.load()
     cap = v + 1
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = L.stream_handle()
         flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        L.launch("hn_cc_init", faces.data_ptr() if n_faces else None, n_faces, out.data_ptr() if v else None, v,
-                 flags.data_ptr(), stream)
+        L.launch("hn_cc_init", L.ptr(faces) if n_faces else None, n_faces, L.ptr(out) if v else None, v,
+                 L.ptr(flags), stream)
         if n_faces == 0:
             return (out, rounds) if return_rounds else out
         if v == 0:
@@ -1365,7 +1362,7 @@ def mesh_components(faces: torch.Tensor, num_vertices: int, out: Optional[torch.
             rounds += 1
             if rounds > cap:
                 raise RuntimeError(f"mesh_components: no fixed point after the cap of V + 1 = {cap} rounds")
-            L.launch("hn_cc_round", faces.data_ptr(), n_faces, out.data_ptr(), v, rounds, flags.data_ptr(), stream)
+            L.launch("hn_cc_round", L.ptr(faces), n_faces, L.ptr(out), v, rounds, L.ptr(flags), stream)
             err, changed = flags.tolist()
             if err:
                 raise ValueError(f"mesh_components: faces hold a vertex id outside [0, {v})")
@@ -1388,8 +1385,8 @@ def component_sizes(labels: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
         L.load()
         with torch.cuda.device(faces.device):
             flags = torch.zeros(2, dtype=torch.int32, device=faces.device)
-            L.launch("hn_cc_sizes", labels.detach().contiguous().data_ptr(), faces.data_ptr(), faces.shape[0], v,
-                     sizes.data_ptr(), flags.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            L.launch("hn_cc_sizes", L.ptr(labels.detach().contiguous()), L.ptr(faces), faces.shape[0], v,
+                     L.ptr(sizes), L.ptr(flags), L.stream_handle())
     return sizes
 
 
@@ -1404,8 +1401,8 @@ def gather_rows(src: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
         L.load()
         row_bytes = out.numel() // n * out.element_size()
         with torch.cuda.device(src.device):
-            L.launch("hn_gather_rows", src.data_ptr(), src.shape[0], index.data_ptr(), n, row_bytes, out.data_ptr(),
-                     torch.cuda.current_stream().cuda_stream)
+            L.launch("hn_gather_rows", L.ptr(src), src.shape[0], L.ptr(index), n, row_bytes, L.ptr(out),
+                     L.stream_handle())
     return out
 
 
@@ -1422,21 +1419,21 @@ def compact_mesh(faces: torch.Tensor, labels: torch.Tensor, keep_comp: torch.Ten
     L.load()
     keep_comp = keep_comp.to(torch.uint8).contiguous()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
+        stream = L.stream_handle()
         vkeep = torch.empty(v, dtype=torch.int32, device=dev)
         fkeep = torch.empty(max(n_faces, 1), dtype=torch.int32, device=dev)
         if n_faces == 0:
             fkeep.zero_()
-        L.launch("hn_mesh_keep", labels.contiguous().data_ptr(), faces.data_ptr() if n_faces else None, keep_comp.data_ptr(),
-                 v, n_faces, vkeep.data_ptr(), fkeep.data_ptr(), stream)
+        L.launch("hn_mesh_keep", L.ptr(labels.contiguous()), L.ptr(faces) if n_faces else None, L.ptr(keep_comp),
+                 v, n_faces, L.ptr(vkeep), L.ptr(fkeep), stream)
         vscan = torch.cumsum(vkeep, 0, dtype=torch.int32)
         fscan = torch.cumsum(fkeep, 0, dtype=torch.int32)
         n_v, n_f = torch.stack([vscan[-1], fscan[-1]]).tolist()
         vertex_index = torch.empty(n_v, dtype=torch.int32, device=dev)
         faces_out = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
         if n_v:
-            L.launch("hn_mesh_compact", faces.data_ptr() if n_faces else None, vscan.data_ptr(), fscan.data_ptr(), v, n_faces,
-                     n_v, n_f, vertex_index.data_ptr(), faces_out.data_ptr() if n_f else None, stream)
+            L.launch("hn_mesh_compact", L.ptr(faces) if n_faces else None, L.ptr(vscan), L.ptr(fscan), v, n_faces,
+                     n_v, n_f, L.ptr(vertex_index), L.ptr(faces_out) if n_f else None, stream)
     return vertex_index, faces_out
 
 
@@ -1458,9 +1455,9 @@ def vertex_viewdirs(vertices: torch.Tensor, normals: Optional[torch.Tensor], sta
     out = torch.empty((count, 3), dtype=torch.float32, device=ref.device)
     cam = None if camera is None else (C.c_float * 3)(*(float(x) for x in camera))
     with torch.cuda.device(ref.device):
-        L.launch("hn_vertex_viewdirs", ref.data_ptr() if camera is not None else None,
-                 ref.data_ptr() if camera is None else None, v, start, count, cam, out.data_ptr(),
-                 torch.cuda.current_stream().cuda_stream)
+        L.launch("hn_vertex_viewdirs", L.ptr(ref) if camera is not None else None,
+                 L.ptr(ref) if camera is None else None, v, start, count, cam, L.ptr(out),
+                 L.stream_handle())
     return out
 
 
@@ -1478,8 +1475,7 @@ def _generate_rays(entry: str, h: int, w: int, name: str, table: torch.Tensor, s
     t = table.detach().contiguous().float()
     cols = 9 if image_id is not None else 8
     rays = torch.empty(h * w, cols, dtype=torch.float32, device=table.device)
-    L.launch(entry, C.c_int(h), C.c_int(w), *before, L.ptr(t), *after, C.c_float(near), C.c_float(far),
-             C.c_float(float(image_id or 0)), C.c_int(cols), L.ptr(rays), L.stream_handle())
+    L.launch(entry, h, w, *before, L.ptr(t), *after, near, far, float(image_id or 0), cols, L.ptr(rays), L.stream_handle())
     return rays
 
 
@@ -1487,8 +1483,8 @@ def generate_rays(h: int, w: int, focal: float, c2w: torch.Tensor, near: float, 
                   ndc_near: float = 1.0, image_id: Optional[int] = None) -> torch.Tensor:
     """(h*w, 8|9) ray rows [o, d, near, far(, image id)] of one image, generated on the GPU
     (reference: datasets/ray_utils.py get_ray_directions / get_rays / get_ndc_rays, datasets/llff.py:244-264)."""
-    return _generate_rays("hn_generate_rays", h, w, "c2w", c2w, (3, 4), (C.c_float(focal),),
-                          (C.c_int(int(ndc)), C.c_float(ndc_near)), near, far, image_id)
+    return _generate_rays("hn_generate_rays", h, w, "c2w", c2w, (3, 4), (focal,), (int(ndc), ndc_near), near, far,
+                          image_id)
 
 
 def _ray_batch(entry: str, channels: int, table_row: tuple, before: tuple, after: tuple, perm, state, batch, h, w, table,
@@ -1508,10 +1504,9 @@ def _ray_batch(entry: str, channels: int, table_row: tuple, before: tuple, after
           and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
     if not ok:
         raise L.HnError(f"{entry[3:]}: bad shapes / dtypes")
-    L.launch(entry, L.ptr(perm), C.c_longlong(perm.numel()), L.ptr(state), C.c_int(batch),
-             C.c_longlong(px8.numel() // channels), C.c_int(h), C.c_int(w), *before, L.ptr(table),
-             L.ptr(image_ids if cols == 9 else None), *after, C.c_float(near), C.c_float(far), C.c_int(cols),
-             L.ptr(px8), L.ptr(rays), L.ptr(rgbs), L.stream_handle())
+    L.launch(entry, L.ptr(perm), perm.numel(), L.ptr(state), batch, px8.numel() // channels, h, w, *before, L.ptr(table),
+             L.ptr(image_ids if cols == 9 else None), *after, near, far, cols, L.ptr(px8), L.ptr(rays), L.ptr(rgbs),
+             L.stream_handle())
 
 
 def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float, c2w: torch.Tensor,
@@ -1523,8 +1518,8 @@ def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: in
     `state` (3 int64 words: cursor, arrival counter, error flag) is advanced by `batch` on the device: no host sync.
     A row whose position lies past the permutation, or whose index lies outside the dataset, is written as NaN and sets
     the error flag."""
-    _ray_batch("hn_ray_batch", 3, (3, 4), (C.c_float(focal),), (C.c_int(int(ndc)), C.c_float(ndc_near)), perm, state,
-               batch, h, w, c2w, rgb8, rays, rgbs, near, far, image_ids)
+    _ray_batch("hn_ray_batch", 3, (3, 4), (focal,), (int(ndc), ndc_near), perm, state, batch, h, w, c2w, rgb8, rays, rgbs,
+               near, far, image_ids)
 
 
 def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float,
@@ -1533,8 +1528,8 @@ def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, 
                    image_ids: Optional[torch.Tensor] = None) -> None:
     """`ray_batch` over an RGBA stack ((n_images, h, w, 4) uint8, hn_ray_batch_rgba): rgbs[:batch] is each pixel
     blended onto white as `blend_white_u8` computes it, in the same launch."""
-    _ray_batch("hn_ray_batch_rgba", 4, (3, 4), (C.c_float(focal),), (C.c_int(int(ndc)), C.c_float(ndc_near)), perm,
-               state, batch, h, w, c2w, rgba8, rays, rgbs, near, far, image_ids)
+    _ray_batch("hn_ray_batch_rgba", 4, (3, 4), (focal,), (int(ndc), ndc_near), perm, state, batch, h, w, c2w, rgba8, rays,
+               rgbs, near, far, image_ids)
 
 
 NERFIES_CAM_FLOATS = 24      # hn_kernels.h: orientation 9, position 3, f, aspect, skew, cx, cy, k1 k2 k3, p1 p2, 2 zeros
@@ -1572,7 +1567,7 @@ def blend_white_u8(rgba8: torch.Tensor, with_mask: bool = False):
     n = x.numel() // 4
     rgbs = torch.empty((n, 3), dtype=torch.float32, device=x.device)
     mask = torch.empty(n, dtype=torch.bool, device=x.device) if with_mask else None
-    L.launch("hn_blend_white_u8", L.ptr(x), C.c_longlong(n), L.ptr(rgbs), L.ptr(mask), L.stream_handle())
+    L.launch("hn_blend_white_u8", L.ptr(x), n, L.ptr(rgbs), L.ptr(mask), L.stream_handle())
     return (rgbs, mask) if with_mask else rgbs
 
 
@@ -1608,14 +1603,12 @@ def resize_lanczos_u8(img: torch.Tensor, size) -> torch.Tensor:
     if out_w != w:
         bounds, kk, ksize = _resample_tables(w, out_w, x.device)
         y = torch.empty((h, out_w, c), dtype=torch.uint8, device=x.device)
-        L.launch("hn_resample_u8", L.ptr(x), C.c_int(h), C.c_int(w), C.c_int(c), C.c_int(out_w), C.c_int(0),
-                 L.ptr(bounds), L.ptr(kk), C.c_int(ksize), L.ptr(y), L.stream_handle())
+        L.launch("hn_resample_u8", L.ptr(x), h, w, c, out_w, 0, L.ptr(bounds), L.ptr(kk), ksize, L.ptr(y), L.stream_handle())
         x, w = y, out_w
     if out_h != h:
         bounds, kk, ksize = _resample_tables(h, out_h, x.device)
         y = torch.empty((out_h, w, c), dtype=torch.uint8, device=x.device)
-        L.launch("hn_resample_u8", L.ptr(x), C.c_int(h), C.c_int(w), C.c_int(c), C.c_int(out_h), C.c_int(1),
-                 L.ptr(bounds), L.ptr(kk), C.c_int(ksize), L.ptr(y), L.stream_handle())
+        L.launch("hn_resample_u8", L.ptr(x), h, w, c, out_h, 1, L.ptr(bounds), L.ptr(kk), ksize, L.ptr(y), L.stream_handle())
         x = y
     return x if x is not img else x.clone()
 
@@ -1629,7 +1622,7 @@ def premultiply_u8(img: torch.Tensor, inverse: bool = False) -> torch.Tensor:
         raise L.HnError("premultiply_u8: (H, W, 4) uint8")
     x = img.contiguous()
     out = torch.empty_like(x)
-    L.launch("hn_premultiply_u8", L.ptr(x), C.c_longlong(x.numel() // 4), C.c_int(int(inverse)), L.ptr(out),
+    L.launch("hn_premultiply_u8", L.ptr(x), x.numel() // 4, int(inverse), L.ptr(out),
              L.stream_handle())
     return out
 
@@ -1661,7 +1654,7 @@ class _Se3Fn(torch.autograd.Function):
         if w_c.shape[0] != n or v_c.shape[0] != n:
             raise L.HnError("se3_apply: w, v and points must have the same number of rows")
         out = torch.empty_like(p_c)
-        L.launch("hn_se3_apply_forward", L.ptr(w_c), L.ptr(v_c), L.ptr(p_c), C.c_int(n), L.ptr(out),
+        L.launch("hn_se3_apply_forward", L.ptr(w_c), L.ptr(v_c), L.ptr(p_c), n, L.ptr(out),
                  L.stream_handle())
         ctx.saved = (w_c, v_c, p_c)
         ctx.shapes = (w.shape, v.shape, points.shape)
@@ -1676,9 +1669,8 @@ class _Se3Fn(torch.autograd.Function):
         d_w = torch.empty_like(w_c) if need[0] else None
         d_v = torch.empty_like(v_c) if need[1] else None
         d_p = torch.empty_like(p_c) if need[2] else None
-        L.launch("hn_se3_apply_backward", L.ptr(w_c), L.ptr(v_c), L.ptr(p_c), L.ptr(g), C.c_int(p_c.shape[0]),
-                 L.ptr(d_w) if d_w is not None else None, L.ptr(d_v) if d_v is not None else None,
-                 L.ptr(d_p) if d_p is not None else None, L.stream_handle())
+        L.launch("hn_se3_apply_backward", L.ptr(w_c), L.ptr(v_c), L.ptr(p_c), L.ptr(g), p_c.shape[0], L.ptr(d_w), L.ptr(d_v),
+                 L.ptr(d_p), L.stream_handle())
         sw, sv, sp = ctx.shapes
         return (d_w.view(sw) if d_w is not None else None, d_v.view(sv) if d_v is not None else None,
                 d_p.view(sp) if d_p is not None else None)
@@ -1721,10 +1713,9 @@ class _Se3WarpFn(torch.autograd.Function):
             if gidx.numel() * int(samples_per_ray) != n:
                 raise L.HnError(f"se3_warp: {gidx.numel()} ray indices x {samples_per_ray} samples != {n} points")
             warped = torch.empty(n, 3 + h, dtype=torch.float32, device=p_c.device)
-        L.launch("hn_se3_warp_forward", C.c_void_p(wv_c.data_ptr()), C.c_int(wv_c.stride(0)),
-                 C.c_void_p(wv_c.data_ptr() + 12), C.c_int(wv_c.stride(0)), L.ptr(p_c), C.c_int(p_c.stride(0)), C.c_int(n),
-                 L.ptr(xyz), L.ptr(warped), C.c_int(3 + h), L.ptr(tab), L.ptr(gidx), C.c_int(h),
-                 C.c_int(tab.shape[0] if tab is not None else 0), C.c_int(int(samples_per_ray)), L.stream_handle())
+        L.launch("hn_se3_warp_forward", L.ptr(wv_c), wv_c.stride(0), wv_c.data_ptr() + 12, wv_c.stride(0), L.ptr(p_c),
+                 p_c.stride(0), n, L.ptr(xyz), L.ptr(warped), 3 + h, L.ptr(tab), L.ptr(gidx), h,
+                 tab.shape[0] if tab is not None else 0, int(samples_per_ray), L.stream_handle())
         ctx.saved = (wv_c, p_c)
         ctx.pshape = points.shape
         ctx.rows = None if table is None else (gidx, tuple(table.shape), int(samples_per_ray))
@@ -1755,10 +1746,9 @@ class _Se3WarpFn(torch.autograd.Function):
         need_p = ctx.needs_input_grad[1]
         d_wv = torch.empty(n, 6, dtype=torch.float32, device=p_c.device)
         d_p = torch.empty(n, 3, dtype=torch.float32, device=p_c.device) if need_p else None
-        L.launch("hn_se3_warp_backward", C.c_void_p(wv_c.data_ptr()), C.c_int(wv_c.stride(0)),
-                 C.c_void_p(wv_c.data_ptr() + 12), C.c_int(wv_c.stride(0)), L.ptr(p_c), C.c_int(p_c.stride(0)),
-                 L.ptr(g), C.c_int(g.stride(0)), C.c_int(n), C.c_void_p(d_wv.data_ptr()), C.c_int(6),
-                 C.c_void_p(d_wv.data_ptr() + 12), C.c_int(6), L.ptr(d_p), L.stream_handle())
+        L.launch("hn_se3_warp_backward", L.ptr(wv_c), wv_c.stride(0), wv_c.data_ptr() + 12, wv_c.stride(0), L.ptr(p_c),
+                 p_c.stride(0), L.ptr(g), g.stride(0), n, L.ptr(d_wv), 6, d_wv.data_ptr() + 12, 6, L.ptr(d_p),
+                 L.stream_handle())
         return d_wv, (d_p.view(ctx.pshape) if d_p is not None else None), d_table, None, None
 
 
@@ -1782,8 +1772,8 @@ class _PosencFn(torch.autograd.Function):
         n, nf = xf.shape[0], freqs.numel()
         width = c * (2 * nf + (1 if identity else 0))
         out = torch.empty(n, width, dtype=torch.float32, device=x.device)
-        L.launch("hn_posenc", L.ptr(xf), C.c_int64(n), C.c_int(c), L.ptr(freqs), C.c_int(nf), C.c_int(int(identity)),
-                              C.c_int(int(jax_cos)), L.ptr(out), None, None, L.stream_handle())
+        L.launch("hn_posenc", L.ptr(xf), n, c, L.ptr(freqs), nf, int(identity), int(jax_cos), L.ptr(out), None, None,
+                 L.stream_handle())
         ctx.save_for_backward(xf, freqs)
         ctx.cfg = (identity, jax_cos, x.shape)
         return out.view(*x.shape[:-1], width)
@@ -1796,8 +1786,8 @@ class _PosencFn(torch.autograd.Function):
         n, c = xf.shape
         g = g.reshape(n, -1).contiguous()
         gx = torch.empty_like(xf)
-        L.launch("hn_posenc", L.ptr(xf), C.c_int64(n), C.c_int(c), L.ptr(freqs), C.c_int(freqs.numel()),
-                              C.c_int(int(identity)), C.c_int(int(jax_cos)), None, L.ptr(g), L.ptr(gx),
+        L.launch("hn_posenc", L.ptr(xf), n, c, L.ptr(freqs), freqs.numel(),
+                              int(identity), int(jax_cos), None, L.ptr(g), L.ptr(gx),
                               L.stream_handle())
         return gx.view(shp), None, None, None
 
@@ -1816,7 +1806,7 @@ def sample_legacy(rays, t_vals, one_minus_t, use_disp, t_rand, scale):
     z = torch.empty(b, n, dtype=torch.float32, device=rays.device)
     pts = torch.empty(b, n, 3, dtype=torch.float32, device=rays.device)
     t_rand = t_rand.contiguous() if t_rand is not None else None
-    L.launch("hn_sample_legacy", L.ptr(rays), C.c_int(rays.stride(0)), L.ptr(t_vals), L.ptr(one_minus_t),
-                                 C.c_int(int(use_disp)), L.ptr(t_rand), C.c_float(scale), C.c_int(b), C.c_int(n),
+    L.launch("hn_sample_legacy", L.ptr(rays), rays.stride(0), L.ptr(t_vals), L.ptr(one_minus_t),
+                                 int(use_disp), L.ptr(t_rand), scale, b, n,
                                  L.ptr(z), L.ptr(pts), L.stream_handle())
     return z, pts

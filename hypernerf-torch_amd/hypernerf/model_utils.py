@@ -120,7 +120,6 @@ def posenc(x, min_deg, max_deg, use_identity=False, alpha=None):
 def _depth_index(weights, z_vals, depth_threshold, want_index, want_depth, want_mask):
     L.require_gpu(weights)
     L.load()
-    import ctypes as C
     shp = weights.shape
     s = shp[-1]
     w = weights.detach().reshape(-1, s).contiguous().float()
@@ -129,7 +128,7 @@ def _depth_index(weights, z_vals, depth_threshold, want_index, want_depth, want_
     idx = torch.empty(b, dtype=torch.int64, device=w.device) if want_index else None
     dep = torch.empty(b, dtype=torch.float32, device=w.device) if want_depth else None
     msk = torch.empty(b, s, dtype=torch.float32, device=w.device) if want_mask else None
-    L.launch("hn_depth_index", L.ptr(w), L.ptr(z), C.c_int(b), C.c_int(s), C.c_float(float(depth_threshold)),
+    L.launch("hn_depth_index", L.ptr(w), L.ptr(z), b, s, float(depth_threshold),
              L.ptr(idx), L.ptr(dep), L.ptr(msk), L.stream_handle())
     return (idx.view(shp[:-1]) if idx is not None else None, dep.view(shp[:-1]) if dep is not None else None,
             msk.view(shp).to(weights.dtype) if msk is not None else None)

@@ -7,7 +7,6 @@ fused HIP launches per level: sampling -> warp-field machine -> hyper-sheet mach
 """
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import os
 from typing import Any, Callable, Dict, Mapping, Optional, Sequence
@@ -679,7 +678,7 @@ class NerfModel(nn.Module):
             if len(groups) <= 1:
                 return groups
             for m, arr, grp in groups:           # two numeric modes in one model: not the step head's business
-                L.launch("hn_pack_units_multi", C.c_int(m), arr, C.c_int(len(grp)), L.stream_handle())
+                L.launch("hn_pack_units_multi", m, arr, len(grp), L.stream_handle())
                 machine.mark_packed(grp)
             return []
         machine.pack_many([c.runner for c in calls], device, F.mode_of(self.precision), force=grad)

@@ -969,7 +969,7 @@ def _embed_struct(embeds: Sequence[dict]) -> "L.HnEmbedReduce":
 
 def _launch_embed_reduce(mode: int, embeds: Sequence[dict]):
     em = _embed_struct(embeds)
-    L.launch("hn_mlp_wgrad_reduce", C.c_int(wgrad_mode_word(mode)), None, C.c_int(0), None, None, C.c_int(0), C.byref(em),
+    L.launch("hn_mlp_wgrad_reduce", wgrad_mode_word(mode), None, 0, None, None, 0, C.byref(em),
              L.stream_handle())
 
 
@@ -1065,8 +1065,8 @@ class PendingReduce:
         self.mode, self.red, self.arr, self.n_grp, self.em, self.keep = mode, red, arr, n_grp, em, keep
 
     def plain(self):
-        L.launch("hn_mlp_wgrad_reduce", C.c_int(wgrad_mode_word(self.mode)), L.ptr(self.red[0]), C.c_int(self.red[2]),
-                 L.ptr(self.red[1]), self.arr, C.c_int(self.n_grp), C.byref(self.em) if self.em is not None else None,
+        L.launch("hn_mlp_wgrad_reduce", wgrad_mode_word(self.mode), L.ptr(self.red[0]), self.red[2],
+                 L.ptr(self.red[1]), self.arr, self.n_grp, C.byref(self.em) if self.em is not None else None,
                  L.stream_handle())
 
     def rest_table(self, grads: torch.Tensor):
@@ -1096,8 +1096,8 @@ class PendingReduce:
         return None if hit[1] < 0 else hit
 
     def fused(self, adam_struct):
-        L.launch("hn_mlp_wgrad_reduce_adam", C.c_int(wgrad_mode_word(self.mode)), L.ptr(self.red[0]), C.c_int(self.red[2]),
-                 L.ptr(self.red[1]), self.arr, C.c_int(self.n_grp), C.byref(self.em) if self.em is not None else None,
+        L.launch("hn_mlp_wgrad_reduce_adam", wgrad_mode_word(self.mode), L.ptr(self.red[0]), self.red[2],
+                 L.ptr(self.red[1]), self.arr, self.n_grp, C.byref(self.em) if self.em is not None else None,
                  C.byref(adam_struct), L.stream_handle())
 
 
@@ -1208,8 +1208,8 @@ def launch_resolved_wgrads(shares: Sequence[ResolvedWgrad]):
                         raise L.HnError("weight-gradient reduce tables: first use of this set of programs inside a stream "
                                         "capture (run one warm-up step of the same shapes first)")
                     red = cache[rkey] = _reduce_tables(grp, grp[0].stash.device)
-            L.launch("hn_mlp_wgrad_batched_t", C.c_int(wgrad_mode_word(mode)), arr, C.c_int(len(grp)), L.ptr(order),
-                     C.c_void_p(L.timeline_slot("hn_mlp_wgrad_batched", grp[0].stash.device)), L.stream_handle(),
+            L.launch("hn_mlp_wgrad_batched_t", wgrad_mode_word(mode), arr, len(grp), L.ptr(order),
+                     L.timeline_slot("hn_mlp_wgrad_batched", grp[0].stash.device), L.stream_handle(),
                      tag="batched")
             embeds = [p.embed for p in grp if p.embed is not None]
             by_table: Dict[int, list] = {}
@@ -1299,7 +1299,7 @@ def pack_many(runners: Sequence["MlpRunner"], device, mode: int, force: bool = F
     launch (hn_pack_units_multi) where more than one of them needs it; each runner's own `pack` then finds its streams
     fresh."""
     for m, arr, grp in collect_pack_jobs(runners, device, mode, force):
-        L.launch("hn_pack_units_multi", C.c_int(m), arr, C.c_int(len(grp)), L.stream_handle(),
+        L.launch("hn_pack_units_multi", m, arr, len(grp), L.stream_handle(),
                  tag="+".join(r.prog.name for r, *_ in grp))
         mark_packed(grp)
 
@@ -1374,8 +1374,8 @@ class MlpRunner:
             return d
         d.pack_backward = BACKWARD_SERIAL[0]
         self._pack_job(d, device)
-        L.launch("hn_pack_units", C.c_int(mode), L.ptr(d.units), C.c_int(d.n_units), L.ptr(d.ptrs), L.ptr(d.wstream),
-                 L.ptr(d.bias_desc), C.c_int(d.n_bias), L.ptr(d.bias), L.stream_handle(), tag=self.prog.name)
+        L.launch("hn_pack_units", mode, L.ptr(d.units), d.n_units, L.ptr(d.ptrs), L.ptr(d.wstream),
+                 L.ptr(d.bias_desc), d.n_bias, L.ptr(d.bias), L.stream_handle(), tag=self.prog.name)
         d.pack_key = key
         return d
 
@@ -1515,7 +1515,7 @@ class MlpRunner:
         else:
             _, gtot = self.prog.grad_offsets()
             grads = ret = torch.zeros(gtot, dtype=torch.float32, device=device)
-        L.launch("hn_mlp_wgrad", C.c_int(wgrad_mode_word(mode)), L.ptr(jobs_dev), C.c_int(n_jobs), L.ptr(stash), L.ptr(grads),
+        L.launch("hn_mlp_wgrad", wgrad_mode_word(mode), L.ptr(jobs_dev), n_jobs, L.ptr(stash), L.ptr(grads),
                  L.stream_handle(), tag=self.prog.name)
         return dsrc, ret
 

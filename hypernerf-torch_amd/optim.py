@@ -11,7 +11,6 @@ eagerly, and whoever replays a graph that contains the step calls it before the 
 """
 from __future__ import annotations
 
-import ctypes as C
 from bisect import bisect_right
 from typing import Sequence
 
@@ -89,8 +88,8 @@ class ArenaAdam:
             pend.fused(f)
         else:
             L.launch("hn_adam_step", L.ptr(a.data), L.ptr(a.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                     C.c_longlong(a.numel), L.ptr(self.hyper), L.ptr(self.step_count),
-                     C.c_int(int(self.zero_grad_in_step)), L.stream_handle())
+                     a.numel, L.ptr(self.hyper), L.ptr(self.step_count),
+                     int(self.zero_grad_in_step), L.stream_handle())
         a.bump()
 
     def finish_gradients(self):
@@ -394,8 +393,8 @@ class ArenaSGD(_ArenaOptimizer):
 
     def _launch(self):
         a = self.arena
-        L.launch("hn_sgd_step", L.ptr(a.data), L.ptr(a.grad), L.ptr(self.momentum_buffer), C.c_longlong(a.numel),
-                 L.ptr(self.hyper), L.ptr(self._step_words), C.c_int(int(self.zero_grad_in_step)), L.stream_handle())
+        L.launch("hn_sgd_step", L.ptr(a.data), L.ptr(a.grad), L.ptr(self.momentum_buffer), a.numel,
+                 L.ptr(self.hyper), L.ptr(self._step_words), int(self.zero_grad_in_step), L.stream_handle())
 
 
 def _check_radam_args(lr, betas, eps):
@@ -445,8 +444,8 @@ class ArenaRAdam(_ArenaOptimizer):
     def _launch(self):
         a = self.arena
         L.launch("hn_radam_step", L.ptr(a.data), L.ptr(a.grad), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                 L.ptr(self._slow()), C.c_longlong(a.numel), C.c_int(self._k()), L.ptr(self.hyper),
-                 L.ptr(self._step_words), C.c_int(int(self.zero_grad_in_step)), L.stream_handle())
+                 L.ptr(self._slow()), a.numel, self._k(), L.ptr(self.hyper),
+                 L.ptr(self._step_words), int(self.zero_grad_in_step), L.stream_handle())
 
 
 class ArenaRanger(ArenaRAdam):
@@ -541,12 +540,12 @@ class GradClip:
         from . import machine
         machine.flush_pending_reduce(self.arena.grad)       # a held-back reduce launch: the buffer must be complete
         a, inf = self.arena, float("inf")
-        value = C.c_float(inf if self._clip_value is None else self._clip_value)
+        value = inf if self._clip_value is None else self._clip_value
         if self._max_norm is not None:
-            L.launch("hn_grad_norm", L.ptr(a.grad), C.c_longlong(a.numel), C.c_float(self._grad_scale), value,
-                     C.c_float(self._max_norm), L.ptr(self._work), L.ptr(self._out), L.stream_handle())
+            L.launch("hn_grad_norm", L.ptr(a.grad), a.numel, self._grad_scale, value,
+                     self._max_norm, L.ptr(self._work), L.ptr(self._out), L.stream_handle())
         if (self._clip_value is not None and self._clip_value != inf) or (self._max_norm is not None and self._max_norm != inf):
-            L.launch("hn_grad_scale", L.ptr(a.grad), C.c_longlong(a.numel), C.c_float(self._grad_scale), value,
+            L.launch("hn_grad_scale", L.ptr(a.grad), a.numel, self._grad_scale, value,
                      L.ptr(self._out if self._max_norm is not None else None), L.stream_handle())
 
 

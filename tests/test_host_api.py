@@ -22,6 +22,9 @@ EMB = {"warp": list(range(100)), "camera": [0], "appearance": list(range(100)), 
 
 
 def test_library_exports_every_declared_symbol():
+    """Header, binding and library agree: EXPORTS / ARGTYPES are read from include/hn_kernels.h, so every prototype is
+    bound with as many argument types as it has parameters and the built library exports it.  The header is read here
+    with the test's own expressions, and three signatures are spelled out, as a guard on the binding's parser."""
     HN.build()
     lib = L.load()
     header = open(os.path.join(ROOT, "include", "hn_kernels.h")).read()
@@ -31,6 +34,75 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.hn_version() == 340
+    assert len(L.EXPORTS) == len(declared) and set(L.ARGTYPES) == declared
+    assert L.EXPORTS == re.findall(r"^int (hn_\w+)\(", header, flags=re.M)          # header order
+    protos = dict(re.findall(r"^int (hn_\w+)\(([^;]*)\);", re.sub(r"/\*.*?\*/", "", header, flags=re.S), flags=re.M))
+    assert set(protos) == declared
+    for name, params in protos.items():
+        n_params = 0 if params.strip() == "void" else params.count(",") + 1
+        assert len(L.ARGTYPES[name]) == n_params, name
+        assert getattr(lib, name).argtypes == L.ARGTYPES[name] and getattr(lib, name).restype is ctypes.c_int, name
+    p, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    assert L.ARGTYPES["hn_version"] == []
+    assert L.ARGTYPES["hn_posenc"] == [p, ctypes.c_int64, i, p, i, i, i, p, p, p, p]
+    assert L.ARGTYPES["hn_adam_step"] == [p, p, p, p, ctypes.c_longlong, p, p, i, p]
+    assert L.ARGTYPES["hn_grad_norm"] == [p, ctypes.c_longlong, f, f, f, p, p, p]
+    assert ctypes.sizeof(ctypes.c_int64) == ctypes.sizeof(ctypes.c_longlong) == 8 and ctypes.sizeof(i) == 4
+
+
+def test_prototype_parser_refuses_what_it_does_not_know():
+    """A parameter type outside the header's vocabulary raises, naming the entry and the parameter (never a guess); so
+    does a prototype that is not a plain parameter list."""
+    assert L.parse_prototypes("int hn_a(void);\nint hn_b(const float* x, /* n */ long long n,\n  hnStream_t stream);") == \
+        {"hn_a": [], "hn_b": [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]}
+    with pytest.raises(L.HnError, match=r"hn_new.*double scale"):
+        L.parse_prototypes("int hn_new(const float* x, double scale, hnStream_t stream);")
+    with pytest.raises(L.HnError, match=r"hn_new.*unsigned n"):
+        L.parse_prototypes("int hn_new(unsigned n);")
+    with pytest.raises(L.HnError, match="hn_cb"):
+        L.parse_prototypes("int hn_cb(void (*done)(int), hnStream_t stream);")
+
+
+def test_64_bit_scalars_arrive_whole():
+    """hn_mlp_workspace_bytes (host arithmetic) takes `int64_t n_points`.  A plain Python int reaches it whole: the same
+    status and sizes as the explicit ctypes.c_int64, also past 2^31 and 2^32.  Without declared argument types ctypes
+    passes a Python int as a C int, and 2^32 + 32 points would size the workspace of 32."""
+    lib = L.load()
+    ops = np.ascontiguousarray(warping.SE3Field(in_ch=3)._field_call(True).program.resolved_ops(L.HN_MODE_BF16, 32)[0],
+                               dtype=np.int32)
+
+    def query(n):
+        s_out, m_out = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        rc = lib.hn_mlp_workspace_bytes(ops.ctypes.data_as(ctypes.c_void_p), len(ops), 0, L.HN_MODE_BF16, n,
+                                        ctypes.byref(s_out), ctypes.byref(m_out))
+        return rc, s_out.value, m_out.value
+
+    sizes = {}
+    for n in (32, 2 ** 31, 2 ** 32 + 32):
+        sizes[n] = query(n)
+        assert sizes[n][0] == 0 and sizes[n] == query(ctypes.c_int64(n)), (n, sizes[n])
+        assert sizes[n][1] > 0 and sizes[n][2] > 0
+    assert sizes[2 ** 32 + 32] != sizes[32]
+    assert sizes[32][1] < sizes[2 ** 31][1] < sizes[2 ** 32 + 32][1] and sizes[32][2] < sizes[2 ** 31][2] < sizes[2 ** 32 + 32][2]
+
+
+def test_wrong_argument_kinds_are_refused_not_reinterpreted():
+    """With declared argument types a str where a float belongs, or a float where a pointer belongs, raises
+    ctypes.ArgumentError before the C function runs.  hn_grad_norm answers NULL pointers with a status, so nothing
+    here can reach a GPU."""
+    lib = L.load()
+    assert lib.hn_grad_norm(None, 4, 1.0, 1.0, 1.0, None, None, None) < 0
+    assert lib.hn_grad_norm(None, 4, 1, True, ctypes.c_float(1.0), 0, ctypes.c_void_p(0), None) < 0    # ints widen to float
+    with pytest.raises(ctypes.ArgumentError):
+        lib.hn_grad_norm(None, 4, "1.0", 1.0, 1.0, None, None, None)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.hn_grad_norm(1.5, 4, 1.0, 1.0, 1.0, None, None, None)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.hn_grad_norm(None, 4.0, 1.0, 1.0, 1.0, None, None, None)                                    # no float -> integer
+    with pytest.raises(TypeError):
+        lib.hn_grad_norm(None, 4, 1.0, 1.0, 1.0, None, None)                                            # one argument short
+    with pytest.raises(L.HnError):
+        L.launch("hn_grad_norm", L.ptr(None), 4, 1.0, 1.0, 1.0, L.ptr(None), None, None)                # ptr(None) is NULL
 
 
 def test_abi_struct_sizes_match_c():

@@ -1,6 +1,6 @@
 """HBM stream probes (csrc/hn_calib.hip) in several forms on one box: what rate the weight-gradient kernel's access
 pattern and DMA protocol can reach without its products.   python tools/stream_pattern_probe.py"""
-import ctypes as C, sys, os
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import hypernerf_torch_amd as HN  # noqa: F401
@@ -15,7 +15,7 @@ sink = torch.zeros(4, device=d)
 def ring(stages, proto, reps=12):
     t = torch.zeros(16, dtype=torch.int64, device=d)
     for _ in range(reps):
-        L.launch("hn_calib_ring", L.ptr(buf), C.c_longlong(n), C.c_int(stages), C.c_int(proto), L.ptr(sink), L.ptr(t), L.stream_handle())
+        L.launch("hn_calib_ring", L.ptr(buf), n, stages, proto, L.ptr(sink), L.ptr(t), L.stream_handle())
     torch.cuda.synchronize()
     v = t.cpu().tolist()
     return n * v[5] / (v[4] * 1e-8) / 1e12

@@ -41,7 +41,7 @@ def run(sel, reps=6, partial=True):
     for i in range(reps + 2):
         if i == 2:
             torch.cuda.synchronize(); t.zero_()
-        L.launch("hn_mlp_wgrad_batched_t", C.c_int(mode), arr, C.c_int(1), L.ptr(order), L.ptr(t), L.stream_handle())
+        L.launch("hn_mlp_wgrad_batched_t", mode, arr, 1, L.ptr(order), L.ptr(t), L.stream_handle())
     torch.cuda.synchronize()
     v = t.cpu().tolist()
     return w.sum() * 2048, v[4] * 1e-8 / v[5], len(part)
