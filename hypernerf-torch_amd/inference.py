@@ -168,10 +168,360 @@ def read_pfm(path: str):
     return np.flipud(data), scale
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# The GIF of the evaluated frames (eval.py:172, imageio.mimsave(..., fps=30)).  A GIF colour table has at most 256
+# entries: the frames are quantised on the device (functional.color_histogram / palette_map), the palette is cut on the
+# host from the 2^18-cell table, the index maps are LZW-coded by the library's host code (functional.gif_lzw) and the
+# container is written with the standard library.
+# ------------------------------------------------------------------------------------------------------------------
+GIF_COLORS = 256
+
+
+def palette_from_histogram(hist, colors: int = GIF_COLORS):
+    """(palette (256, 3) uint8 array, n_colors) from a colour table of functional.color_histogram: a pure, deterministic
+    function of the table (`colors`: fewer boxes than a GIF table holds, 1..256).  Entries are its non-empty cells: key k, count c, mean colour sums / c in float64.  With at
+    most 256 entries the palette is floor(mean + 0.5) of each, in key order.  Otherwise median cut: one box holds all
+    entries; until there are 256 boxes the box with more than one entry and the largest count_sum * range is cut (range:
+    the largest per-channel extent of its entries' means; equal scores: the lower box index, equal extents: the lower
+    channel), its entries ordered by (mean on that channel, key), after the first entry whose cumulative count reaches
+    half of the box's count (both sides keep at least one entry); the left part keeps the box's index, the right part
+    is appended.  A palette entry is floor(sum of sums / sum of counts + 0.5) of its box; unused entries are zero.
+    The scores of untouched boxes are kept from cut to cut, so a frame with 3e4 cells costs 255 small sorts."""
+    import numpy as np
+    h = np.asarray(hist.detach().cpu().numpy() if isinstance(hist, torch.Tensor) else hist)
+    if h.ndim != 2 or h.shape[1] != 4 or h.dtype.kind not in "iu":
+        raise ValueError("palette_from_histogram: an (N, 4) integer table [count, sum r, sum g, sum b]")
+    h = h.astype(np.int64, copy=False)
+    keys = np.flatnonzero(h[:, 0])
+    if keys.size == 0:
+        raise ValueError("palette_from_histogram: the table is empty")
+    if not 1 <= colors <= GIF_COLORS:
+        raise ValueError("palette_from_histogram: 1 .. 256 colours")
+    cnt, sums = h[keys, 0], h[keys, 1:4]
+    means = sums / cnt[:, None].astype(np.float64)
+    pal = np.zeros((GIF_COLORS, 3), dtype=np.uint8)
+    if keys.size <= colors:
+        pal[:keys.size] = np.floor(means + 0.5).astype(np.uint8)
+        return pal, int(keys.size)
+
+    def score(idx):
+        if idx.size < 2:
+            return -1.0, 0
+        m = means[idx]
+        ext = m.max(axis=0) - m.min(axis=0)
+        ch = int(np.argmax(ext))                        # the first maximum: the lower channel
+        return float(int(cnt[idx].sum())) * float(ext[ch]), ch
+
+    boxes = [np.arange(keys.size)]
+    scored = [score(boxes[0])]
+    while len(boxes) < colors:
+        b = int(np.argmax([s for s, _ in scored]))      # the first maximum: the lower box index
+        idx, ch = boxes[b], scored[b][1]
+        idx = idx[np.lexsort((keys[idx], means[idx, ch]))]
+        cum = np.cumsum(cnt[idx])
+        j = min(int(np.searchsorted(2 * cum, cum[-1], side="left")), idx.size - 2)
+        boxes[b], right = idx[:j + 1], idx[j + 1:]
+        boxes.append(right)
+        scored[b] = score(boxes[b])
+        scored.append(score(right))
+    for b, idx in enumerate(boxes):
+        pal[b] = np.floor(sums[idx].sum(axis=0) / float(int(cnt[idx].sum())) + 0.5).astype(np.uint8)
+    return pal, colors
+
+
+def _check_frames(frames, what: str):
+    """A non-empty list of equally sized (H, W, 3) uint8 frames as tensors; ValueError otherwise."""
+    import numpy as np
+    if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 4:
+        frames = list(frames)
+    frames = [torch.from_numpy(np.ascontiguousarray(f)) if isinstance(f, np.ndarray) else f for f in frames]
+    if not frames:
+        raise ValueError(f"{what}: no frames")
+    for f in frames:
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+            raise ValueError(f"{what}: every frame must be (H, W, 3) uint8")
+        if f.shape != frames[0].shape:
+            raise ValueError(f"{what}: frames differ in size: {tuple(f.shape[:2])} and {tuple(frames[0].shape[:2])}")
+    _check_gif_size(int(frames[0].shape[0]), int(frames[0].shape[1]), what)
+    return frames
+
+
+def _check_gif_size(h: int, w: int, what: str):
+    if not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError(f"{what}: a GIF side is 1 .. 65535 pixels, got {h} x {w}")
+
+
+@torch.no_grad()
+def quantize_frames(frames, palette: str = "global"):
+    """(palettes, indices) of uint8 (H, W, 3) frames, on the device or the host (host frames are uploaded: the colour
+    table and the palette search run in HIP, and there is no CPU fallback).  palette='global': ONE colour table over all
+    frames and one palette, so a colour keeps its index from frame to frame and nothing flickers; 'frame': one palette
+    per frame.  palettes: a list (of one, or one per frame) of (256, 3) uint8 host tensors, unused entries zero;
+    indices: one (H, W) uint8 host tensor per frame, each pixel the nearest USED palette entry (squared RGB distance,
+    the smaller index among equals).  No dithering."""
+    from . import _lib as L
+    from . import functional as F
+    if palette not in ("global", "frame"):
+        raise ValueError("palette: 'global' or 'frame'")
+    frames = _check_frames(frames, "quantize_frames")
+    dev = next((f.device for f in frames if f.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            L.require_gpu(frames[0])
+        dev = torch.device("cuda", torch.cuda.current_device())
+    frames = [f.to(dev).contiguous() for f in frames]
+    palettes, indices = [], []
+    if palette == "global":
+        table = None
+        for f in frames:
+            table = F.color_histogram(f, out=table)
+        pal, n_colors = palette_from_histogram(table)
+        palettes.append(torch.from_numpy(pal))
+        pal_dev = palettes[0][:n_colors].to(dev)
+        indices = [F.palette_map(f, pal_dev).cpu() for f in frames]
+    else:
+        for f in frames:
+            pal, n_colors = palette_from_histogram(F.color_histogram(f))
+            palettes.append(torch.from_numpy(pal))
+            indices.append(F.palette_map(f, palettes[-1][:n_colors].to(dev)).cpu())
+    return palettes, indices
+
+
+def write_gif(path: str, frames, fps: float = 30, loop: int = 0, palette: str = "global") -> None:
+    """Frames -> an animated GIF, what eval.py:172 does through imageio (`imageio.mimsave(..., fps=30)`), with the
+    standard library only.  `frames`: uint8 (H, W, 3) frames (quantised by `quantize_frames(frames, palette)`, on the
+    GPU), or the (palettes, indices) pair quantize_frames returned (one palette for 'global', one per frame for
+    'frame').  Layout: 'GIF89a'; the logical screen; for 'global' a global colour table, for 'frame' a local table in
+    front of every image, always 256 entries; the NETSCAPE2.0 application block with `loop` repetitions (0 = for ever);
+    per frame a graphic control extension with the delay max(1, round(100 / fps)) centiseconds (fps=30 gives 3, as
+    imageio and Pillow write it), no disposal, no transparency; an image descriptor covering the whole screen; LZW
+    minimum code size 8 and the code bytes of functional.gif_lzw in sub-blocks of at most 255.  ValueError: no frames,
+    frames of differing size, a side above 65535."""
+    import struct
+    from . import functional as F
+    if palette not in ("global", "frame"):
+        raise ValueError("palette: 'global' or 'frame'")
+    if not fps > 0:
+        raise ValueError("fps must be positive")
+    if not 0 <= int(loop) <= 65535:
+        raise ValueError("loop: 0 .. 65535")
+    if isinstance(frames, tuple) and len(frames) == 2 and isinstance(frames[0], (list, tuple)):
+        palettes, indices = list(frames[0]), list(frames[1])
+        if not indices:
+            raise ValueError("write_gif: no frames")
+        indices = [torch.as_tensor(x) for x in indices]
+        palettes = [torch.as_tensor(p) for p in palettes]
+        for x in indices:
+            if x.dtype != torch.uint8 or x.dim() != 2:
+                raise ValueError("write_gif: every index map must be (H, W) uint8")
+            if x.shape != indices[0].shape:
+                raise ValueError(f"write_gif: frames differ in size: {tuple(x.shape)} and {tuple(indices[0].shape)}")
+        for p in palettes:
+            if p.dtype != torch.uint8 or tuple(p.shape) != (GIF_COLORS, 3):
+                raise ValueError("write_gif: every palette must be (256, 3) uint8")
+        if len(palettes) != (1 if palette == "global" else len(indices)):
+            raise ValueError(f"write_gif: palette='{palette}' with {len(palettes)} palettes for {len(indices)} frames")
+        _check_gif_size(int(indices[0].shape[0]), int(indices[0].shape[1]), "write_gif")
+    else:
+        palettes, indices = quantize_frames(_check_frames(frames, "write_gif"), palette)
+    h, w = (int(s) for s in indices[0].shape)
+    delay = max(1, int(round(100.0 / fps)))
+    if delay > 65535:
+        raise ValueError("fps: the delay of a frame is at most 65535 centiseconds")
+
+    def table(p) -> bytes:
+        return p.cpu().contiguous().numpy().tobytes()
+    out = [b"GIF89a", struct.pack("<HHBBB", w, h, 0xF7 if palette == "global" else 0x70, 0, 0)]
+    if palette == "global":
+        out.append(table(palettes[0]))
+    out.append(b"\x21\xff\x0bNETSCAPE2.0\x03\x01" + struct.pack("<H", int(loop)) + b"\x00")
+    for i, idx in enumerate(indices):
+        out.append(b"\x21\xf9\x04\x00" + struct.pack("<H", delay) + b"\x00\x00")
+        out.append(b"\x2c" + struct.pack("<HHHHB", 0, 0, w, h, 0x00 if palette == "global" else 0x87))
+        if palette == "frame":
+            out.append(table(palettes[i]))
+        codes = F.gif_lzw(idx.cpu().contiguous())
+        out.append(b"\x08")
+        out.extend(bytes([len(codes[s:s + 255])]) + codes[s:s + 255] for s in range(0, len(codes), 255))
+        out.append(b"\x00")
+    out.append(b"\x3b")
+    with open(path, "wb") as f:
+        f.write(b"".join(out))
+
+
+def _gif_lzw_decode(data: bytes, min_code: int) -> bytes:
+    clear, end = 1 << min_code, (1 << min_code) + 1
+    table, prev, width = None, None, min_code + 1
+    out = bytearray()
+    acc = bits = pos = 0
+    while True:
+        while bits < width:
+            if pos >= len(data):
+                raise ValueError("GIF: the LZW stream ends without an end code")
+            acc |= data[pos] << bits
+            pos += 1
+            bits += 8
+        code = acc & ((1 << width) - 1)
+        acc >>= width
+        bits -= width
+        if code == clear:
+            table = [bytes([i]) for i in range(clear)] + [b"", b""]
+            prev, width = None, min_code + 1
+            continue
+        if code == end:
+            return bytes(out)
+        if table is None:
+            raise ValueError("GIF: the LZW stream does not open with a clear code")
+        if prev is None:
+            if code >= clear:
+                raise ValueError("GIF: bad first LZW code")
+            entry = table[code]
+        else:
+            if code < len(table):
+                entry = table[code]
+            elif code == len(table) and len(table) < 4096:
+                entry = prev + prev[:1]
+            else:
+                raise ValueError("GIF: LZW code outside the table")
+            if len(table) < 4096:
+                table.append(prev + entry[:1])
+        if len(table) == (1 << width) and width < 12:
+            width += 1
+        out += entry
+        prev = entry
+
+
+def read_gif(path: str):
+    """The inverse of write_gif (tests; the standard library and numpy): {'frames': [(H, W, 3) uint8 arrays],
+    'delays_cs': [centiseconds per frame], 'loop': the NETSCAPE2.0 repetition count or None}.  Reads what write_gif
+    writes and a little more: global or local colour tables of any size, images smaller than the screen (drawn over the
+    previous frame), any LZW minimum code size; no interlace, no transparency handling."""
+    import struct
+    import numpy as np
+    data = open(path, "rb").read()
+    if data[:6] not in (b"GIF89a", b"GIF87a"):
+        raise ValueError("not a GIF")
+    w, h, packed = struct.unpack("<HHB", data[6:11])
+    pos, gct = 13, None
+    if packed & 0x80:
+        n = 3 << ((packed & 7) + 1)
+        gct = np.frombuffer(data[pos:pos + n], dtype=np.uint8).reshape(-1, 3)
+        pos += n
+
+    def sub_blocks(pos):
+        parts = []
+        while data[pos]:
+            parts.append(data[pos + 1:pos + 1 + data[pos]])
+            pos += 1 + data[pos]
+        return b"".join(parts), pos + 1
+    frames, delays, loop, delay = [], [], None, 0
+    canvas = np.zeros((h, w, 3), dtype=np.uint8)
+    while True:
+        tag = data[pos]
+        if tag == 0x3B:
+            break
+        if tag == 0x21:
+            label = data[pos + 1]
+            body, end = sub_blocks(pos + 2)
+            if label == 0xF9:
+                delay = struct.unpack("<H", body[1:3])[0]
+            elif label == 0xFF and body[:11] == b"NETSCAPE2.0" and body[11:12] == b"\x01":
+                loop = struct.unpack("<H", body[12:14])[0]
+            pos = end
+        elif tag == 0x2C:
+            x0, y0, fw, fh, fpacked = struct.unpack("<HHHHB", data[pos + 1:pos + 10])
+            pos += 10
+            if fpacked & 0x40:
+                raise ValueError("read_gif does not read interlaced images")
+            table = gct
+            if fpacked & 0x80:
+                n = 3 << ((fpacked & 7) + 1)
+                table = np.frombuffer(data[pos:pos + n], dtype=np.uint8).reshape(-1, 3)
+                pos += n
+            if table is None:
+                raise ValueError("GIF: an image without a colour table")
+            min_code = data[pos]
+            codes, pos = sub_blocks(pos + 1)
+            idx = np.frombuffer(_gif_lzw_decode(codes, min_code), dtype=np.uint8)
+            if idx.size != fw * fh or x0 + fw > w or y0 + fh > h:
+                raise ValueError("GIF: an image does not match its descriptor")
+            if idx.size and int(idx.max()) >= table.shape[0]:
+                raise ValueError("GIF: an index outside the colour table")
+            canvas[y0:y0 + fh, x0:x0 + fw] = table[idx].reshape(fh, fw, 3)
+            frames.append(canvas.copy())
+            delays.append(delay)
+        else:
+            raise ValueError(f"GIF: unknown block 0x{tag:02x}")
+    return {"frames": frames, "delays_cs": delays, "loop": loop}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The depth image and the image stack of the validation step (utils/visualization.py:6-18, train.py:175-183)
+# ------------------------------------------------------------------------------------------------------------------
+def jet_lut() -> torch.Tensor:
+    """(256, 3) uint8 colour table for visualize_depth, BLUE channel first: the reference hands OpenCV's BGR array of
+    cv2.applyColorMap(x, COLORMAP_JET) to Image.fromarray unswapped, so channel 0 of its picture is cv2's blue.  The table
+    is MATLAB's jet(64) — per channel a trapezoid in sixteenths: red 0 up to entry 24, rising 1/16 .. 1 over entries
+    24..39, 1 to entry 54, falling to 8/16 at entry 63; green the 47-entry trapezoid from entry 8; blue 9/16 rising to 1
+    at entry 7, 1 to entry 22, falling to 1/16 at entry 38, 0 after — interpolated linearly from 64 to 256 entries and
+    times 255, rounded to nearest (halves to even), which is how OpenCV states its JET table.  Integer arithmetic: entry
+    k sits at 63 k / 255 = 21 k / 85 on the 64-entry axis."""
+    u = list(range(1, 17)) + [16] * 15 + list(range(16, 0, -1))
+    red, green, blue = [0] * 64, [0] * 64, [0] * 64
+    red[24:64] = u[0:40]
+    green[8:55] = u
+    blue[0:39] = u[8:47]
+    lut = torch.zeros((256, 3), dtype=torch.uint8)
+    for c, chan in enumerate((blue, green, red)):
+        for k in range(256):
+            i, m = divmod(21 * k, 85)
+            a, b = chan[i], chan[min(i + 1, 63)]
+            q, r = divmod(3 * (85 * a + (b - a) * m), 16)          # 255 * value = 3 * (85 a + (b - a) m) / 16
+            lut[k, c] = q + (1 if 2 * r > 16 or (2 * r == 16 and q % 2 == 1) else 0)
+    return lut
+
+
+def _unit_u8(device) -> torch.Tensor:
+    """k / 255 in float32 for k = 0..255, divided (not multiplied by a reciprocal) on the host: ToTensor's values."""
+    import numpy as np
+    return torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(device)
+
+
+@torch.no_grad()
+def visualize_depth(depth: torch.Tensor, lut=None) -> torch.Tensor:
+    """(H, W) depth on the device -> the (3, H, W) float32 picture of utils/visualization.py:visualize_depth, on the
+    device: nan_to_num, min-max normalisation, (255 x).astype(uint8), the colour table (functional.depth_colormap: HIP,
+    no host read) and ToTensor's uint8 / 255.  `lut`: a (256, 3) uint8 table, jet_lut() by default."""
+    from . import functional as F
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 2:
+        raise ValueError("visualize_depth: depth must be an (H, W) tensor")
+    img8 = F.depth_colormap(depth.detach().float(), jet_lut() if lut is None else lut)
+    return _unit_u8(img8.device)[img8.long()].permute(2, 0, 1).contiguous()
+
+
+@torch.no_grad()
+def validation_stack(gt: torch.Tensor, pred: torch.Tensor, depth: torch.Tensor, lut=None) -> torch.Tensor:
+    """The (3, 3, H, W) stack [ground truth, prediction, depth picture] the validation step logs (train.py:175-183), on
+    the host as there.  gt, pred: (H, W, 3) or (H*W, 3) images in [0, 1]; depth: the (H, W) depth map (coloured by
+    visualize_depth, on the GPU) or an already coloured (3, H, W) picture."""
+    if depth.dim() == 2:
+        depth = visualize_depth(depth, lut)
+    if depth.dim() != 3 or depth.shape[0] != 3:
+        raise ValueError("validation_stack: depth must be (H, W) or a (3, H, W) picture")
+    h, w = int(depth.shape[1]), int(depth.shape[2])
+    planes = []
+    for name, img in (("gt", gt), ("pred", pred)):
+        if img.shape[-1] != 3 or img.numel() != h * w * 3:
+            raise ValueError(f"validation_stack: {name} must be ({h}, {w}, 3) or ({h * w}, 3)")
+        planes.append(img.detach().reshape(h, w, 3).permute(2, 0, 1).float().cpu())
+    return torch.stack(planes + [depth.float().cpu()])
+
+
 @torch.no_grad()
 def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False, save_dir=None, group=None,
                     image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm",
-                    use_valid_mask: bool = False, ms_ssim: bool = False) -> Dict:
+                    use_valid_mask: bool = False, ms_ssim: bool = False, save_gif=None, gif_fps: float = 30,
+                    gif_palette: str = "global", save_depth_gif: bool = False) -> Dict:
     """The per-image loop of the reference's eval.py:145-178 on the GPU: for every sample {'rays': (H*W, 8|9),
     'rgbs': (H*W, 3) optional, 'hw': (H, W) optional} render the fine level in chunks, form the (H, W, 3) image,
     its 8-bit version (eval.py:165 `(img*255).astype(uint8)`) and, when ground truth is present, the PSNR
@@ -182,7 +532,11 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     `save_depth` writes every depth map (after nan_to_num) into `save_dir` (eval.py:150-158): `depth_{i:03d}.pfm`
     (`write_pfm`, the reference's save_pfm layout) for depth_format 'pfm', the raw float32 bytes as `depth_{i:03d}` for
     'bytes' — the reference writes that file into the current directory (eval.py:157), this port into `save_dir`.
-    The reference's GIF of all frames (eval.py:172, imageio.mimsave) is not written: the frames are in the result.
+    `save_gif='scene'` writes the reference's GIF of all frames (eval.py:172, imageio.mimsave(..., fps=30)) as
+    `save_dir/scene.gif` from the 8-bit frames formed here, quantised on the device (`write_gif` with `gif_fps` and
+    `gif_palette`); `save_depth_gif` writes the colour-mapped depths (functional.depth_colormap with jet_lut(), the
+    picture of visualize_depth) as `scene_depth.gif` (`depth.gif` without `save_gif`).  Both need `save_dir`; without
+    them the files written, the result and the work done are unchanged.
     `white_back` is accepted and ignored as in the reference's batched_inference (eval.py:77-85).
     `use_valid_mask` restricts the PSNR to the sample's 'valid_mask' ((H*W,) bool; the Blender splits carry alpha > 0)
     through metrics.psnr's own argument; off by default, as the reference's eval.py does not mask.
@@ -195,18 +549,31 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
         raise ValueError("depth_format: 'pfm' or 'bytes'")
     if save_depth and save_dir is None:
         raise ValueError("save_depth needs save_dir")
+    if (save_gif is not None or save_depth_gif) and save_dir is None:
+        raise ValueError("save_gif / save_depth_gif need save_dir")
+    if gif_palette not in ("global", "frame"):
+        raise ValueError("gif_palette: 'global' or 'frame'")
     from .losses import psnr as _psnr
     from .losses import ssim as _ssim
     from .losses import ms_ssim as _ms_ssim
     imgs, depths, psnrs, ssims, ms_ssims = [], [], [], [], []
+    gif_frames, depth_frames = [], []
+    if save_depth_gif:
+        from .functional import depth_colormap
+        lut = jet_lut()
     for i, sample in enumerate(images):
         rays = sample['rays']
         res = render_image(model, rays, chunk=chunk, keys=('rgb', 'depth'), group=group)
         n = rays.shape[0]
         h, w = sample.get('hw', (1, n))
         img = res['rgb'].view(h, w, 3)
-        img8 = (img * 255).to(torch.uint8).cpu()          # truncation, like numpy's astype(uint8) on [0, 1] data
+        img8_dev = (img * 255).to(torch.uint8)            # truncation, like numpy's astype(uint8) on [0, 1] data
+        img8 = img8_dev.cpu()
         imgs.append(img8)
+        if save_gif is not None:
+            gif_frames.append(img8_dev)
+        if save_depth_gif:
+            depth_frames.append(depth_colormap(res['depth'].view(h, w).float(), lut))
         depths.append(torch.nan_to_num(res['depth'].view(h, w)).cpu())
         if sample.get('rgbs') is not None:
             gt = sample['rgbs'].to(img.device).view(h, w, 3)
@@ -229,6 +596,13 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
             else:
                 with open(os.path.join(save_dir, f"{i:03d}.ppm"), "wb") as f:
                     f.write(f"P6 {w} {h} 255\n".encode() + img8.numpy().tobytes())
+    if save_dir is not None and (gif_frames or depth_frames):
+        import os
+        if gif_frames:
+            write_gif(os.path.join(save_dir, f"{save_gif}.gif"), gif_frames, fps=gif_fps, palette=gif_palette)
+        if depth_frames:
+            name = f"{save_gif}_depth.gif" if save_gif is not None else "depth.gif"
+            write_gif(os.path.join(save_dir, name), depth_frames, fps=gif_fps, palette=gif_palette)
     out = {'images': imgs, 'depths': depths, 'psnrs': psnrs,
            'mean_psnr': (sum(psnrs) / len(psnrs)) if psnrs else None,
            'ssims': ssims, 'mean_ssim': (sum(ssims) / len(ssims)) if ssims else None}

@@ -876,6 +876,39 @@ int hn_se3_warp_backward(const float* w, int w_ld, const float* v, int v_ld, con
                          const float* g_out, int g_ld, int n_points, float* d_w, int dw_ld, float* d_v, int dv_ld,
                          float* d_points, hnStream_t stream);
 
+/* The GIF of the evaluated frames (eval.py:172, imageio.mimsave) and the depth image of the validation step
+ * (utils/visualization.py:6-18): csrc/hn_gif.hip.  Pixels are packed 8-bit RGB, (n, 3) uint8 with NO alignment assumed;
+ * 1 <= n <= 2^31 everywhere.  Status, checked before any launch and before anything is written: -2 a count out of range,
+ * -3 a NULL pointer, -4 a misaligned word buffer (hist: 8 bytes; depth, range: 4 bytes).
+ *
+ * hn_color_hist: hist (2^18, 4) uint64, cell key = (r>>2)<<12 | (g>>2)<<6 | b>>2, holds [pixels, sum r, sum g, sum b].
+ * The launch ADDS to the table (the caller zeroes it; several frames may feed one table).  64-bit integer adds: exact for
+ * any number of calls that stays below 2^64 / 255 pixels per cell, and independent of arrival order.  Equal keys are
+ * folded per wave and, for the key of a workgroup's first pixel, per workgroup, before one add reaches memory.
+ * hn_palette_map: index[i] = argmin over k < n_colors (1..256) of (r-pr)^2 + (g-pg)^2 + (b-pb)^2 in integers against
+ * palette (n_colors, 3) uint8, the smallest k among equal distances; index (n,) uint8. */
+int hn_color_hist(const uint8_t* rgb_dev, long long n, unsigned long long* hist_dev, hnStream_t stream);
+int hn_palette_map(const uint8_t* rgb_dev, long long n, const uint8_t* palette_dev, int n_colors, uint8_t* index_dev,
+                   hnStream_t stream);
+
+/* visualize_depth in two launches without a host read between them.  d = nan_to_num(depth): NaN -> 0, +-inf -> +-FLT_MAX.
+ * hn_depth_range: range[0] = min d, range[1] = max d (one workgroup: depth maps are image-sized; the sign of a zero
+ * minimum or maximum is unspecified, and changes no pixel).
+ * hn_depth_colormap: x = (d - range[0]) / (range[1] - range[0] + 1e-8f), every operation rounded on its own in fp32;
+ * k = (uint8)(255 * x) by truncation; out[i] = lut[k] for a (256, 3) uint8 table; out (n, 3) uint8.  Where x is NaN
+ * (range[1] - range[0] overflowed) k = 0: NumPy's cast is undefined there, this is the one stated deviation. */
+int hn_depth_range(const float* depth_dev, long long n, float* range_dev, hnStream_t stream);
+int hn_depth_colormap(const float* depth_dev, long long n, const float* range_dev, const uint8_t* lut_dev,
+                      uint8_t* out_dev, hnStream_t stream);
+
+/* GIF's variable-width LZW of n >= 0 palette indices with minimum code size 8.  HOST code, host pointers, no launch and
+ * no stream: the chain of codes is serial and the frame is on its way to a file.  The clear code 256 comes first; codes
+ * are 9 to 12 bits, packed least significant bit first; when the 4096 codes are used up a clear code is sent and the
+ * table starts over; the end code 257 closes the stream.  out receives the raw code bytes (the caller cuts them into
+ * sub-blocks of at most 255) and *out_len their number.  -2: n or capacity negative; -3: a NULL pointer that must not be;
+ * -6: the stream needs *out_len bytes and `capacity` is smaller (nothing is written past capacity). */
+int hn_gif_lzw(const uint8_t* indices, long long n, uint8_t* out, long long capacity, long long* out_len);
+
 /* Box calibration for a benchmark line (no reference counterpart: measurement infrastructure).  Both kernels time
  * themselves into t_dev (device uint64[16], zeroed by the caller; layout of HnMlpArgs.timeline in [0..7]).
  * hn_calib_mfma: every wave of 512 workgroups x 8 waves runs `iters` x 8 independent v_mfma_f32_32x32x16_bf16 from
