@@ -18,7 +18,7 @@ from .optim import ArenaAdam, ArenaRAdam, ArenaRanger, ArenaSGD, GradClip
 from .functional import get_precision, set_precision
 from . import geometry
 from .geometry import (component_sizes, density_grid, extract_isosurface, extract_mesh, filter_mesh, mesh_components, read_ply,
-                       vertex_colors, write_ply)
+                       simplify_mesh, vertex_colors, write_ply)
 
 __version__ = "0.1.0"
 

@@ -20,6 +20,11 @@ Colours: a lattice has no view direction, but a mesh vertex has a normal and a f
 looks at every vertex along -normal (head-on from outside) or from a camera position, (v - c)/|v - c| — a zero length
 gives (0, 0, 1) — and takes the field's `rgb` at the vertex (rows of one point through NerfModel.query_points, the
 directions written chunk by chunk by hn_vertex_viewdirs), as float32 or as (rgb * 255) truncated to uint8.
+
+Simplification: marching tetrahedra emits about two triangles per surface vertex at lattice resolution.  `simplify_mesh`
+collapses the vertices of every cell of a coarser lattice into one (vertex clustering, csrc/hn_simplify.hip), placed by
+the members' tangent planes, and cancels the folded flaps the collapse leaves; `extract_mesh(simplify=k)` does it with
+cells of k lattice spacings.  The definition fixes every summation order: two runs give the same bits.
 """
 from __future__ import annotations
 
@@ -167,14 +172,121 @@ def vertex_colors(model, vertices: torch.Tensor, normals: Optional[torch.Tensor]
     return out
 
 
+def _simplify_factor(simplify):
+    """Three positive finite floats from extract_mesh's `simplify`, or ValueError."""
+    k = F._float3(simplify, "extract_mesh: simplify")
+    if not all(np.isfinite(x) and x > 0.0 for x in k):
+        raise ValueError(f"extract_mesh: simplify must be positive and finite, got {simplify!r}")
+    return k
+
+
+@torch.no_grad()
+def simplify_mesh(mesh: Dict[str, torch.Tensor], cell, origin=None, placement: str = 'quadric',
+                  regularization: float = 0.1) -> Dict[str, torch.Tensor]:
+    """The mesh simplified by vertex clustering (csrc/hn_simplify.hip; DESIGN.md holds the definition).  mesh: a dict as
+    extract_isosurface / filter_mesh return it — 'vertices' (V, 3) fp32, 'faces' (F, 3) int32, optional 'normals' (V, 3)
+    fp32 and 'colors' (V, 3) uint8 or fp32.  `cell`: the cell size, a float or three, positive and finite; `origin`: three
+    floats, None = the per-axis minimum of the vertices.  All vertices of a cell idx_c = floor((v_c - origin_c) / cell_c)
+    collapse into one: placement='mean' puts it at their mean, 'quadric' (needs 'normals') at the point of the cell
+    closest to their tangent planes, pulled towards the mean by `regularization`.  Its normal is the normalised sum of the
+    members' normals, its colour their mean.  Faces go through the collapse; those that degenerate leave, and so do pairs
+    of opposite faces over the same three vertices (folded flaps): the directed edges of the result balance as those of
+    the input did.
+    Returns 'vertices', 'faces', 'normals' and 'colors' when they were given, and 'vertex_cluster' (V,) int32: the output
+    vertex of every input vertex, -1 where its cluster lost all its faces.  Other keys of `mesh`, 'vertex_index'
+    included, are NOT carried over (an output vertex stands for several input ones).  Output vertices ascend with their
+    cell key ix | iy << 21 | iz << 42, faces with their sorted vertex triple; two runs give the same bits; an empty
+    input, or one that collapses entirely, gives zero-length tensors.
+    ValueError: origin above the vertices' minimum, 2**21 or more cells along an axis, vertices that are not finite.
+    Host synchronisations, four: the extent of the vertices (one read of six floats), the cluster count, the output
+    face count, the output vertex count."""
+    what = "simplify_mesh"
+    if placement not in ('quadric', 'mean'):
+        raise ValueError(f"{what}: placement must be 'quadric' or 'mean', got {placement!r}")
+    vertices = F._check_points(mesh.get('vertices'), what, "vertices")
+    v = vertices.shape[0]
+    faces = mesh.get('faces')
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{what}: faces must be a (F, 3) int32 tensor")
+    normals, colors = mesh.get('normals'), mesh.get('colors')
+    if normals is not None:
+        normals = F._check_points(normals, what, "normals", v)
+    elif placement == 'quadric':
+        raise ValueError(f"{what}: placement='quadric' needs the mesh's 'normals'")
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.shape != (v, 3)
+                               or colors.dtype not in (torch.uint8, torch.float32)):
+        raise ValueError(f"{what}: colors must be a ({v}, 3) uint8 or float32 tensor")
+    regularization = float(regularization)
+    if not (np.isfinite(regularization) and regularization >= 0.0):
+        raise ValueError(f"{what}: regularization must be finite and not negative, got {regularization}")
+    cell_c, _ = F.check_cells(cell, (0.0, 0.0, 0.0) if origin is None else origin, what)
+    dev = vertices.device
+
+    def empty():
+        out = {'vertices': torch.zeros((0, 3), dtype=torch.float32, device=dev),
+               'faces': torch.zeros((0, 3), dtype=torch.int32, device=dev),
+               'vertex_cluster': torch.full((v,), -1, dtype=torch.int32, device=dev)}
+        if normals is not None:
+            out['normals'] = torch.zeros((0, 3), dtype=torch.float32, device=dev)
+        if colors is not None:
+            out['colors'] = torch.zeros((0, 3), dtype=colors.dtype, device=dev)
+        return out
+
+    if v:
+        # host read 1: the extent, which the key layout (21 bits per axis, no negative index) must hold
+        lo, hi = (np.asarray(t, dtype=np.float32) for t in F.vertex_extent(vertices))
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError(f"{what}: the vertices are not finite")
+        origin_f = lo if origin is None else np.asarray(F._float3(origin, f"{what}: origin"), dtype=np.float32)
+        cell_f = np.asarray(list(cell_c), dtype=np.float32)
+        if (origin_f > lo).any():
+            raise ValueError(f"{what}: origin {origin_f.tolist()} lies above the vertices' minimum {lo.tolist()}")
+        with np.errstate(all="ignore"):
+            cells = np.floor((hi - origin_f) / cell_f)
+        if not (cells < 2 ** F.CELL_BITS).all():
+            raise ValueError(f"{what}: the vertices span {cells.tolist()} cells from the origin; the keys hold fewer than "
+                             f"2**{F.CELL_BITS} = {2 ** F.CELL_BITS} per axis")
+        origin = origin_f.tolist()
+    if not vertices.is_cuda or not faces.is_cuda:
+        raise ValueError(f"{what}: the mesh must live on the GPU (there is no CPU fallback)")
+    if v == 0 or faces.shape[0] == 0:
+        return empty()
+    clusters = F.cluster_vertices(vertices, cell, origin)                                   # host read 2: the cluster count
+    n_clusters = clusters['cluster_keys'].shape[0]
+    cfaces, used = F.cluster_faces(faces, clusters['vertex_cluster'], n_clusters, return_used=True)    # host read 3: F'
+    n_faces = cfaces.shape[0]
+    if n_faces == 0:
+        return empty()
+    rep = F.reduce_clusters(vertices, normals, colors, clusters, cell, origin, placement, regularization)
+    scan = torch.cumsum(used, 0, dtype=torch.int32)
+    n_out = int(scan[-1])                                                                   # host read 4: V'
+    kept = torch.empty(n_out, dtype=torch.int32, device=dev)
+    out_faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    every_face = torch.arange(1, n_faces + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        F.L.launch("hn_mesh_compact", F.L.ptr(cfaces), F.L.ptr(scan), F.L.ptr(every_face), n_clusters, n_faces, n_out,
+                   n_faces, F.L.ptr(kept), F.L.ptr(out_faces), F.L.stream_handle())
+    out = {name: F.gather_rows(t, kept) for name, t in rep.items()}
+    out['faces'] = out_faces
+    out['vertex_cluster'] = F.relabel_vertices(clusters['vertex_cluster'], used, scan)
+    return out
+
+
 def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, colors=None, min_faces: Optional[int] = None,
-                 keep_largest: Optional[int] = None, **kw) -> Dict[str, torch.Tensor]:
+                 keep_largest: Optional[int] = None, simplify=None, **kw) -> Dict[str, torch.Tensor]:
     """extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds), then
-    filter_mesh(min_faces, keep_largest) when either is given, then — only on what survived — 'colors' (V, 3) uint8 =
+    filter_mesh(min_faces, keep_largest) when either is given, then simplify_mesh when `simplify` = k (a float or three,
+    in units of the lattice spacing) is given: cells of k * (hi - lo)/(n - 1) per axis from the lower bounds, so the
+    clusters align with the lattice; then — only on what survived, along the new normals — 'colors' (V, 3) uint8 =
     vertex_colors(view=colors) when `colors` is 'normal' or a camera position, with density_grid's level / chunk /
     render_opts."""
+    factor = None if simplify is None else _simplify_factor(simplify)
     mesh = extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds)
     mesh = filter_mesh(mesh, min_faces=min_faces, keep_largest=keep_largest)
+    if factor is not None:
+        shape, b = F.check_lattice(_resolution(resolution), bounds, "extract_mesh")
+        cell = [k * (b[2 * c + 1] - b[2 * c]) / (shape[c] - 1) for c, k in enumerate(factor)]
+        mesh = simplify_mesh(mesh, cell, origin=(b[0], b[2], b[4]))
     if colors is not None:
         mesh = dict(mesh)
         mesh['colors'] = vertex_colors(model, mesh['vertices'], mesh['normals'], frame_id, view=colors, **kw)

@@ -699,6 +699,51 @@ int hn_gather_rows(const void* src_dev, long long n_src, const int32_t* index_de
 int hn_vertex_viewdirs(const float* vertices_dev, const float* normals_dev, long long n_vertices, long long start,
                        long long count, const float* cam_host, float* out_dev, hnStream_t stream);
 
+/* Mesh simplification by vertex clustering (csrc/hn_simplify.hip; DESIGN.md holds the definition, tests/simplify_restated.py
+ * restates it in NumPy float32).  origin_host / cell_host: three HOST floats each, every cell side positive and finite.
+ *   hn_simplify_extent     partial[6 b + 0 .. 2] / [6 b + 3 .. 5] = the per-axis minimum / maximum of the vertices 2048 b ..
+ *                2048 b + 2047 (n_partial must be ceil(V / 2048)); NaN in all six when the tile holds a NaN.  The caller
+ *                reduces the partials.
+ *   hn_simplify_keys       keys[v] (int64) = ix | iy << 21 | iz << 42 with idx_c = floorf((v_c - origin_c) / cell_c), fp32,
+ *                the subtraction and the division rounded on their own; an index outside [0, 2^21) is clamped (the caller
+ *                checks the extent first).
+ *   hn_simplify_reduce     one work-item per cluster c < n_clusters walks its members order[starts[c] .. starts[c + 1]) (order:
+ *                the vertex ids sorted by key, stable; starts: C + 1 int32) and writes the representative: out_vertices
+ *                (C, 3) = the sequential fp32 mean, or with quadric != 0 mean + adj(A) b / det(A) clamped into the cell box of
+ *                cluster_keys[c] (A = sum n n^T + regularization * k * I, b = sum n (n . (p - mean)); no step unless det is
+ *                finite and positive); out_normals (C, 3) = the normalised sequential sum (zero when its length is not > 0;
+ *                normals_dev may be NULL when quadric == 0: then no normals are written); colours by color_kind: 0 none,
+ *                1 uint8 (C, 3) = (2 * sum + k) / (2 k) in integers, 2 fp32 (C, 3) = sequential sum / k.
+ *   hn_simplify_face_keys  per face through vertex_cluster (V int32): rotated so that the smallest cluster id a comes first,
+ *                (a, x, y) -> key_ab = a << 31 | min(x, y) (int64), key_c = max(x, y), sign = +1 when x < y, else -1; a face
+ *                with two equal ids, an id outside [0, V) or a cluster id below 0: key_ab = 2^63 - 1, key_c = 2^31 - 1, sign 0.
+ *   hn_simplify_face_net   over the faces sorted by (key_ab, key_c): sorted_ab[i] = key_ab[perm[i]], perm int64; key_c and sign
+ *                are read through perm.  net[i] = the sum of the signs of the group of equal names that ENDS at i, 0 elsewhere.
+ *   hn_simplify_face_emit  ends = the inclusive scan (int64) of |net|, n_out its last entry: the group that ends at i writes
+ *                |net[i]| rows (a, b, c) (net > 0) or (a, c, b) (net < 0) at ends[i] - |net[i]| and stores 1 into used[a], used[b],
+ *                used[c] (used: C int32 zeroed by the caller; plain stores of the same value, no atomics).
+ *   hn_simplify_relabel    out[v] = scan[vertex_cluster[v]] - 1 when that cluster is used, else -1 (scan = inclusive scan of used).
+ * Status: -2 for every refused argument (a NULL pointer that must not be, a count <= 0 or above 2^31 - 1, n_clusters above
+ * n_vertices, n_out above n_faces, a cell side that is not positive and finite), before any launch. */
+int hn_simplify_extent(const float* vertices_dev, long long n_vertices, float* partial_dev, long long n_partial,
+                       hnStream_t stream);
+int hn_simplify_keys(const float* vertices_dev, long long n_vertices, const float* origin_host, const float* cell_host,
+                     int64_t* keys_dev, hnStream_t stream);
+int hn_simplify_reduce(const float* vertices_dev, const float* normals_dev, const void* colors_dev, int color_kind,
+                       const int32_t* order_dev, const int32_t* starts_dev, const int64_t* cluster_keys_dev,
+                       long long n_clusters, long long n_vertices, const float* origin_host, const float* cell_host,
+                       float regularization, int quadric, float* out_vertices_dev, float* out_normals_dev,
+                       void* out_colors_dev, hnStream_t stream);
+int hn_simplify_face_keys(const int32_t* faces_dev, long long n_faces, const int32_t* vertex_cluster_dev, long long n_vertices,
+                          int64_t* key_ab_dev, int32_t* key_c_dev, int32_t* sign_dev, hnStream_t stream);
+int hn_simplify_face_net(const int64_t* sorted_ab_dev, const int32_t* key_c_dev, const int32_t* sign_dev,
+                         const int64_t* perm_dev, long long n_faces, int32_t* net_dev, hnStream_t stream);
+int hn_simplify_face_emit(const int64_t* sorted_ab_dev, const int32_t* key_c_dev, const int64_t* perm_dev,
+                          const int32_t* net_dev, const int64_t* ends_dev, long long n_faces, long long n_clusters,
+                          long long n_out, int32_t* faces_out_dev, int32_t* used_dev, hnStream_t stream);
+int hn_simplify_relabel(const int32_t* vertex_cluster_dev, long long n_vertices, const int32_t* used_dev,
+                        const int32_t* scan_dev, long long n_clusters, int32_t* out_dev, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *

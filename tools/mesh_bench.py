@@ -24,7 +24,15 @@ Then, on that mesh, the post-processing stages, timed the same way (V' / F' = wh
                     written, 12 F' gathered; vertices and normals 2 x (12 V' gathered + 12 V' written)
   vertex_colors(view='normal')   12 V normals + 12 V positions read, 3 V of uint8 written (the directions and the float
                     colours live one chunk at a time); its time is the level program's, so `points_per_s` is the figure to
-                    hold against density_grid's."""
+                    hold against density_grid's.
+
+Then `simplify_mesh` on the unfiltered mesh with cells of --simplify (default 2 and 4) lattice spacings from the lower
+bounds, beside `extract_isosurface_ms` of the same grid.  `total_ms` is the whole call (four host reads); the stages are
+timed on their own the same way: `extent_ms` (vertex_extent: hn_simplify_extent, a reduction of its partials and
+the host read), `keys_ms` (the hn_simplify_keys launch, device events), `sort_ms` (the rest of
+cluster_vertices: torch's stable sort of V int64 keys, run lengths, the inverse), `reduce_ms` (hn_simplify_reduce, one
+work-item per cluster), `faces_ms` (cluster_faces: three launches, `faces_kernels_ms`, and two stable sorts over F names
+plus a scan, `faces_sorts_ms`) and `rest_ms` (compaction, gathers, relabelling, two host reads)."""
 import argparse
 import json
 import os
@@ -65,6 +73,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--chunk", type=int, default=1 << 20)
     ap.add_argument("--hbm-tbs", type=float, default=8.0)
+    ap.add_argument("--simplify", type=float, nargs="*", default=[2.0, 4.0], help="cell sizes in lattice spacings")
     a = ap.parse_args()
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     import torch
@@ -122,8 +131,33 @@ def main():
                                        "floor_ms": floor(color_b),
                                        "launches": per_launch(lambda: HN.vertex_colors(m, mesh["vertices"], mesh["normals"], 7,
                                                                                        chunk=a.chunk))}
+        del colors
+        row["simplify_mesh"] = []
+        origin = (bounds[0], bounds[2], bounds[4])
+        for k in a.simplify:
+            cell = k * (bounds[1] - bounds[0]) / (res - 1)
+            total_ms, small = timed(lambda: HN.simplify_mesh(mesh, cell, origin), a.repeats)
+            extent_ms, _ = timed(lambda: FN.vertex_extent(mesh["vertices"]), a.repeats)
+            cluster_ms, clusters = timed(lambda: FN.cluster_vertices(mesh["vertices"], cell, origin), a.repeats)
+            n_clusters = int(clusters["cluster_keys"].shape[0])
+            reduce_ms, _ = timed(lambda: FN.reduce_clusters(mesh["vertices"], mesh["normals"], None, clusters, cell, origin),
+                                 a.repeats)
+            faces_ms, _ = timed(lambda: FN.cluster_faces(mesh["faces"], clusters["vertex_cluster"], n_clusters), a.repeats)
+            launches = per_launch(lambda: HN.simplify_mesh(mesh, cell, origin))
+            keys_ms = launches["hn_simplify_keys"]["ms"]
+            face_kernels = sum(launches.get(n, {"ms": 0.0})["ms"] for n in
+                               ("hn_simplify_face_keys", "hn_simplify_face_net", "hn_simplify_face_emit"))
+            row["simplify_mesh"].append({
+                "k": k, "cell": cell, "total_ms": total_ms, "extent_ms": extent_ms, "keys_ms": keys_ms, "sort_ms": cluster_ms - keys_ms,
+                "reduce_ms": reduce_ms, "faces_ms": faces_ms, "faces_kernels_ms": face_kernels,
+                "faces_sorts_ms": faces_ms - face_kernels,
+                "rest_ms": total_ms - extent_ms - cluster_ms - reduce_ms - faces_ms, "clusters": n_clusters,
+                "members_mean": v / max(n_clusters, 1), "vertices": int(small["vertices"].shape[0]),
+                "faces": int(small["faces"].shape[0]), "fraction_of_extract_isosurface": total_ms / iso_ms,
+                "launches": launches})
+            del small, clusters
         rows.append(row)
-        del mesh, colors
+        del mesh
     print(json.dumps({"tool": "mesh_bench", "precision": a.precision, "chunk": a.chunk, "repeats": a.repeats,
                       "hbm_tbs": a.hbm_tbs, "build": L.build_id(),
                       "workload": "NerfModel use_warp bendy_sheet nerf_embed+alpha_cond (config 2), fine level", "results": rows}))
