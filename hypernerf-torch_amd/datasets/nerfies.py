@@ -249,6 +249,11 @@ class NerfiesDataset(GpuRayDataset):
         self.image_ids = torch.tensor(self.metadata_ids, dtype=torch.float32).to(self.device)
 
     # ---- rays --------------------------------------------------------------------------------------
+    def camera_record(self, idx: int) -> torch.Tensor:
+        """The (24,) fp32 camera record of image `idx` of this split, on the dataset's device: the camera the rays of
+        that image come from, as geometry.render_mesh takes it."""
+        return torch.from_numpy(self.camera_table[idx]).to(self.device)
+
     def _rays_of(self, cam: torch.Tensor, image_id: int) -> torch.Tensor:
         from .. import functional as F
         w, h = self.img_wh

@@ -25,6 +25,16 @@ Simplification: marching tetrahedra emits about two triangles per surface vertex
 collapses the vertices of every cell of a coarser lattice into one (vertex clustering, csrc/hn_simplify.hip), placed by
 the members' tangent planes, and cancels the folded flaps the collapse leaves; `extract_mesh(simplify=k)` does it with
 cells of k lattice spacings.  The definition fixes every summation order: two runs give the same bits.
+
+Looking at it: `render_mesh` casts the rays of a camera of the field at the mesh (csrc/hn_mesh_render.hip, DESIGN.md
+3.11) and gives face-id, depth, barycentric, normal and shaded colour images; `depth_agreement` / `mesh_depth_error`
+compare its depth with the field's along the same rays, and `mesh_turntable` writes an orbit as a GIF:
+
+    cam = camera_from_c2w(c2w, focal, W, H)            # or dataset.camera_record(idx), or orbit_cameras(...)[k]
+    rays = camera_rays(cam, W, H, near, far)
+    img = render_mesh(mesh, rays, cam, (W, H))          # img['rgb8'] (H, W, 3) uint8, img['depth'] (H, W)
+    mesh_depth_error(model, mesh, rays, cam, (W, H))    # {'abs_mean', 'rmse', 'iou', 'n'}
+    mesh_turntable(mesh, "turntable.gif", n=60)
 """
 from __future__ import annotations
 
@@ -291,6 +301,205 @@ def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, co
         mesh = dict(mesh)
         mesh['colors'] = vertex_colors(model, mesh['vertices'], mesh['normals'], frame_id, view=colors, **kw)
     return mesh
+
+
+# ---- looking at a mesh: ray casting through the cameras the field is rendered with (csrc/hn_mesh_render.hip) ------------
+def _check_render_mesh(mesh, what: str):
+    """(vertices, faces, normals, colors) of a mesh dict, checked as far as the host can, or ValueError."""
+    if not isinstance(mesh, dict):
+        raise ValueError(f"{what}: mesh must be a dict with 'vertices' and 'faces'")
+    vertices = F._check_points(mesh.get('vertices'), what, "vertices")
+    faces = F._check_mesh_faces(mesh.get('faces'), what)
+    v = vertices.shape[0]
+    normals, colors = mesh.get('normals'), mesh.get('colors')
+    if normals is not None:
+        normals = F._check_points(normals, what, "normals", v)
+    if colors is not None and (not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (v, 3)
+                               or colors.dtype not in (torch.uint8, torch.float32)):
+        raise ValueError(f"{what}: colors must be a ({v}, 3) uint8 or float32 tensor")
+    return vertices, faces, normals, colors
+
+
+@torch.no_grad()
+def render_mesh(mesh: Dict[str, torch.Tensor], rays: torch.Tensor, camera, image_wh, shading: str = 'headlight',
+                ambient: float = 0.3, background=(1.0, 1.0, 1.0), base_color=(0.8, 0.8, 0.8),
+                binning: bool = True) -> Dict[str, torch.Tensor]:
+    """The mesh seen through a camera of the field: {'face': (H, W) int32, -1 where no face is hit, 'depth': (H, W) fp32,
+    the distance along the unit ray (0 for none), 'bary': (H, W, 3) fp32, 'normal': (H, W, 3) fp32, 'rgb': (H, W, 3) fp32,
+    'rgb8': (H, W, 3) uint8} on the mesh's device.
+    mesh: the dict every function here passes around ('vertices' (V, 3) fp32, 'faces' (F, 3) int32, optional 'normals'
+    (V, 3) fp32 and 'colors' (V, 3) uint8 or fp32).  rays: (H*W, >= 6) fp32, row j*W + i the ray of pixel (col i, row j) —
+    the tensor render_image takes.  camera: the (24,) fp32 record those rays came from (camera_from_c2w, orbit_cameras,
+    NerfiesDataset.camera_record); image_wh = (W, H).
+    The picture is defined by casting exactly those rays: the camera only decides which faces a 16 x 16
+    tile of pixels looks at, so depth agrees with the field's rays bit for bit, lens distortion included, faces that share
+    an edge never leave a pinhole between them, hits are two-sided, and binning=False (every face at every pixel) gives
+    the same bits — except on the extension of a near-degenerate sliver face, where the fp32 edge test is rounding noise
+    and either picture can show a stray hit (limits).  A camera that does not match the rays drops faces.
+    shading: 'headlight' — colour * (ambient + (1 - ambient) |N . d|) with N the interpolated vertex normal (the face
+    normal without 'normals') — or 'none'; colour: the interpolated 'colors', `base_color` without them; `background`
+    where nothing is hit.  An empty mesh gives an all-background image.
+    ValueError: a face with a vertex id outside [0, V); more than 2**31 - 1 (tile, face) pairs.  One host read."""
+    what = "render_mesh"
+    vertices, faces, normals, colors = _check_render_mesh(mesh, what)
+    w, h = F.check_image_wh(image_wh, what)
+    camera = F._check_camera(camera, what)
+    rays = F._check_rays(rays, h * w, what)
+    F.check_shading(shading, ambient, background, base_color, what)
+    if not vertices.is_cuda or not faces.is_cuda or not rays.is_cuda:
+        raise ValueError(f"{what}: the mesh and the rays must live on the GPU (there is no CPU fallback)")
+    out = F.mesh_trace(vertices, faces, rays, camera, (w, h), binning=bool(binning))
+    out.update(F.mesh_shade(vertices, faces, normals, colors, rays, out['face'], out['bary'], shading, ambient, background,
+                            base_color))
+    return {k: t.view((h, w) + tuple(t.shape[1:])) for k, t in out.items()}
+
+
+def camera_from_c2w(c2w, focal: float, W: int, H: int, ndc: bool = False) -> np.ndarray:
+    """The (24,) fp32 camera record whose rays are the LLFF / Blender rays of the pose c2w (3, 4) with `focal`
+    (functional.generate_rays without NDC): orientation rows c2w[:, 0], -c2w[:, 1], -c2w[:, 2] (the pose looks along -z
+    with y up, the record along +z with y down), position c2w[:, 3], principal point (W/2 + 0.5, H/2 + 0.5) (a pixel
+    index there is a pixel centre here), no skew, no distortion.  The pose's rotation must be orthonormal, as a pose is.
+    NDC scenes are refused: a mesh in NDC space is not seen through a pinhole camera."""
+    if ndc:
+        raise ValueError("camera_from_c2w: NDC rays have no pinhole camera (the NDC transform moves origins and bends "
+                         "directions per pixel); extract and render the mesh in world space with ndc=False rays")
+    c2w = np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float64)
+    if c2w.shape != (3, 4):
+        raise ValueError(f"camera_from_c2w: c2w must be (3, 4), got {c2w.shape}")
+    focal, W, H = float(focal), int(W), int(H)
+    if not (np.isfinite(focal) and focal > 0.0) or W < 1 or H < 1:
+        raise ValueError("camera_from_c2w: focal, W and H must be positive")
+    rec = np.zeros(F.NERFIES_CAM_FLOATS, dtype=np.float64)
+    rec[0:3], rec[3:6], rec[6:9], rec[9:12] = c2w[:, 0], -c2w[:, 1], -c2w[:, 2], c2w[:, 3]
+    rec[12:17] = (focal, 1.0, 0.0, W / 2 + 0.5, H / 2 + 0.5)
+    return rec.astype(np.float32)
+
+
+def orbit_cameras(center, radius: float, n: int, elevation: float = 0.0, up=(0.0, -1.0, 0.0), *, focal: float,
+                  image_wh) -> np.ndarray:
+    """(n, 24) fp32 camera records on a circle around `center`, all looking at it: camera k sits at azimuth 2 pi k / n and
+    `elevation` degrees (-90 < elevation < 90) above the plane through `center` whose normal is `up`, at distance `radius`;
+    `up` appears up in the image (the record's y axis points down).  focal in pixels, the principal point at the image
+    centre (W/2, H/2), no skew, no distortion.  NumPy float64, rounded to fp32 at the end."""
+    what = "orbit_cameras"
+    c = np.asarray(F._float3(center, f"{what}: center"), dtype=np.float64)
+    u = np.asarray(F._float3(up, f"{what}: up"), dtype=np.float64)
+    w, h = F.check_image_wh(image_wh, what)
+    radius, focal, elevation, n = float(radius), float(focal), float(elevation), int(n)
+    if n < 1:
+        raise ValueError(f"{what}: n must be at least 1, got {n}")
+    if not (np.isfinite(radius) and radius > 0.0) or not (np.isfinite(focal) and focal > 0.0):
+        raise ValueError(f"{what}: radius and focal must be positive and finite")
+    if not -90.0 < elevation < 90.0:
+        raise ValueError(f"{what}: elevation must lie strictly between -90 and 90 degrees, got {elevation}")
+    if not np.isfinite(c).all() or not np.isfinite(u).all() or not np.linalg.norm(u) > 0.0:
+        raise ValueError(f"{what}: center must be finite and up a finite non-zero vector")
+    u = u / np.linalg.norm(u)
+    e1 = np.cross(u, np.eye(3)[int(np.argmin(np.abs(u)))])
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(u, e1)
+    el = np.deg2rad(elevation)
+    out = np.zeros((n, F.NERFIES_CAM_FLOATS), dtype=np.float64)
+    for k in range(n):
+        az = 2.0 * np.pi * k / n
+        pos = c + radius * (np.cos(el) * (np.cos(az) * e1 + np.sin(az) * e2) + np.sin(el) * u)
+        z = (c - pos) / np.linalg.norm(c - pos)
+        x = np.cross(-u, z)
+        x /= np.linalg.norm(x)
+        y = np.cross(z, x)
+        out[k, 0:3], out[k, 3:6], out[k, 6:9], out[k, 9:12] = x, y, z, pos
+        out[k, 12:17] = (focal, 1.0, 0.0, w / 2, h / 2)
+    return out.astype(np.float32)
+
+
+def camera_rays(record, W: int, H: int, near: float, far: float, device=None) -> torch.Tensor:
+    """(H*W, 8) fp32 ray rows [o, d, near, far] of a (24,) camera record, generated on the GPU
+    (functional.generate_rays_nerfies); `device`: where, the record's own device by default (a host record goes to the
+    current GPU)."""
+    cam = F._check_camera(record, "camera_rays")
+    w, h = F.check_image_wh((W, H), "camera_rays")
+    if device is None and not cam.is_cuda:
+        if not torch.cuda.is_available():
+            F.L.require_gpu(cam)
+        device = torch.device("cuda", torch.cuda.current_device())
+    if device is not None:
+        cam = cam.to(device)
+    with torch.cuda.device(cam.device):
+        return F.generate_rays_nerfies(h, w, cam, float(near), float(far))
+
+
+@torch.no_grad()
+def mesh_turntable(mesh: Dict[str, torch.Tensor], path, n: int = 60, image_wh=(256, 256), elevation: float = 20.0,
+                   radius: Optional[float] = None, focal: Optional[float] = None, up=(0.0, -1.0, 0.0), fps: float = 30,
+                   **render_kw) -> np.ndarray:
+    """An animated GIF of the mesh on a turntable: orbit_cameras around the centre of the vertices' bounding box (n
+    cameras, `elevation` degrees, `up`), render_mesh(**render_kw) per camera, the rgb8 frames through
+    inference.write_gif(path, frames, fps).  radius: 3 half-diagonals of the box by default; focal: by default the one at
+    which the box's bounding sphere spans 0.9 of the smaller image side.  Returns the (n, 24) records."""
+    from . import inference
+    what = "mesh_turntable"
+    vertices, _, _, _ = _check_render_mesh(mesh, what)
+    w, h = F.check_image_wh(image_wh, what)
+    if vertices.shape[0] == 0:
+        raise ValueError(f"{what}: the mesh has no vertices")
+    if not vertices.is_cuda:
+        raise ValueError(f"{what}: the mesh must live on the GPU (there is no CPU fallback)")
+    lo, hi = (np.asarray(t, dtype=np.float64) for t in F.vertex_extent(vertices))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError(f"{what}: the vertices are not finite")
+    half = max(0.5 * float(np.linalg.norm(hi - lo)), 1e-6)
+    radius = 3.0 * half if radius is None else float(radius)
+    if focal is None:
+        if not radius > half:
+            raise ValueError(f"{what}: radius {radius} lies inside the bounding sphere ({half}); give focal")
+        focal = 0.45 * min(w, h) * np.sqrt(radius * radius - half * half) / half
+    cams = orbit_cameras(0.5 * (lo + hi), radius, n, elevation, up, focal=focal, image_wh=(w, h))
+    frames = []
+    for rec in cams:
+        cam = torch.from_numpy(rec).to(vertices.device)
+        rays = camera_rays(cam, w, h, 0.0, radius + half)
+        frames.append(render_mesh(mesh, rays, cam, (w, h), **render_kw)['rgb8'])
+    inference.write_gif(path, frames, fps=fps)
+    return cams
+
+
+@torch.no_grad()
+def depth_agreement(mesh_depth: torch.Tensor, mesh_face: torch.Tensor, field_depth: torch.Tensor, field_acc: torch.Tensor,
+                    acc_min: float = 0.5) -> Dict[str, torch.Tensor]:
+    """How well a mesh's depth image agrees with the field's: {'abs_mean', 'rmse', 'iou', 'n'} as scalars on the inputs'
+    device (no host read).  The mesh covers a pixel when mesh_face >= 0, the field when field_acc >= acc_min; 'n' (int64) is
+    the number of pixels both cover, 'abs_mean' and 'rmse' the mean absolute and root mean square of mesh_depth -
+    field_depth over them (float64 sums; NaN when n is 0), 'iou' the intersection over the union of the two coverages
+    (NaN when neither covers anything).  The four tensors hold one value per pixel, in any matching shape."""
+    tensors = (mesh_depth, mesh_face, field_depth, field_acc)
+    if not all(isinstance(t, torch.Tensor) for t in tensors):
+        raise ValueError("depth_agreement: mesh_depth, mesh_face, field_depth and field_acc must be tensors")
+    numel = mesh_depth.numel()
+    if any(t.numel() != numel for t in tensors):
+        raise ValueError(f"depth_agreement: the four images differ in size: {[tuple(t.shape) for t in tensors]}")
+    if mesh_face.dtype.is_floating_point:
+        raise ValueError("depth_agreement: mesh_face must hold integer face ids")
+    md, mf, fd, fa = (t.detach().reshape(-1) for t in tensors)
+    mesh_cov, field_cov = mf >= 0, fa >= float(acc_min)
+    both = mesh_cov & field_cov
+    n = both.sum()
+    err = torch.where(both, md.double() - fd.double(), torch.zeros((), dtype=torch.float64, device=md.device))
+    return {'abs_mean': err.abs().sum() / n, 'rmse': torch.sqrt((err * err).sum() / n),
+            'iou': n / (mesh_cov | field_cov).sum(), 'n': n}
+
+
+@torch.no_grad()
+def mesh_depth_error(model, mesh: Dict[str, torch.Tensor], rays: torch.Tensor, camera, image_wh, chunk: int = 16384,
+                     depth_key: str = 'depth', acc_min: float = 0.5, level: str = 'fine') -> Dict[str, torch.Tensor]:
+    """depth_agreement between the mesh and the field it came from, through one camera: the field's `depth_key` and
+    'acc' from inference.render_image(model, rays, chunk, level), the mesh's depth and face from render_mesh along the
+    same rays.  Tells whether the iso level, min_faces and the simplification cell left the surface where the field
+    renders it."""
+    from . import inference
+    w, h = F.check_image_wh(image_wh, "mesh_depth_error")
+    field = inference.render_image(model, rays, chunk=chunk, level=level, keys=(depth_key, 'acc'))
+    seen = render_mesh(mesh, rays, camera, (w, h), shading='none')
+    return depth_agreement(seen['depth'], seen['face'], field[depth_key], field['acc'], acc_min=acc_min)
 
 
 def _host(a, dtype):

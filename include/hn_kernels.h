@@ -744,6 +744,52 @@ int hn_simplify_face_emit(const int64_t* sorted_ab_dev, const int32_t* key_c_dev
 int hn_simplify_relabel(const int32_t* vertex_cluster_dev, long long n_vertices, const int32_t* used_dev,
                         const int32_t* scan_dev, long long n_clusters, int32_t* out_dev, hnStream_t stream);
 
+/* Mesh rendering by ray casting (csrc/hn_mesh_render.hip; DESIGN.md 3.11 holds the definition, tests/mesh_render_restated.py
+ * restates it in NumPy float32).  Pixel p of the H x W image has the ray (o, d) = rays[p * ray_ld + 0 .. 5]; cam_dev is the
+ * 24-float camera record of hn_generate_rays_nerfies, on the device.  Vertices (V, 3) fp32, faces (F, 3) int32.
+ *   hn_mesh_project    per vertex the forward camera model (rotate, divide, distort in closed form, intrinsics): pix (V, 2)
+ *                fp32 pixel coordinates (pixel (i, j) covers [i, i + 1) x [j, j + 1)), flags (V) int32: 1 when z <= 1e-6 in the
+ *                camera frame, 2 when 1 + 3 k1 r + 5 k2 r^2 + 7 k3 r^3 <= 0 at r = x^2 + y^2 (the radial map folds) or a
+ *                coordinate is not finite; pix is (0, 0) under a flag.
+ *   hn_mesh_bin_count  counts[f] (int32) = the 16 x 16 tiles in the box of face f: the box of its three projected vertices and
+ *                three projected edge midpoints, padded by 1 pixel (+ 1/8 of its larger side when the camera has distortion),
+ *                clipped to the image; the whole image when a vertex or midpoint has a flag; nothing when all three
+ *                vertices have flag 1.  A face with an id outside [0, V) counts 0 and stores 1 into err[0] (int32, zeroed by
+ *                the caller).
+ *   hn_mesh_bin_fill   ends = the inclusive scan (int64) of counts, n_pairs its last entry: face f writes its (tile, face)
+ *                pairs, tiles row by row (tile = ty * ceil(W / 16) + tx), to the rows ends[f] - counts[f] .. ends[f] - 1 of
+ *                pair_tile / pair_face (int32).  A row outside [0, n_pairs) is not written.
+ *   hn_mesh_trace      one workgroup per tile, one thread per pixel; tile T tests the faces pair_face[tile_begin[T] ..
+ *                tile_end[T]) (int64 bounds, clamped to [0, n_pairs]), 64 at a time through LDS, and writes face (H*W int32, -1
+ *                for none), depth (H*W fp32, the ray parameter t, 0 for none) and bary (H*W, 3 fp32, zeros for none) of the
+ *                nearest hit, equal t going to the smaller face id.  A pair entry outside [0, F) or a vertex id outside
+ *                [0, V) is skipped.  n_pairs may be 0 (pair_face, faces, vertices may then be NULL): an all-empty image.
+ *   hn_mesh_shade      per pixel from face / bary: normal_out (H*W, 3) = the normalised interpolated vertex normal (normals_dev
+ *                NULL: the face normal), rgb_out (H*W, 3) fp32 = clamp(colour * k, 0, 1) with the interpolated vertex colour
+ *                (color_kind 1: uint8 / 255, 2: fp32, 0: base_color_host) and k = ambient + (1 - ambient) |N . d| (headlight
+ *                != 0) or 1, rgb8_out = floor(255 rgb + 0.5); a pixel without a face: normal 0, background_host.
+ *                base_color_host / background_host: three HOST floats in [0, 1]; ambient in [0, 1].
+ * Status, before any launch: -2 for a size out of range (a count <= 0 where one is needed or above 2^31 - 1, an image side
+ * outside 1 .. 65535, ray_ld < 6, a colour outside [0, 1]), -3 for a NULL pointer that must not be. */
+int hn_mesh_project(const float* vertices_dev, long long n_vertices, const float* cam_dev, float* pix_dev, int32_t* flags_dev,
+                    hnStream_t stream);
+int hn_mesh_bin_count(const int32_t* faces_dev, long long n_faces, const float* vertices_dev, const float* pix_dev,
+                      const int32_t* vflags_dev, long long n_vertices, const float* cam_dev, int H, int W,
+                      int32_t* counts_dev, int32_t* err_dev, hnStream_t stream);
+int hn_mesh_bin_fill(const int32_t* faces_dev, long long n_faces, const float* vertices_dev, const float* pix_dev,
+                     const int32_t* vflags_dev, long long n_vertices, const float* cam_dev, int H, int W,
+                     const int64_t* ends_dev, long long n_pairs, int32_t* pair_tile_dev, int32_t* pair_face_dev,
+                     hnStream_t stream);
+int hn_mesh_trace(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces,
+                  const float* rays_dev, int ray_ld, int H, int W, const int64_t* tile_begin_dev,
+                  const int64_t* tile_end_dev, const int32_t* pair_face_dev, long long n_pairs, int32_t* face_out_dev,
+                  float* depth_out_dev, float* bary_out_dev, hnStream_t stream);
+int hn_mesh_shade(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces,
+                  const float* normals_dev, const void* colors_dev, int color_kind, const float* rays_dev, int ray_ld,
+                  long long n_pixels, const int32_t* face_dev, const float* bary_dev, int headlight, float ambient,
+                  const float* base_color_host, const float* background_host, float* normal_out_dev, float* rgb_out_dev,
+                  uint8_t* rgb8_out_dev, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *
