@@ -26,8 +26,6 @@ CSRC_HEADERS = ["hn_common.h", "hn_pack.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hn_kernels.h")
 BUILD_MACROS = ("HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT")     # build-time tuning knobs (A/B experiments)
 
-HN_MODE_F32, HN_MODE_BF16, HN_MODE_BF16_S8 = 0, 1, 2
-
 
 class HnError(RuntimeError):
     pass
@@ -63,118 +61,6 @@ _cfg = BUILD_CONFIG or {}
 WGRAD_STAGES = _cfg.get("WGRAD_STAGES", int(os.environ.get("HN_WGRAD_STAGES") or 2))
 WGRAD_MAXSLOT = _cfg.get("WGRAD_MAXSLOT", int(os.environ.get("HN_WGRAD_MAXSLOT") or 8))
 WGRAD_MAX_STAGE_KB = min(8 * WGRAD_MAXSLOT, 160 // WGRAD_STAGES)
-HN_MAX_SRC, HN_MAX_DST, HN_MAX_SLOTS = 8, 4, 128
-HN_OP_WORDS, HN_CHUNK_UNITS, HN_DSRC_COMPS = 8, _cfg.get("CHUNK_UNITS", int(os.environ.get("HN_CHUNK_UNITS", 32))), 32
-HN_AUXG_MAX = 3
-HN_MAX_COMPS = 32
-
-HN_OP_LAYER, HN_OP_OUT, HN_OP_OUT_WIDE = 1, 4, 5
-HN_ACT_NONE, HN_ACT_RELU, HN_ACT_LEAKY_RELU, HN_ACT_ELU, HN_ACT_SOFTPLUS = 0, 1, 2, 3, 4
-HN_LAYER_NO_COMMIT, HN_LAYER_DIRECT = 1, 2
-HN_BOP_LOAD, HN_BOP_LOAD_WIDE, HN_BOP_LAYER, HN_BOP_AUX = 1, 2, 3, 4
-HN_FEAT_ZERO, HN_FEAT_ID, HN_FEAT_SIN, HN_FEAT_COS, HN_FEAT_SINP, HN_FEAT_ID_DIRECT = 0, 1, 2, 3, 4, 5
-
-
-class HnSrc(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("ld", C.c_int32), ("per_ray", C.c_int32), ("gather_idx", C.c_void_p),
-                ("gather_rows", C.c_int32), ("pad", C.c_int32)]
-
-
-class HnDst(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("ld", C.c_int32), ("pad", C.c_int32)]
-
-
-class HnSlot(C.Structure):
-    _fields_ = [("off", C.c_uint64), ("nt", C.c_int32), ("pad", C.c_int32)]
-
-
-class HnMlpArgs(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int32), ("n_points", C.c_int32), ("samples_per_ray", C.c_int32), ("training", C.c_int32),
-        ("n_ops", C.c_int32), ("n_chunks", C.c_int32), ("n_dsrc", C.c_int32), ("n_bias", C.c_int32),
-        ("n_feat", C.c_int32), ("max_groups", C.c_int32),
-        ("ops", C.c_void_p), ("wstream", C.c_void_p), ("bias", C.c_void_p), ("feat", C.c_void_p),
-        ("stash", C.c_void_p), ("masks", C.c_void_p), ("dsrc", C.c_void_p),
-        ("src", HnSrc * HN_MAX_SRC), ("dst", HnDst * HN_MAX_DST), ("slots", HnSlot * HN_MAX_SLOTS),
-        ("prof", C.c_void_p), ("comps", C.c_void_p), ("n_comps", C.c_int32), ("embed_reg_mask", C.c_int32),
-        ("embed_grad", C.c_void_p), ("embed_idx", C.c_void_p), ("embed_rows", C.c_int32), ("embed_dim", C.c_int32),
-        ("embed_col", C.c_int8 * 32), ("n_trig_comps", C.c_int32), ("wide_ops", C.c_int32), ("dz_scale_log2", C.c_int32), ("trig_lo_planes", C.c_int32),
-        ("timeline", C.c_void_p), ("embed_partial", C.c_void_p),
-    ]
-
-
-class HnDwBatch(C.Structure):
-    _fields_ = [("jobs", C.c_void_p), ("stash", C.c_void_p), ("grads", C.c_void_p), ("n_jobs", C.c_int32),
-                ("pad", C.c_int32), ("partials", C.c_void_p)]
-
-
-HN_MAX_WGRAD_BATCH = 8
-HN_MAX_DRAWS = 8
-
-
-HN_MAX_PACK_JOBS = 8
-
-
-class HnPackJob(C.Structure):
-    _fields_ = [("units", C.c_void_p), ("ptrs", C.c_void_p), ("wstream", C.c_void_p), ("bias", C.c_void_p),
-                ("bias_out", C.c_void_p), ("n_units", C.c_int32), ("n_bias", C.c_int32)]
-
-
-class HnEmbedReduce(C.Structure):
-    _fields_ = [("grad", C.c_void_p), ("rows", C.c_int32), ("dim", C.c_int32), ("col_mask", C.c_uint32), ("n_src", C.c_int32),
-                ("partial", C.c_void_p * HN_MAX_WGRAD_BATCH), ("idx", C.c_void_p * HN_MAX_WGRAD_BATCH),
-                ("n_blocks", C.c_int32 * HN_MAX_WGRAD_BATCH), ("samples_per_ray", C.c_int32 * HN_MAX_WGRAD_BATCH)]
-
-
-class HnDraw(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("n", C.c_int64), ("kind", C.c_int32), ("pad", C.c_int32)]
-
-
-class HnPrologue(C.Structure):
-    _fields_ = [("t_rand_draw", C.c_int32), ("n_rays", C.c_int32), ("n", C.c_int32), ("ray_ld", C.c_int32),
-                ("per_ray_bounds", C.c_int32), ("scale", C.c_float),
-                ("origins", C.c_void_p), ("dirs", C.c_void_p), ("lower", C.c_void_p), ("upper", C.c_void_p),
-                ("z_out", C.c_void_p), ("pts_out", C.c_void_p), ("ids_src", C.c_void_p), ("ids_dst", C.c_void_p),
-                ("ids_ld", C.c_int32), ("n_ids", C.c_int32)]
-
-
-class HnCompositeArgs(C.Structure):
-    _fields_ = [
-        ("variant", C.c_int32), ("n_rays", C.c_int32), ("n_samples", C.c_int32), ("white_bg", C.c_int32),
-        ("sample_at_infinity", C.c_int32), ("warped_ld", C.c_int32), ("has_dust", C.c_int32), ("dust_threshold", C.c_float),
-        ("rgb", C.c_void_p), ("raw", C.c_void_p), ("noise", C.c_void_p), ("z", C.c_void_p), ("dirs", C.c_void_p),
-        ("ray_ld", C.c_int64), ("warped", C.c_void_p),
-        ("out_rgb", C.c_void_p), ("out_depth", C.c_void_p), ("out_acc", C.c_void_p), ("out_weights", C.c_void_p),
-        ("out_med_depth", C.c_void_p), ("out_med_points", C.c_void_p),
-        ("g_rgb", C.c_void_p), ("g_depth", C.c_void_p), ("g_acc", C.c_void_p), ("g_weights", C.c_void_p),
-        ("d_rgb", C.c_void_p), ("d_raw", C.c_void_p), ("keep", C.c_void_p),
-        ("noise_scale", C.c_float), ("split", C.c_int32),
-        ("perm", C.c_void_p), ("rgb1", C.c_void_p), ("raw1", C.c_void_p), ("warped1", C.c_void_p),
-        ("d_rgb1", C.c_void_p), ("d_raw1", C.c_void_p), ("out_warped", C.c_void_p),
-    ]
-
-
-# numpy mirrors of the table structs (uploaded to the device as raw bytes)
-PACK_UNIT_DT = np.dtype([("w_id", "<i4"), ("ld", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r_end", "<i4"),
-                         ("c_end", "<i4"), ("k0", "<i4"), ("transposed", "<i4")])
-PACK_BIAS_DT = np.dtype([("w_id", "<i4"), ("n", "<i4"), ("off", "<i4"), ("len", "<i4")])
-FEAT_DT = np.dtype([("packed", "<i4"), ("freq", "<f4")])
-DWJOB_DT = np.dtype([("z_off", "<u8"), ("x_off", "<u8"), ("z_nt", "<i4"), ("x_nt", "<i4"), ("z_t0", "<i4"),
-                     ("x_t0", "<i4"), ("n_nt", "<i4"), ("n_kt", "<i4"), ("blk0", "<i4"), ("blk1", "<i4"),
-                     ("w_off", "<i4"), ("ld", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r_end", "<i4"),
-                     ("c_end", "<i4"), ("b_off", "<i4"), ("pad", "<i4"), ("x2_off", "<u8"), ("x2_nt", "<i4"),
-                     ("x2_t0", "<i4"), ("n_kt1", "<i4"), ("p_tile", "<i4")])
-DWREDUCE_DT = np.dtype([("batch", "<i4"), ("w_off", "<i4"), ("ld", "<i4"), ("row0", "<i4"), ("col0", "<i4"),
-                        ("r_end", "<i4"), ("c_end", "<i4"), ("first", "<i4"), ("count", "<i4")])
-
-ADAM_RANGE_DT = np.dtype([("start", "<i8"), ("len", "<i4"), ("pad", "<i4")])
-
-
-class HnAdamFuse(C.Structure):
-    _fields_ = [("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                ("n", C.c_int64), ("hyper", C.c_void_p), ("step", C.c_void_p), ("rest", C.c_void_p),
-                ("n_rest", C.c_int32), ("zero_grad", C.c_int32)]
-
 
 _SCALARS = {"int": C.c_int, "float": C.c_float, "int64_t": C.c_int64, "long long": C.c_longlong}
 
@@ -202,10 +88,75 @@ def parse_prototypes(text: str) -> dict:
     return out
 
 
-# names and signatures of the entry points come from the header the library is compiled against: nothing to mirror here
+_FIELD_SCALARS = {"int8_t": C.c_int8, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64,
+                  "uint64_t": C.c_uint64, "float": C.c_float}
+_ABI_ITEM = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(HN_\w+)[ \t]*(.*?)[ \t]*$"
+                       r"|\btypedef\s+(\w+)\s*\w*\s*\{((?:[^{}]|\{[^{}]*\})*)\}\s*(\w+)\s*;", flags=re.M)
+
+
+def parse_abi(text: str):
+    """(constants, structs) of `text`, each a dict in header order: every `#define HN_NAME <integer literal>` (the
+    include guard is skipped) and every `typedef struct [Tag] { ... } Name;` as a ctypes.Structure.  Not a C parser: it
+    knows the member shapes include/hn_kernels.h uses (the six fixed-width scalars, any pointer -> c_void_p, an earlier
+    ABI struct by value, several declarators or declarations per line, one-dimensional arrays sized by an integer or an
+    earlier macro) and raises on anything else (another type, a union, a bit-field, a nested struct, a second dimension,
+    an unknown size, a macro that is an expression) instead of guessing."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts, structs = {}, {}
+    for item in _ABI_ITEM.finditer(text):
+        macro, value, kind, body, name = item.groups()
+        if macro is not None:
+            if not value and re.search(r"#[ \t]*ifndef[ \t]+%s\s*$" % macro, text[:item.start()]):
+                continue                                  # the include guard
+            if not re.fullmatch(r"0|[1-9][0-9]*|0[xX][0-9a-fA-F]+", value):
+                raise HnError(f"{macro}: the macro's value '{value}' is not an integer literal")
+            consts[macro] = int(value, 0)
+            continue
+        if kind != "struct":
+            raise HnError(f"{name}: a typedef of a {kind}, not of a struct")
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            m = re.fullmatch(r"(?:const )?(\w+)( |(?: ?\* ?(?:const ?)?)+)(\w[^*]*)", decl)
+            if m is None or ("*" in decl and "," in decl):
+                raise HnError(f"{name}: declaration '{decl}' has a form the binding does not know")
+            base = C.c_void_p if "*" in decl else _FIELD_SCALARS.get(m.group(1)) or structs.get(m.group(1))
+            if base is None:
+                raise HnError(f"{name}: declaration '{decl}' has a type the binding does not know")
+            for declarator in m.group(3).split(","):
+                d = re.fullmatch(r" ?(\w+) ?(?:\[ ?(\w+) ?\])? ?", declarator)
+                if d is None:
+                    raise HnError(f"{name}: declaration '{decl}' has a form the binding does not know")
+                field, size = d.groups()
+                if size is None:
+                    fields.append((field, base))
+                elif size.isdigit() or size in consts:
+                    fields.append((field, base * (int(size) if size.isdigit() else consts[size])))
+                else:
+                    raise HnError(f"{name}: declaration '{decl}' has an array size the binding does not know")
+        structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+    return consts, structs
+
+
+# entry points, ABI structs and constants all come from the header the library is compiled against: nothing to mirror
+# here.  Every struct and every macro is a module attribute under its header name (HnMlpArgs, HN_MODE_BF16, ...).
 with open(HEADER) as _f:
-    ARGTYPES = parse_prototypes(_f.read())
+    _header = _f.read()
+ARGTYPES = parse_prototypes(_header)
 EXPORTS = list(ARGTYPES)
+CONSTANTS, STRUCTS = parse_abi(_header)
+globals().update(CONSTANTS)
+globals().update(STRUCTS)
+# the header's HN_CHUNK_UNITS is only the default of a build-time knob: the library's own value wins, as for the ring above
+HN_CHUNK_UNITS = _cfg.get("CHUNK_UNITS", int(os.environ.get("HN_CHUNK_UNITS", CONSTANTS["HN_CHUNK_UNITS"])))
+HN_AUXG_MAX = 3      # no macro in the header: a template argument of the machine kernels in csrc/hn_mlp.hip
+
+# numpy views of the table structs (uploaded to the device as raw bytes)
+PACK_UNIT_DT = np.dtype(STRUCTS["HnPackUnit"])
+PACK_BIAS_DT = np.dtype(STRUCTS["HnPackBias"])
+FEAT_DT = np.dtype(STRUCTS["HnFeat"])
+DWJOB_DT = np.dtype(STRUCTS["HnDwJob"])
+DWREDUCE_DT = np.dtype(STRUCTS["HnDwReduceTile"])
+ADAM_RANGE_DT = np.dtype(STRUCTS["HnAdamRange"])
 
 _lib = None
 

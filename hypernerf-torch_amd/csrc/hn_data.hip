@@ -81,7 +81,6 @@ extern "C" int hn_generate_rays(int H, int W, float focal, const float* c2w, int
 // Shared by hn_generate_rays_nerfies_kernel and the Nerfies instance of hn_ray_batch_kernel; every operation is rounded
 // on its own, so that both write the same bits whatever either inlining context would contract.
 // ------------------------------------------------------------------------------------------------
-#define HN_NERFIES_CAM_FLOATS 24
 #define HN_NERFIES_NEWTON_STEPS 10
 
 __device__ __forceinline__ void hn_nerfies_pixel_ray(const float* cam, int i, int j, float o[3], float d[3]) {

@@ -22,8 +22,6 @@
 // 28 bytes of slots per lattice point are the largest term.
 #include "hn_common.h"
 
-#define HN_ISO_BLOCK 256
-
 struct HnLattice {
   int nx, ny, nz;
   float lo[3], step[3];

@@ -30,7 +30,7 @@ HN_DEV unsigned long long hn_wave_sum_u64(unsigned long long x) {
 // Packed per-lane sums: r | g << 17 | b << 34 | count << 51.  A thread holds at most HN_HIST_PER_THREAD = 8 pixels of the
 // common key, a wave 512: every colour sum stays below 512 * 255 < 2^17 and the count below 2^13.
 // ------------------------------------------------------------------------------------------------
-#define HN_HIST_BINS (1 << 18)
+static_assert(HN_HIST_BINS == 1 << 18, "hn_kernels.h: HN_HIST_BINS is one cell per 18-bit colour key");
 #define HN_HIST_PER_THREAD 8
 #define HN_HIST_TILE (256 * HN_HIST_PER_THREAD)
 #define HN_HIST_FIELD 17

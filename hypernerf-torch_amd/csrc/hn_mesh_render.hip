@@ -21,11 +21,9 @@
 // face's own tiles (limits).
 #include "hn_common.h"
 
-#define HN_MESH_TILE 16            // pixels per tile side: one workgroup of 256 threads per tile, one thread per pixel
 #define HN_MESH_BATCH 64           // faces staged through LDS at a time
 #define HN_MESH_BEHIND 1           // vertex flag: z <= 1e-6 in the camera frame
 #define HN_MESH_UNPROJECTABLE 2    // vertex flag: the radial map folds at its radius, or a coordinate is not finite
-#define HN_MESH_MAX_SIDE 65535     // image sides: pixel and tile coordinates stay exact in fp32
 
 HN_DEV float hn_mr_dot(const float* a, const float* b) {
   return __fadd_rn(__fadd_rn(__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1])), __fmul_rn(a[2], b[2]));

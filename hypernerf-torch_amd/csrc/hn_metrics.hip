@@ -20,7 +20,6 @@
 // and the inputs on tile + 2R.
 #include "hn_common.h"
 
-#define HN_SSIM_MAX_R 7          // window sizes 3, 5, ..., 15
 #define HN_SSIM_TW 32
 #define HN_SSIM_TH 16
 #define HN_SSIM_THREADS 256

@@ -19,8 +19,6 @@
 // valid positions of all channels.  No float atomics anywhere: the same bits run to run.
 #include "hn_common.h"
 
-#define HN_MS_LEVELS 5
-#define HN_MS_MAX_SIZE 11
 #define HN_MS_TW 32
 #define HN_MS_TH 16
 #define HN_MS_THREADS 256

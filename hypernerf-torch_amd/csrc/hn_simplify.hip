@@ -23,7 +23,6 @@
 // handful).
 #include "hn_common.h"
 
-#define HN_SIMPLIFY_BITS 21
 #define HN_SIMPLIFY_MASK ((1ll << HN_SIMPLIFY_BITS) - 1ll)
 #define HN_SIMPLIFY_DROPPED 0x7fffffffffffffffll
 
@@ -49,7 +48,7 @@ static bool hn_cells(const float* origin_host, const float* cell_host, HnCells* 
 // taken in.  A tile that holds a NaN reports NaN in all six, so that the caller sees it.
 // ------------------------------------------------------------------------------------------------
 #define HN_EXTENT_PER_THREAD 8
-#define HN_EXTENT_TILE (256 * HN_EXTENT_PER_THREAD)
+static_assert(HN_EXTENT_TILE == 256 * HN_EXTENT_PER_THREAD, "hn_kernels.h: HN_EXTENT_TILE is one workgroup's vertices");
 
 __global__ __launch_bounds__(256) void hn_simplify_extent_kernel(const float* __restrict__ vertices, long long n_vertices,
                                                                  float* __restrict__ partial) {

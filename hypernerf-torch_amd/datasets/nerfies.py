@@ -35,12 +35,13 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from .. import _lib as L
 from . import image_io
 from .base import GpuRayDataset, u8_to_unit
 
 SPLITS = ("train", "val", "test")
 METADATA_KEYS = ("warp_id", "appearance_id", "camera_id")
-CAM_FLOATS = 24              # functional.NERFIES_CAM_FLOATS, hn_kernels.h
+CAM_FLOATS = L.HN_NERFIES_CAM_FLOATS    # the camera record of hn_kernels.h
 _CAMERA_KEYS = ("orientation", "position", "focal_length", "principal_point", "image_size", "skew",
                 "pixel_aspect_ratio", "radial_distortion", "tangential_distortion")
 

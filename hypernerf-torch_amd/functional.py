@@ -999,7 +999,7 @@ def bg_loss(warped: torch.Tensor, points: torch.Tensor, scale: float) -> torch.T
 # --------------------------------------------------------------------------------------------
 # SSIM (metrics.py:15-20: kornia's ssim loss)
 # --------------------------------------------------------------------------------------------
-SSIM_MAX_WINDOW = 15          # hn_ssim_*: odd windows 3 .. 15
+SSIM_MAX_WINDOW = 2 * L.HN_SSIM_MAX_R + 1    # hn_ssim_*: odd windows 3 .. 15
 _SSIM_WINDOWS: Dict[int, C.Array] = {}
 
 
@@ -1105,8 +1105,8 @@ def ssim_dssim(pred: torch.Tensor, gt: torch.Tensor, window_size: int = 3, max_v
 # --------------------------------------------------------------------------------------------
 # multi-scale SSIM (the metric the Nerfies / HyperNeRF tables report)
 # --------------------------------------------------------------------------------------------
-MSSSIM_LEVELS = 5
-MSSSIM_MAX_SIZE = 11          # hn_msssim_forward: window sizes 1 .. 11
+MSSSIM_LEVELS = L.HN_MS_LEVELS
+MSSSIM_MAX_SIZE = L.HN_MS_MAX_SIZE    # hn_msssim_forward: window sizes 1 .. 11
 MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 _MSSSIM_TILE_W, _MSSSIM_TILE_H = 32, 16
 _MSSSIM_PLANS: Dict[tuple, tuple] = {}
@@ -1187,7 +1187,7 @@ def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) ->
 # --------------------------------------------------------------------------------------------
 # geometry out of a trained field (csrc/hn_geometry.hip)
 # --------------------------------------------------------------------------------------------
-ISO_BLOCK = 256               # lattice points (cells) per workgroup of the hn_iso_* passes
+ISO_BLOCK = L.HN_ISO_BLOCK    # lattice points (cells) per workgroup of the hn_iso_* passes
 INT32_MAX = 2 ** 31 - 1
 
 
@@ -1464,7 +1464,7 @@ def vertex_viewdirs(vertices: torch.Tensor, normals: Optional[torch.Tensor], sta
 # --------------------------------------------------------------------------------------------
 # mesh simplification by vertex clustering (csrc/hn_simplify.hip)
 # --------------------------------------------------------------------------------------------
-CELL_BITS = 21                # bits per axis of a cell key: fewer than 2**21 cells along every axis
+CELL_BITS = L.HN_SIMPLIFY_BITS    # bits per axis of a cell key: fewer than 2**21 cells along every axis
 
 
 def _float3(x, what: str):
@@ -1501,7 +1501,7 @@ def _check_points(t, what: str, name: str, rows=None):
     return t.detach().contiguous()
 
 
-EXTENT_TILE = 2048            # vertices per workgroup of hn_simplify_extent
+EXTENT_TILE = L.HN_EXTENT_TILE    # vertices per workgroup of hn_simplify_extent
 
 
 @torch.no_grad()
@@ -1664,8 +1664,8 @@ def relabel_vertices(vertex_cluster: torch.Tensor, used: torch.Tensor, scan: tor
 # --------------------------------------------------------------------------------------------
 # mesh rendering by ray casting (csrc/hn_mesh_render.hip)
 # --------------------------------------------------------------------------------------------
-MESH_TILE = 16                # pixels per tile side of hn_mesh_trace
-MESH_MAX_SIDE = 65535         # image sides the mesh renderer takes
+MESH_TILE = L.HN_MESH_TILE    # pixels per tile side of hn_mesh_trace
+MESH_MAX_SIDE = L.HN_MESH_MAX_SIDE    # image sides the mesh renderer takes
 
 
 def check_image_wh(image_wh, what: str):
@@ -1682,8 +1682,9 @@ def check_image_wh(image_wh, what: str):
 def _check_camera(camera, what: str) -> torch.Tensor:
     if not isinstance(camera, torch.Tensor) and hasattr(camera, "__array__"):
         camera = torch.as_tensor(camera)
-    if not isinstance(camera, torch.Tensor) or tuple(camera.shape) != (24,) or camera.dtype != torch.float32:
-        raise ValueError(f"{what}: camera must be a (24,) float32 record")
+    if (not isinstance(camera, torch.Tensor) or tuple(camera.shape) != (NERFIES_CAM_FLOATS,)
+            or camera.dtype != torch.float32):
+        raise ValueError(f"{what}: camera must be a ({NERFIES_CAM_FLOATS},) float32 record")
     return camera.detach().contiguous()
 
 
@@ -1970,7 +1971,7 @@ def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, 
                rgbs, near, far, image_ids)
 
 
-NERFIES_CAM_FLOATS = 24      # hn_kernels.h: orientation 9, position 3, f, aspect, skew, cx, cy, k1 k2 k3, p1 p2, 2 zeros
+NERFIES_CAM_FLOATS = L.HN_NERFIES_CAM_FLOATS    # hn_kernels.h: orientation 9, position 3, f, aspect, skew, cx, cy, k1 k2 k3, p1 p2, 2 zeros
 
 
 def generate_rays_nerfies(h: int, w: int, cam: torch.Tensor, near: float, far: float,
@@ -2082,7 +2083,7 @@ def resize_lanczos_rgba8(img: torch.Tensor, size) -> torch.Tensor:
 # --------------------------------------------------------------------------------------------
 # GIF of the evaluated frames, depth image of the validation step (csrc/hn_gif.hip)
 # --------------------------------------------------------------------------------------------
-HIST_BINS = 1 << 18
+HIST_BINS = L.HN_HIST_BINS
 
 
 def _check_pixels(pixels, what: str) -> torch.Tensor:

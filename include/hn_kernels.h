@@ -267,7 +267,10 @@ typedef struct {
 
 int hn_version(void);
 /* sizeof() of the ABI structs, in the order HnMlpArgs, HnPackUnit, HnPackBias, HnDwJob,
- * HnCompositeArgs, HnFeat, HnSlot, HnSrc — lets a foreign-language binding verify its mirror. */
+ * HnCompositeArgs, HnFeat, HnSlot, HnSrc — lets a foreign-language binding that keeps mirrors of its own verify them.
+ * The Python binding keeps none: it derives every struct and every integer macro from this header's text when it is
+ * imported, so the typedefs and #defines here stay in the plain forms that parser knows (one-dimensional arrays sized by
+ * an integer or an earlier macro, macros that are integer literals). */
 int hn_abi_sizes(int32_t* out, int n);
 /* The build-time tuning knobs of THIS library (ABI 340): out[0..] = ring depth and LDS-DMA pieces per wave and stage of
  * hn_wgrad_kernel, bias-by-MFMA build, weight-stream chunk in units, block-read build, asymmetric weight-stream issue,
@@ -576,6 +579,7 @@ int hn_mse_loss_forward_grad(const float* coarse, const float* fine, const float
  * hn_ssim_backward: the upstream gradient is either g_scalar (ONE device float: every element of the map gets it) or
  * g_map (contiguous (n, c, h, w)), exactly one of them; d_pred (and d_gt unless NULL) are written, contiguous, as the
  * adjoint of the forward including the reflect padding. */
+#define HN_SSIM_MAX_R 7 /* largest window radius: window sizes 3, 5, ..., 15 */
 int hn_ssim_workspace_bytes(int n, int c, int h, int w, int window, int64_t* bytes);
 int hn_ssim_forward(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int n,
                     int c, int h, int w, const float* window_host, int window, float c1, float c2, float eps,
@@ -600,6 +604,8 @@ int hn_ssim_backward(const float* pred, const int64_t* pred_strides, const float
  * the partial sums in a fixed order: no float atomics, bit-reproducible.  The host arrays are consumed at the call.
  * Status: -2 for every refused argument (n, c, h, w < 1, a NULL pointer, a size outside 1 .. 11 or above its level's
  * sides), checked before the first launch. */
+#define HN_MS_LEVELS 5
+#define HN_MS_MAX_SIZE 11 /* taps per row of taps_host; window sizes 1 .. 11 */
 int hn_msssim_workspace_bytes(int n, int c, int h, int w, int64_t* bytes);
 int hn_msssim_forward(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int n,
                       int c, int h, int w, const float* taps_host, const int* sizes_host, float c1, float c2,
@@ -638,6 +644,7 @@ int hn_msssim_forward(const float* pred, const int64_t* pred_strides, const floa
  *                    normals point from inside to outside (towards lower f).
  * No atomics: the same grid gives the same arrays on every run.  Status: -2 for every refused argument (a NULL pointer
  * that must not be, a side < 2, 7*N above 2^31 - 1, hi <= lo, start / count outside the lattice), before any launch. */
+#define HN_ISO_BLOCK 256 /* lattice points (hn_iso_faces: cells) per workgroup: the length of every *_blocks array */
 int hn_grid_points(int nx, int ny, int nz, const float* bounds_host, long long start, long long count, float* out_dev,
                    hnStream_t stream);
 int hn_density_activate(const float* raw_dev, const float* points_dev, long long n, int has_dust, float dust_threshold,
@@ -725,6 +732,8 @@ int hn_vertex_viewdirs(const float* vertices_dev, const float* normals_dev, long
  *   hn_simplify_relabel    out[v] = scan[vertex_cluster[v]] - 1 when that cluster is used, else -1 (scan = inclusive scan of used).
  * Status: -2 for every refused argument (a NULL pointer that must not be, a count <= 0 or above 2^31 - 1, n_clusters above
  * n_vertices, n_out above n_faces, a cell side that is not positive and finite), before any launch. */
+#define HN_EXTENT_TILE 2048  /* vertices per workgroup of hn_simplify_extent: n_partial = ceil(V / HN_EXTENT_TILE) */
+#define HN_SIMPLIFY_BITS 21  /* bits per axis of a cell key (hn_simplify_keys) */
 int hn_simplify_extent(const float* vertices_dev, long long n_vertices, float* partial_dev, long long n_partial,
                        hnStream_t stream);
 int hn_simplify_keys(const float* vertices_dev, long long n_vertices, const float* origin_host, const float* cell_host,
@@ -771,6 +780,8 @@ int hn_simplify_relabel(const int32_t* vertex_cluster_dev, long long n_vertices,
  *                base_color_host / background_host: three HOST floats in [0, 1]; ambient in [0, 1].
  * Status, before any launch: -2 for a size out of range (a count <= 0 where one is needed or above 2^31 - 1, an image side
  * outside 1 .. 65535, ray_ld < 6, a colour outside [0, 1]), -3 for a NULL pointer that must not be. */
+#define HN_MESH_TILE 16        /* pixels per tile side: one workgroup of 256 threads per tile, one thread per pixel */
+#define HN_MESH_MAX_SIDE 65535 /* image sides: pixel and tile coordinates stay exact in fp32 */
 int hn_mesh_project(const float* vertices_dev, long long n_vertices, const float* cam_dev, float* pix_dev, int32_t* flags_dev,
                     hnStream_t stream);
 int hn_mesh_bin_count(const int32_t* faces_dev, long long n_faces, const float* vertices_dev, const float* pix_dev,
@@ -911,6 +922,7 @@ int hn_ray_batch_rgba(const int64_t* perm_dev, long long n_perm, unsigned long l
  * undistort: exactly 10 Newton steps from the distorted point on  D x + 2 p1 x y + p2 (r + 2 x^2) = xd,
  * D y + 2 p2 x y + p1 (r + 2 y^2) = yd,  r = x^2 + y^2,  D = 1 + r (k1 + r (k2 + k3 r)); a step whose determinant is
  * within 1e-9 of zero moves nothing; skipped when all five coefficients are zero.  No NDC. */
+#define HN_NERFIES_CAM_FLOATS 24
 int hn_generate_rays_nerfies(int H, int W, const float* cam_dev, float near, float far, float image_id, int row_floats,
                              float* rays_dev, hnStream_t stream);
 
@@ -978,6 +990,7 @@ int hn_se3_warp_backward(const float* w, int w_ld, const float* v, int v_ld, con
  * folded per wave and, for the key of a workgroup's first pixel, per workgroup, before one add reaches memory.
  * hn_palette_map: index[i] = argmin over k < n_colors (1..256) of (r-pr)^2 + (g-pg)^2 + (b-pb)^2 in integers against
  * palette (n_colors, 3) uint8, the smallest k among equal distances; index (n,) uint8. */
+#define HN_HIST_BINS 262144 /* 2^18 cells of hn_color_hist's table, one per colour key */
 int hn_color_hist(const uint8_t* rgb_dev, long long n, unsigned long long* hist_dev, hnStream_t stream);
 int hn_palette_map(const uint8_t* rgb_dev, long long n, const uint8_t* palette_dev, int n_colors, uint8_t* index_dev,
                    hnStream_t stream);

@@ -3,8 +3,11 @@ declares, struct mirrors have the C sizes, module constructors / state_dict keys
 the reference's golden key lists, and ops refuse CPU tensors (no CPU fallback)."""
 import ctypes
 import glob
+import json
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +15,9 @@ import torch
 
 import hypernerf_torch_amd as HN
 from hypernerf_torch_amd import _lib as L
+from hypernerf_torch_amd import functional as F
 from hypernerf_torch_amd import machine
+from hypernerf_torch_amd.datasets import nerfies
 from hypernerf_torch_amd.hypernerf import model_utils, models, modules, warping
 from hypernerf_torch_amd.models import nerf as legacy_nerf
 from hypernerf_torch_amd.models import rendering as legacy_rendering
@@ -114,6 +119,148 @@ def test_abi_struct_sizes_match_c():
     assert c[1] == L.PACK_UNIT_DT.itemsize and c[2] == L.PACK_BIAS_DT.itemsize and c[3] == L.DWJOB_DT.itemsize
     assert c[4] == ctypes.sizeof(L.HnCompositeArgs)
     assert c[5] == L.FEAT_DT.itemsize and c[6] == ctypes.sizeof(L.HnSlot) and c[7] == ctypes.sizeof(L.HnSrc)
+
+
+RECORD_DTYPES = {"PACK_UNIT_DT": "HnPackUnit", "PACK_BIAS_DT": "HnPackBias", "FEAT_DT": "HnFeat", "DWJOB_DT": "HnDwJob",
+                 "DWREDUCE_DT": "HnDwReduceTile", "ADAM_RANGE_DT": "HnAdamRange"}
+
+
+def _ctypes_layout(cls):
+    return [[name, getattr(cls, name).offset, getattr(cls, name).size] for name, _ in cls._fields_]
+
+
+def test_derived_layout_equals_the_recorded_one(golden_dir):
+    """tests/golden/abi_layout_340.json holds (field, offset, size) and sizeof of the ctypes structs and numpy record
+    dtypes (with each field's format) the binding carried by hand at ABI 340, dumped before they were deleted.  What the
+    binding now derives from the header equals that record exactly."""
+    with open(os.path.join(golden_dir, "abi_layout_340.json")) as f:
+        rec = json.load(f)
+    assert len(rec["structs"]) == 11 and set(rec["dtypes"]) == set(RECORD_DTYPES)
+    for name, want in rec["structs"].items():
+        cls = getattr(L, name)
+        assert issubclass(cls, ctypes.Structure) and cls is L.STRUCTS[name]
+        assert _ctypes_layout(cls) == want["fields"] and ctypes.sizeof(cls) == want["sizeof"], name
+    for name, want in rec["dtypes"].items():
+        dt = getattr(L, name)
+        assert dt == np.dtype(L.STRUCTS[RECORD_DTYPES[name]])
+        got = [[k, dt.fields[k][1], dt.fields[k][0].itemsize, dt.fields[k][0].str] for k in dt.names]
+        assert got == want["fields"] and dt.itemsize == want["sizeof"], name
+    sizes = {"HnFeat": 8, "HnSrc": 32, "HnDst": 16, "HnSlot": 16, "HnMlpArgs": 2576, "HnPackUnit": 32, "HnPackBias": 16,
+             "HnDwJob": 104, "HnPackJob": 48, "HnDwBatch": 40, "HnDwReduceTile": 36, "HnEmbedReduce": 216,
+             "HnAdamRange": 16, "HnAdamFuse": 72, "HnCompositeArgs": 256, "HnDraw": 24, "HnPrologue": 96}
+    assert {name: ctypes.sizeof(cls) for name, cls in L.STRUCTS.items()} == sizes
+
+
+def _host_c_compiler():
+    """$CC, cc, gcc, clang, then the clang that ships beside hipcc: one of them exists wherever the library builds."""
+    hipcc = shutil.which(L.hipcc_path())
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc))) if hipcc else ""
+    beside = [os.path.join(rocm, *sub, "clang") for sub in (("lib", "llvm", "bin"), ("llvm", "bin"), ("bin",))] if rocm else []
+    for cand in [os.environ.get("CC"), "cc", "gcc", "clang"] + beside:
+        if cand and shutil.which(cand):
+            return shutil.which(cand)
+    raise AssertionError("no host C compiler found ($CC, cc, gcc, clang, the clang beside hipcc)")
+
+
+def test_derived_layout_matches_the_c_compiler(tmp_path):
+    """sizeof and every offsetof of all 17 ABI structs, as a host C compiler lays the real header out, against the ctypes
+    structs the binding derived from the same header: field by field, so two swapped fields of equal size show."""
+    assert len(L.STRUCTS) == 17
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "hn_kernels.h"', "int main(void) {"]
+    for name, cls in L.STRUCTS.items():
+        lines.append(f'  printf("{name} sizeof %zu\\n", sizeof({name}));')
+        lines += [f'  printf("{name} {field} %zu\\n", offsetof({name}, {field}));' for field, _ in cls._fields_]
+    lines += ["  return 0;", "}", ""]
+    src, exe = tmp_path / "abi_layout.c", tmp_path / "abi_layout"
+    src.write_text("\n".join(lines))
+    cc = subprocess.run([_host_c_compiler(), "-std=c99", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)],
+                        capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout
+    c_says = [(s, f, int(v)) for s, f, v in (line.split() for line in out.splitlines())]
+    binding = []
+    for name, cls in L.STRUCTS.items():
+        binding.append((name, "sizeof", ctypes.sizeof(cls)))
+        binding += [(name, field, getattr(cls, field).offset) for field, _ in cls._fields_]
+    assert len(binding) > 200 and c_says == binding, set(c_says) ^ set(binding)
+
+
+def test_header_constants_have_the_values_the_host_code_was_written_for():
+    """An independent guard on the parser, as the three spelled-out prototypes are: the 35 integer macros the header
+    defined at ABI 340 and the constants shared between host code and individual kernels, as literals."""
+    at_340 = dict(
+        HN_VERSION=340, HN_MODE_F32=0, HN_MODE_BF16=1, HN_MODE_BF16_S8=2, HN_MAX_SRC=8, HN_MAX_DST=4, HN_MAX_SLOTS=128,
+        HN_OP_WORDS=8, HN_CHUNK_UNITS=32, HN_DSRC_COMPS=32, HN_OP_LAYER=1, HN_ACT_NONE=0, HN_ACT_RELU=1,
+        HN_ACT_LEAKY_RELU=2, HN_ACT_ELU=3, HN_ACT_SOFTPLUS=4, HN_LAYER_NO_COMMIT=1, HN_LAYER_DIRECT=2, HN_OP_OUT=4,
+        HN_OP_OUT_WIDE=5, HN_BOP_LOAD=1, HN_BOP_LOAD_WIDE=2, HN_BOP_LAYER=3, HN_BOP_AUX=4, HN_MAX_COMPS=32,
+        HN_FEAT_ID_DIRECT=5, HN_FEAT_ZERO=0, HN_FEAT_ID=1, HN_FEAT_SIN=2, HN_FEAT_COS=3, HN_FEAT_SINP=4,
+        HN_BUILD_CONFIG_N=8, HN_MAX_PACK_JOBS=8, HN_MAX_WGRAD_BATCH=8, HN_MAX_DRAWS=8)
+    moved = dict(HN_SSIM_MAX_R=7, HN_MS_LEVELS=5, HN_MS_MAX_SIZE=11, HN_ISO_BLOCK=256, HN_EXTENT_TILE=2048,
+                 HN_SIMPLIFY_BITS=21, HN_MESH_TILE=16, HN_MESH_MAX_SIDE=65535, HN_NERFIES_CAM_FLOATS=24, HN_HIST_BINS=262144)
+    assert len(at_340) == 35 and L.CONSTANTS == {**at_340, **moved}
+    for name, value in {**at_340, **moved}.items():
+        if name != "HN_CHUNK_UNITS":     # the header holds the default of that build-time knob: the library's own value is used
+            assert type(getattr(L, name)) is int and getattr(L, name) == value, name
+    assert L.HN_CHUNK_UNITS ==(L.BUILD_CONFIG or {}).get("CHUNK_UNITS", int(os.environ.get("HN_CHUNK_UNITS", 32)))
+    assert L.HN_AUXG_MAX == 3 and "HN_AUXG_MAX" not in L.CONSTANTS
+    assert F.ISO_BLOCK == 256
+    assert F.EXTENT_TILE == 2048
+    assert F.MESH_TILE == 16
+    assert F.MESH_MAX_SIDE == 65535
+    assert F.HIST_BINS == 262144
+    assert F.CELL_BITS == 21
+    assert F.MSSSIM_LEVELS == 5
+    assert F.MSSSIM_MAX_SIZE == 11
+    assert F.SSIM_MAX_WINDOW == 15
+    assert F.NERFIES_CAM_FLOATS == 24
+    assert nerfies.CAM_FLOATS == 24
+
+
+def test_abi_parser_refuses_what_it_does_not_know():
+    """A member or macro outside the header's vocabulary raises, naming the struct and the declaration, or the macro
+    (never a guess); a snippet in the header's own style gives the fields it spells."""
+    consts, structs = L.parse_abi(
+        "#ifndef HN_SNIPPET_H\n#define HN_SNIPPET_H\n#define HN_N 3 /* rows */\n#define HN_MASK 0x1f\n"
+        "typedef struct {\n  int32_t a, b; /* two\n declarators */\n} HnInner;\n"
+        "typedef struct HnOuter {\n  float* p; const float* const* q;   /* two declarations */\n"
+        "  const HnInner* rows[HN_N];\n  HnInner by_value[2];\n  int8_t col[HN_N]; uint64_t big;\n} HnOuter;\n#endif\n")
+    assert consts == {"HN_N": 3, "HN_MASK": 31} and list(structs) == ["HnInner", "HnOuter"]
+    inner, p = structs["HnInner"], ctypes.c_void_p
+    assert inner._fields_ == [("a", ctypes.c_int32), ("b", ctypes.c_int32)]
+    assert structs["HnOuter"]._fields_ == [("p", p), ("q", p), ("rows", p * 3), ("by_value", inner * 2),
+                                           ("col", ctypes.c_int8 * 3), ("big", ctypes.c_uint64)]
+    assert issubclass(structs["HnOuter"], ctypes.Structure) and ctypes.sizeof(structs["HnOuter"]) == 72
+    for member, offender in (("double x;", r"HnBad.*double x"),
+                             ("int32_t flags : 3;", r"HnBad.*int32_t flags : 3"),
+                             ("union { int32_t i; float f; } u;", r"HnBad.*union \{ int32_t i"),
+                             ("struct { int32_t i; } s;", r"HnBad.*struct \{ int32_t i"),
+                             ("int32_t a[2][2];", r"HnBad.*int32_t a\[2\]\[2\]"),
+                             ("int32_t a[HN_UNKNOWN];", r"HnBad.*int32_t a\[HN_UNKNOWN\]"),
+                             ("float *x, y;", r"HnBad.*float \*x, y"),
+                             ("unsigned n;", r"HnBad.*unsigned n")):
+        with pytest.raises(L.HnError, match=offender):
+            L.parse_abi("typedef struct {\n  int32_t ok;\n  %s\n} HnBad;" % member)
+    with pytest.raises(L.HnError, match="HnLater"):                       # a struct by value must have been defined before
+        L.parse_abi("typedef struct { HnLater x; } HnBad;\ntypedef struct { float f; } HnLater;")
+    with pytest.raises(L.HnError, match="HnU"):
+        L.parse_abi("typedef union { int32_t i; float f; } HnU;")
+    with pytest.raises(L.HnError, match=r"HN_X.*\(1 << 3\)"):
+        L.parse_abi("#define HN_X (1 << 3)")
+    with pytest.raises(L.HnError, match="HN_LATE"):                       # an array size must be an EARLIER macro
+        L.parse_abi("typedef struct { int32_t a[HN_LATE]; } HnBad;\n#define HN_LATE 4")
+    for value in ("1u", "010", "1.5", "HN_OTHER", ""):
+        with pytest.raises(L.HnError, match="HN_X"):
+            L.parse_abi("#define HN_X %s\n" % value)
+
+
+def test_no_hand_written_copy_of_the_abi_is_left():
+    """The binding spells out no struct, no record dtype and no number the header defines."""
+    with open(os.path.join(ROOT, "hypernerf-torch_amd", "_lib.py")) as f:
+        text = f.read()
+    assert "_fields_ = [" not in text and "np.dtype([" not in text
+    targets = re.findall(r"^\s*(HN_\w+(?:\s*,\s*HN_\w+)*)\s*=\s*[-+(0-9]", text, flags=re.M)     # HN_A, HN_B = 1, 2
+    assigned = {name for names in targets for name in re.findall(r"\w+", names)}
+    assert assigned == {"HN_AUXG_MAX"} and not assigned & set(L.CONSTANTS)
 
 
 def test_argument_errors_are_reported_not_crashes():
