@@ -8,7 +8,7 @@ Drop-in module layout (same import paths as the reference, under this package):
     hypernerf_torch_amd.models.rendering.render_rays        <- models/rendering.py (nerf_pl signature)
     hypernerf_torch_amd.models.nerf.{Embedding,NeRF}        <- models/nerf.py
 Beside the reference's surface: hypernerf_torch_amd.geometry (density lattice of a frame, isosurface mesh, PLY files,
-mesh images by ray casting).
+mesh images by ray casting) and hypernerf_torch_amd.ops (metrics, data path, mesh and GIF ops, one module per kernel file).
 
 All device arithmetic runs in hand-written HIP kernels behind the C ABI in include/hn_kernels.h
 (csrc/libhn_hip.so).  There is no CPU execution path: ops raise on CPU tensors or a missing library.

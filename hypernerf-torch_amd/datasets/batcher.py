@@ -23,7 +23,7 @@ from typing import Iterator, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from .. import functional as F
+from .. import _lib as L
 
 
 def random_sampler_order(n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
@@ -120,7 +120,7 @@ class RayBatcher:
         """Raise if a gather read outside the permutation or the dataset (its rows were written as NaN).  Reads one
         device word: a host sync."""
         if int(self.state[2].item()) != 0:
-            raise F.L.HnError("the batch gather read past the end of the epoch's permutation or found an index outside "
+            raise L.HnError("the batch gather read past the end of the epoch's permutation or found an index outside "
                               "the dataset (the batch rows were NaN): the host's epoch bookkeeping is out of step")
 
     def begin_epoch(self) -> None:

@@ -2,7 +2,7 @@
 
 `transforms_{split}.json` is read on the host (focal in float64).  The RGBA images are decoded on the host one at a
 time, resized on the GPU as Pillow resizes an RGBA image — LANCZOS in premultiplied alpha, restated bit-exactly in HIP
-(functional.resize_lanczos_rgba8) — and kept on the device as uint8 RGBA: 4 bytes per ray where the reference's fp32
+(ops.data.resize_lanczos_rgba8) — and kept on the device as uint8 RGBA: 4 bytes per ray where the reference's fp32
 `all_rays` / `all_rgbs` take 44.  The training colour is the reference's blend onto white, `rgb * a + (1 - a)` in
 fp32; it is not a u8 / 255 value, so it is computed where it is consumed: by hn_blend_white_u8 for `all_rgbs` and the
 val / test samples, and inside the gather launch (hn_ray_batch_rgba) for a training run fed by `RayBatcher`.
@@ -18,6 +18,7 @@ import os
 import numpy as np
 import torch
 
+from ..ops import data as ops_data
 from . import image_io
 from .base import GpuRayDataset
 
@@ -63,9 +64,8 @@ class BlenderDataset(GpuRayDataset):
 
     # ---- images ----------------------------------------------------------------------------------
     def _to_device_resized(self, path: str) -> torch.Tensor:
-        from .. import functional as F
         x = torch.from_numpy(image_io.load_rgba8(path, use_pillow=self._use_pillow)).to(self.device)
-        return F.resize_lanczos_rgba8(x, self.img_wh)
+        return ops_data.resize_lanczos_rgba8(x, self.img_wh)
 
     def _load_train_images(self):
         """One image at a time is decoded, uploaded and resized (host memory: one decoded image, as the reference)."""
@@ -79,17 +79,15 @@ class BlenderDataset(GpuRayDataset):
     ray_cols = 8
 
     def _rays_of(self, c2w: torch.Tensor) -> torch.Tensor:
-        from .. import functional as F
         w, h = self.img_wh
-        return F.generate_rays(h, w, float(self.focal), c2w, near=self.near, far=self.far, ndc=False)
+        return ops_data.generate_rays(h, w, float(self.focal), c2w, near=self.near, far=self.far, ndc=False)
 
     def _build_all_rays(self) -> torch.Tensor:
         return torch.cat([self._rays_of(c) for c in self.c2w], 0)
 
     def _build_all_rgbs(self) -> torch.Tensor:
         """Every pixel blended onto white."""
-        from .. import functional as F
-        return F.blend_white_u8(self.rgba8)
+        return ops_data.blend_white_u8(self.rgba8)
 
     @property
     def n_rays(self) -> int:
@@ -100,10 +98,9 @@ class BlenderDataset(GpuRayDataset):
                      rgbs: torch.Tensor) -> None:
         """RayBatcher's launch: rows perm[cursor : cursor + rows] of all_rays / all_rgbs, gathered and blended from
         the RGBA stack by one launch (no NDC, 8 columns)."""
-        from .. import functional as F
         w, h = self.img_wh
-        F.ray_batch_rgba(perm, state, rows, h, w, float(self.focal), self.c2w, self.rgba8, rays, rgbs,
-                         near=self.near, far=self.far, ndc=False)
+        ops_data.ray_batch_rgba(perm, state, rows, h, w, float(self.focal), self.c2w, self.rgba8, rays, rgbs,
+                                near=self.near, far=self.far, ndc=False)
 
     def __len__(self):
         if self.split == 'train':
@@ -116,8 +113,7 @@ class BlenderDataset(GpuRayDataset):
         return -len(self.poses), min(len(self), len(self.poses))
 
     def _view(self, idx):
-        from .. import functional as F
         c2w = torch.tensor(self.poses[idx], dtype=torch.float32).to(self.device)
-        rgbs, valid_mask = F.blend_white_u8(self._to_device_resized(self.image_paths[idx]), with_mask=True)
+        rgbs, valid_mask = ops_data.blend_white_u8(self._to_device_resized(self.image_paths[idx]), with_mask=True)
         w, h = self.img_wh
         return {'rays': self._rays_of(c2w), 'rgbs': rgbs, 'c2w': c2w, 'valid_mask': valid_mask, 'hw': (h, w)}

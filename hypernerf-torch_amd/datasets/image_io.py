@@ -1,5 +1,5 @@
 """Host side of the dataset's image path: decoding an image file to 8-bit RGB (LLFF) or RGBA (Blender), and the
-coefficient tables of Pillow's LANCZOS resize that the GPU passes (functional.resize_lanczos_u8, hn_resample_u8) apply.
+coefficient tables of Pillow's LANCZOS resize that the GPU passes (ops.data.resize_lanczos_u8, hn_resample_u8) apply.
 
 Decoding uses Pillow when it imports (`Image.open(p).convert('RGB')`, what the reference's datasets/llff.py does);
 without Pillow a PNG decoder of the standard library (zlib) reads 8-bit greyscale, grey+alpha, RGB and RGBA files with
@@ -260,7 +260,7 @@ def unpremultiply_u8_reference(img: np.ndarray) -> np.ndarray:
 
 
 def resample_rgba8_reference(img: np.ndarray, size) -> np.ndarray:
-    """A NumPy statement of functional.resize_lanczos_rgba8 (tests): Pillow's LANCZOS resize of an (H, W, 4) RGBA
+    """A NumPy statement of ops.data.resize_lanczos_rgba8 (tests): Pillow's LANCZOS resize of an (H, W, 4) RGBA
     image — a copy at equal size, else premultiply, the two fixed-point passes on four channels, un-premultiply."""
     x = np.asarray(img, dtype=np.uint8)
     if x.ndim != 3 or x.shape[2] != 4:

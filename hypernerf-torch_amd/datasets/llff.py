@@ -1,7 +1,7 @@
 """The LLFF forward-facing dataset of the reference (datasets/llff.py), resident on the GPU.
 
 Pose math runs on the host in float64 NumPy (the reference's values); images are decoded on the host, resized on the
-GPU by Pillow's LANCZOS filter restated bit-exactly in HIP (functional.resize_lanczos_u8), and kept on the device as
+GPU by Pillow's LANCZOS filter restated bit-exactly in HIP (ops.data.resize_lanczos_u8), and kept on the device as
 uint8.  Rays are generated on the GPU (hn_generate_rays).  `all_rays` / `all_rgbs` — the reference's (N, 8|9) and
 (N, 3) fp32 tensors — are built on first access only: a training run fed by `RayBatcher` gathers each batch straight
 from the uint8 stack and the poses (hn_ray_batch) and never holds 36 bytes per ray.
@@ -15,6 +15,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from ..ops import data as ops_data
 from . import image_io
 from .base import GpuRayDataset, u8_to_unit
 
@@ -166,9 +167,8 @@ class LLFFDataset(GpuRayDataset):
         return img
 
     def _to_device_resized(self, img: np.ndarray) -> torch.Tensor:
-        from .. import functional as F
         x = torch.from_numpy(img).to(self.device)
-        return F.resize_lanczos_u8(x, self.img_wh)
+        return ops_data.resize_lanczos_u8(x, self.img_wh)
 
     def _load_train_images(self):
         """Every image's aspect ratio is checked from its header before any pixel reaches the device; then one image
@@ -187,10 +187,9 @@ class LLFFDataset(GpuRayDataset):
 
     # ---- rays --------------------------------------------------------------------------------------
     def _rays_of(self, c2w: torch.Tensor, image_id: Optional[int]) -> torch.Tensor:
-        from .. import functional as F
         w, h = self.img_wh
-        return F.generate_rays(h, w, float(self.focal), c2w, near=float(self.near), far=float(self.far),
-                               ndc=not self.spheric_poses, ndc_near=1.0, image_id=image_id)
+        return ops_data.generate_rays(h, w, float(self.focal), c2w, near=float(self.near), far=float(self.far),
+                                      ndc=not self.spheric_poses, ndc_near=1.0, image_id=image_id)
 
     def _build_all_rays(self) -> torch.Tensor:
         return torch.cat([self._rays_of(self.c2w[k], i if self.include_idx else None)
@@ -205,11 +204,10 @@ class LLFFDataset(GpuRayDataset):
                      rgbs: torch.Tensor) -> None:
         """RayBatcher's launch: rows perm[cursor : cursor + rows] of all_rays / all_rgbs, gathered from the uint8 stack
         and the poses by one launch."""
-        from .. import functional as F
         w, h = self.img_wh
-        F.ray_batch(perm, state, rows, h, w, float(self.focal), self.c2w, self.rgb8, rays, rgbs,
-                    near=float(self.near), far=float(self.far), ndc=not self.spheric_poses, ndc_near=1.0,
-                    image_ids=self.image_ids)
+        ops_data.ray_batch(perm, state, rows, h, w, float(self.focal), self.c2w, self.rgb8, rays, rgbs,
+                           near=float(self.near), far=float(self.far), ndc=not self.spheric_poses, ndc_near=1.0,
+                           image_ids=self.image_ids)
 
     def __len__(self):
         if self.split == 'train':

@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
+from ..ops import data as ops_data
 from . import image_io
 from .base import GpuRayDataset, u8_to_unit
 
@@ -256,10 +257,9 @@ class NerfiesDataset(GpuRayDataset):
         return torch.from_numpy(self.camera_table[idx]).to(self.device)
 
     def _rays_of(self, cam: torch.Tensor, image_id: int) -> torch.Tensor:
-        from .. import functional as F
         w, h = self.img_wh
-        return F.generate_rays_nerfies(h, w, cam, near=self.near, far=self.far,
-                                       image_id=image_id if self.include_idx else None)
+        return ops_data.generate_rays_nerfies(h, w, cam, near=self.near, far=self.far,
+                                              image_id=image_id if self.include_idx else None)
 
     def _build_all_rays(self) -> torch.Tensor:
         return torch.cat([self._rays_of(self.cams[k], i) for k, i in enumerate(self.metadata_ids)], 0)
@@ -273,10 +273,9 @@ class NerfiesDataset(GpuRayDataset):
                      rgbs: torch.Tensor) -> None:
         """RayBatcher's launch: rows perm[cursor : cursor + rows] of all_rays / all_rgbs, gathered from the uint8 stack
         and the camera table by one launch."""
-        from .. import functional as F
         w, h = self.img_wh
-        F.ray_batch_nerfies(perm, state, rows, h, w, self.cams, self.rgb8, rays, rgbs, near=self.near, far=self.far,
-                            image_ids=self.image_ids)
+        ops_data.ray_batch_nerfies(perm, state, rows, h, w, self.cams, self.rgb8, rays, rgbs, near=self.near,
+                                   far=self.far, image_ids=self.image_ids)
 
     def __len__(self):
         return self.n_rays if self.split == 'train' else len(self.ids)

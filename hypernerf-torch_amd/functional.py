@@ -2,6 +2,11 @@
 
 PyTorch is used for device memory, streams and the autograd graph only; all arithmetic of the
 hot path happens in the HIP kernels.  Every function here raises if handed a CPU tensor.
+
+This module holds the training step: precision mode, MLP programs, weight-gradient scheduling, the GLO embedding,
+sampling, draws, the step prologue, compositing, the loss heads, SE(3) and the stand-alone encoders.  Metrics, the data
+path, meshes and the GIF quantiser live in ops/, one module per kernel source file; their public names (each module's
+__all__) stay reachable here.
 """
 from __future__ import annotations
 
@@ -14,6 +19,13 @@ import torch
 from . import _lib as L
 from .arena import ParamArena
 from .machine import MlpRunner, PendingWgrad, Program, ResolvedWgrad, launch_resolved_wgrads, resolve_pending
+from .ops.checks import INT32_MAX           # noqa: F401
+from .ops.data import *                     # noqa: F401,F403
+from .ops.gif import *                      # noqa: F401,F403
+from .ops.mesh import *                     # noqa: F401,F403
+from .ops.mesh_render import *              # noqa: F401,F403
+from .ops.metrics import *                  # noqa: F401,F403
+from .ops.simplify import *                 # noqa: F401,F403
 
 _PRECISION = os.environ.get("HN_PRECISION", "bf16")
 
@@ -994,1182 +1006,6 @@ def bg_loss(warped: torch.Tensor, points: torch.Tensor, scale: float) -> torch.T
     if not scale > 0:
         raise ValueError(f"bg_loss: scale must be positive, got {scale}")
     return _BgLossFn.apply(warped, points, float(scale))
-
-
-# --------------------------------------------------------------------------------------------
-# SSIM (metrics.py:15-20: kornia's ssim loss)
-# --------------------------------------------------------------------------------------------
-SSIM_MAX_WINDOW = 2 * L.HN_SSIM_MAX_R + 1    # hn_ssim_*: odd windows 3 .. 15
-_SSIM_WINDOWS: Dict[int, C.Array] = {}
-
-
-def ssim_window(window_size: int) -> torch.Tensor:
-    """kornia's get_gaussian_kernel1d(window_size, 1.5) (kornia/filters/kernels.py `gaussian`), computed by torch in
-    fp32 on the CPU: the kernels take these weights as they are."""
-    x = torch.arange(window_size).float() - window_size // 2
-    if window_size % 2 == 0:
-        x = x + 0.5
-    g = torch.exp(-x.pow(2.0) / float(2 * 1.5 ** 2))
-    return g / g.sum()
-
-
-def _ssim_window_host(window_size: int):
-    buf = _SSIM_WINDOWS.get(window_size)
-    if buf is None:
-        buf = _SSIM_WINDOWS[window_size] = (C.c_float * window_size)(*ssim_window(window_size).tolist())
-    return buf
-
-
-def _ssim_check(pred, gt, window_size, reduction):
-    if not isinstance(window_size, int) or window_size < 3 or window_size % 2 == 0:
-        raise ValueError(f"ssim: window_size must be an odd integer >= 3, got {window_size!r}")
-    if window_size > SSIM_MAX_WINDOW:
-        raise ValueError(f"ssim: window_size {window_size} is above the kernels' limit of {SSIM_MAX_WINDOW}")
-    if reduction not in ("mean", "sum", "none"):
-        raise ValueError(f"ssim: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
-    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
-        raise ValueError("ssim: pred and gt must be tensors")
-    if pred.dim() != 4 or pred.shape != gt.shape:
-        raise ValueError(f"ssim: pred and gt must both be (N, C, H, W) of one shape, got {tuple(pred.shape)} and "
-                         f"{tuple(gt.shape)}")
-    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError("ssim: pred and gt must be float32")
-    h, w = pred.shape[2], pred.shape[3]
-    if h <= window_size // 2 or w <= window_size // 2:
-        raise ValueError(f"ssim: H and W must be larger than window_size // 2 = {window_size // 2} (reflect padding), "
-                         f"got {h} x {w}")
-    if pred.numel() == 0:
-        raise ValueError("ssim: empty images")
-
-
-class _SsimFn(torch.autograd.Function):
-    """The dssim map (`none`) or its sum (`mean` / `sum`): hn_ssim_forward / hn_ssim_backward."""
-
-    @staticmethod
-    def forward(ctx, pred, gt, window_size, c1, c2, eps, want_map):
-        L.load()
-        x, y = pred.detach(), gt.detach()
-        n, c, h, w = x.shape
-        args = (L.ptr(x), (C.c_int64 * 4)(*x.stride()), L.ptr(y), (C.c_int64 * 4)(*y.stride()), n, c, h, w,
-                _ssim_window_host(window_size), window_size, c1, c2, eps)
-        if want_map:
-            out = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-            L.launch("hn_ssim_forward", *args, L.ptr(out), None, None, L.stream_handle())
-        else:
-            nbytes = C.c_int64(0)
-            L.check(L.load().hn_ssim_workspace_bytes(n, c, h, w, window_size, C.byref(nbytes)), "hn_ssim_workspace_bytes")
-            ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=x.device)
-            out = torch.empty((), dtype=torch.float32, device=x.device)
-            L.launch("hn_ssim_forward", *args, None, L.ptr(out), L.ptr(ws), L.stream_handle())
-        ctx.save_for_backward(x, y)
-        ctx.cfg = (window_size, c1, c2, eps, want_map)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, y = ctx.saved_tensors
-        window_size, c1, c2, eps, want_map = ctx.cfg
-        need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_x or need_y):
-            return (None,) * 7
-        if not need_x:          # S is symmetric in its two images: d/dgt is d/dpred with the roles swapped
-            x, y = y, x
-        n, c, h, w = x.shape
-        g = g.detach().float().contiguous()
-        d_first = torch.empty((n, c, h, w), dtype=torch.float32, device=x.device)
-        d_second = torch.empty_like(d_first) if (need_x and need_y) else None
-        L.launch("hn_ssim_backward", L.ptr(x), (C.c_int64 * 4)(*x.stride()), L.ptr(y), (C.c_int64 * 4)(*y.stride()),
-                 n, c, h, w, _ssim_window_host(window_size), window_size, c1, c2, eps,
-                 None if want_map else L.ptr(g), L.ptr(g) if want_map else None, L.ptr(d_first), L.ptr(d_second),
-                 L.stream_handle())
-        if need_x:
-            return d_first, d_second, None, None, None, None, None
-        return None, d_first, None, None, None, None, None
-
-
-def ssim_dssim(pred: torch.Tensor, gt: torch.Tensor, window_size: int = 3, max_val: float = 1.0, eps: float = 1e-12,
-               reduction: str = 'mean') -> torch.Tensor:
-    """kornia's structural dissimilarity (kornia.losses.ssim_loss, 0.6.1): clamp((1 - SSIM) / 2, 0, 1) of (N, C, H, W)
-    fp32 images on the GPU, the 2-D Gaussian window (sigma 1.5) over reflect padding, reduced by 'mean', 'sum' or
-    'none' (the per-pixel map).  Any element strides (e.g. an (H, W, 3) image as `permute(2, 0, 1)[None]`).
-    Differentiable in both images; the sum is bit-reproducible run to run."""
-    _ssim_check(pred, gt, window_size, reduction)
-    L.require_gpu(pred, gt)
-    c1, c2 = (0.01 * max_val) ** 2, (0.03 * max_val) ** 2
-    out = _SsimFn.apply(pred, gt, window_size, c1, c2, float(eps), reduction == 'none')
-    if reduction == 'mean':
-        out = out / pred.numel()
-    return out
-
-
-# --------------------------------------------------------------------------------------------
-# multi-scale SSIM (the metric the Nerfies / HyperNeRF tables report)
-# --------------------------------------------------------------------------------------------
-MSSSIM_LEVELS = L.HN_MS_LEVELS
-MSSSIM_MAX_SIZE = L.HN_MS_MAX_SIZE    # hn_msssim_forward: window sizes 1 .. 11
-MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
-_MSSSIM_TILE_W, _MSSSIM_TILE_H = 32, 16
-_MSSSIM_PLANS: Dict[tuple, tuple] = {}
-
-
-def msssim_window(size: int) -> torch.Tensor:
-    """The 1-D taps of one level's window, float64: exp(-x^2 / (2 sigma^2)) with sigma = size * 1.5 / 11 at the integer
-    offsets -(size//2) .. size//2 (odd size) or the half-integer offsets -(size/2) + 0.5 .. size/2 - 0.5 (even size),
-    normalised to sum 1.  Their outer product is the normalised 2-D Gaussian of the original exactly."""
-    sigma = size * 1.5 / MSSSIM_MAX_SIZE
-    x = torch.arange(size, dtype=torch.float64) - (size - 1) / 2.0
-    g = torch.exp(-x * x / (2.0 * sigma * sigma))
-    return g / g.sum()
-
-
-def msssim_pyramid(h: int, w: int):
-    """[(h_l, w_l, size_l)] of the five levels: sides halve rounding up, size_l = min(11, h_l, w_l)."""
-    out = []
-    for _ in range(MSSSIM_LEVELS):
-        out.append((h, w, min(MSSSIM_MAX_SIZE, h, w)))
-        h, w = (h + 1) // 2, (w + 1) // 2
-    return out
-
-
-def msssim_workspace_bytes(n: int, c: int, h: int, w: int) -> int:
-    """hn_msssim_workspace_bytes in Python: the planes of levels 1 .. 4 of both images, then two partial sums per
-    32 x 16 tile of every plane of levels 0 .. 4, in floats, rounded up to 16 bytes."""
-    pyr = msssim_pyramid(h, w)
-    floats = sum(2 * n * c * hl * wl for hl, wl, _ in pyr[1:])
-    floats += sum(2 * n * c * (-(-wl // _MSSSIM_TILE_W)) * (-(-hl // _MSSSIM_TILE_H)) for hl, wl, _ in pyr)
-    return (floats * 4 + 15) // 16 * 16
-
-
-def _msssim_plan(n, c, h, w):
-    """(taps, sizes, workspace floats) of a shape: host arrays built once (float64 taps rounded to fp32)."""
-    plan = _MSSSIM_PLANS.get((n, c, h, w))
-    if plan is None:
-        sizes = [s for _, _, s in msssim_pyramid(h, w)]
-        taps = (C.c_float * (MSSSIM_LEVELS * MSSSIM_MAX_SIZE))()
-        for l, s in enumerate(sizes):
-            for i, v in enumerate(msssim_window(s).tolist()):
-                taps[l * MSSSIM_MAX_SIZE + i] = v
-        nbytes = C.c_int64(0)
-        L.check(L.load().hn_msssim_workspace_bytes(n, c, h, w, C.byref(nbytes)), "hn_msssim_workspace_bytes")
-        plan = _MSSSIM_PLANS[(n, c, h, w)] = (taps, (C.c_int * MSSSIM_LEVELS)(*sizes), nbytes.value // 4)
-    return plan
-
-
-@torch.no_grad()
-def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) -> torch.Tensor:
-    """(N, 5, 2) fp32: per image and pyramid level the mean SSIM and the mean contrast-structure term of multi-scale
-    SSIM (hn_msssim_forward: one launch per level and one that adds the tiles' sums, bit-reproducible).  pred / gt:
-    (N, C, H, W) fp32 on the GPU, any element strides, any H, W >= 1 (the window shrinks to min(11, h, w)).  A metric:
-    the result carries no gradient.  The host plan (taps, sizes, workspace size) is cached per shape; the workspace
-    itself comes from torch's allocator at every call, as ssim_dssim's does, so a call captured in a HIP graph takes it
-    from the graph's pool and the host arrays are consumed at the launch."""
-    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
-        raise ValueError("ms_ssim: pred and gt must be tensors")
-    if pred.dim() != 4 or pred.shape != gt.shape:
-        raise ValueError(f"ms_ssim: pred and gt must both be (N, C, H, W) of one shape, got {tuple(pred.shape)} and "
-                         f"{tuple(gt.shape)}")
-    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError("ms_ssim: pred and gt must be float32")
-    if pred.numel() == 0:
-        raise ValueError("ms_ssim: empty images")
-    L.require_gpu(pred, gt)
-    x, y = pred.detach(), gt.detach()
-    n, c, h, w = x.shape
-    taps, sizes, ws_floats = _msssim_plan(n, c, h, w)
-    ws = torch.empty(ws_floats, dtype=torch.float32, device=x.device)
-    out = torch.empty((n, MSSSIM_LEVELS, 2), dtype=torch.float32, device=x.device)
-    L.launch("hn_msssim_forward", L.ptr(x), (C.c_int64 * 4)(*x.stride()), L.ptr(y), (C.c_int64 * 4)(*y.stride()),
-             n, c, h, w, taps, sizes, (0.01 * max_val) ** 2, (0.03 * max_val) ** 2, L.ptr(out), L.ptr(ws),
-             L.stream_handle())
-    return out
-
-
-# --------------------------------------------------------------------------------------------
-# geometry out of a trained field (csrc/hn_geometry.hip)
-# --------------------------------------------------------------------------------------------
-ISO_BLOCK = L.HN_ISO_BLOCK    # lattice points (cells) per workgroup of the hn_iso_* passes
-INT32_MAX = 2 ** 31 - 1
-
-
-def check_lattice(shape, bounds, what: str):
-    """(nx, ny, nz) and the six bounds of a lattice as the hn_geometry entry points accept them, or ValueError."""
-    try:
-        nx, ny, nz = (int(v) for v in shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: the lattice must have three sides, got {shape!r}") from None
-    if min(nx, ny, nz) < 2:
-        raise ValueError(f"{what}: every side of the lattice needs at least 2 points, got {(nx, ny, nz)}")
-    if 7 * nx * ny * nz > INT32_MAX:
-        raise ValueError(f"{what}: 7 * {nx} * {ny} * {nz} = {7 * nx * ny * nz} edge slots exceed the int32 limit "
-                         f"2**31 - 1 = {INT32_MAX} of the mesh indices")
-    try:
-        bounds = tuple(float(v) for v in bounds)
-    except (TypeError, ValueError):
-        bounds = ()
-    if len(bounds) != 6:
-        raise ValueError(f"{what}: bounds must be (xmin, xmax, ymin, ymax, zmin, zmax), got {bounds!r}")
-    if not all(hi > lo for lo, hi in zip(bounds[0::2], bounds[1::2])):
-        raise ValueError(f"{what}: bounds need hi > lo on every axis, got {bounds}")
-    return (nx, ny, nz), bounds
-
-
-@torch.no_grad()
-def grid_points(shape, bounds, start: int, count: int, device) -> torch.Tensor:
-    """(count, 3) fp32: lattice points start .. start + count - 1 of the (nx, ny, nz) lattice over `bounds`
-    (hn_grid_points), p = (i*ny + j)*nz + k at lo + (i, j, k) * (hi - lo)/(n - 1); indices past the lattice repeat its last
-    point.  float32 NumPy gives the same bits."""
-    (nx, ny, nz), bounds = check_lattice(shape, bounds, "grid_points")
-    if not 0 <= start < nx * ny * nz or not 0 < count <= INT32_MAX:
-        raise ValueError(f"grid_points: start {start} / count {count} outside the lattice of {nx * ny * nz} points")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise L.HnError("hypernerf_torch_amd runs on MI355X only: grid_points needs a GPU device")
-    L.load()
-    out = torch.empty((count, 3), dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        L.launch("hn_grid_points", nx, ny, nz, (C.c_float * 6)(*bounds), start, count, L.ptr(out),
-                 L.stream_handle())
-    return out
-
-
-@torch.no_grad()
-def density_activate(raw: torch.Tensor, points: torch.Tensor, render_opts=None) -> torch.Tensor:
-    """Raw densities (...,) of points (..., 3) -> Softplus, then filter_sigma (dust threshold, bounding box) exactly as the
-    compositing kernel applies them (hn_density_activate), as fp32 of raw's shape."""
-    L.require_gpu(raw, points)
-    L.load()
-    raw = raw.detach().float().contiguous()
-    has_dust, dust, box = 0, 0.0, None
-    if render_opts is not None:
-        if 'dust_threshold' in render_opts:
-            has_dust, dust = 1, float(render_opts.get('dust_threshold', 0.0))
-        if 'bounding_box' in render_opts:
-            box = (C.c_float * 6)(*(float(v) for v in render_opts['bounding_box']))
-            points = points.detach().float().contiguous()
-            if points.shape != raw.shape + (3,):
-                raise ValueError(f"density_activate: points {tuple(points.shape)} do not match raw {tuple(raw.shape)}")
-    out = torch.empty_like(raw)
-    if raw.numel():
-        L.launch("hn_density_activate", L.ptr(raw), L.ptr(points) if box is not None else None, raw.numel(),
-                 has_dust, dust, box, L.ptr(out), L.stream_handle())
-    return out
-
-
-@torch.no_grad()
-def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torch.Tensor]:
-    """Indexed triangle mesh of the surface grid = iso by marching tetrahedra (hn_iso_*): grid (nx, ny, nz) fp32,
-    C-contiguous, on the GPU, its points spread over bounds (xmin, xmax, ymin, ymax, zmin, zmax) ->
-    {'vertices': (V, 3) fp32, 'normals': (V, 3) fp32 unit (from inside, grid >= iso, to outside), 'faces': (F, 3) int32}.
-    Vertices ascend with their edge slot, faces with cell, tetrahedron, triangle: the same grid gives the same arrays on
-    every run.  An empty surface gives zero-length tensors.  Working memory: 28 bytes of edge slots + 1 of marks per
-    lattice point.  Two host synchronisations (the vertex and the face count size the outputs)."""
-    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
-        raise ValueError("extract_isosurface: grid must be a (nx, ny, nz) tensor")
-    (nx, ny, nz), bounds = check_lattice(grid.shape, bounds, "extract_isosurface")
-    if grid.dtype != torch.float32:
-        raise ValueError(f"extract_isosurface: grid must be float32, got {grid.dtype}")
-    if not grid.is_contiguous():
-        raise ValueError("extract_isosurface: grid must be C-contiguous")
-    if not grid.is_cuda:
-        raise ValueError("extract_isosurface: grid must live on the GPU (there is no CPU fallback)")
-    L.load()
-    f = grid.detach()
-    dev = f.device
-    empty = {'vertices': torch.zeros((0, 3), dtype=torch.float32, device=dev),
-             'normals': torch.zeros((0, 3), dtype=torch.float32, device=dev),
-             'faces': torch.zeros((0, 3), dtype=torch.int32, device=dev)}
-    n = nx * ny * nz
-    iso = float(iso)
-    with torch.cuda.device(dev):
-        stream = L.stream_handle()
-        # pass A: marks and per-workgroup counts; the scan of the counts is torch's
-        mask = torch.empty(n, dtype=torch.uint8, device=dev)
-        counts = torch.empty((n + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
-        L.launch("hn_iso_mark", L.ptr(f), nx, ny, nz, iso, L.ptr(mask), L.ptr(counts), stream)
-        ends = torch.cumsum(counts, 0, dtype=torch.int64)
-        n_vertices = int(ends[-1])
-        if n_vertices == 0:
-            return empty
-        # pass B
-        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
-        normals = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
-        slots = torch.empty(7 * n, dtype=torch.int32, device=dev)
-        offsets = ends - counts
-        L.launch("hn_iso_vertices", L.ptr(f), nx, ny, nz, (C.c_float * 6)(*bounds), iso, L.ptr(mask),
-                 L.ptr(offsets), L.ptr(vertices), L.ptr(normals), L.ptr(slots), stream)
-        # pass C: count, scan, emit
-        n_cells = (nx - 1) * (ny - 1) * (nz - 1)
-        fcounts = torch.empty((n_cells + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
-        L.launch("hn_iso_faces", L.ptr(f), nx, ny, nz, iso, None, None, L.ptr(fcounts), None, stream)
-        fends = torch.cumsum(fcounts, 0, dtype=torch.int64)
-        n_faces = int(fends[-1])
-        if n_faces > INT32_MAX:
-            raise ValueError(f"extract_isosurface: {n_faces} faces exceed the int32 limit 2**31 - 1 = {INT32_MAX}")
-        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
-        if n_faces:
-            foffsets = fends - fcounts
-            L.launch("hn_iso_faces", L.ptr(f), nx, ny, nz, iso, L.ptr(slots), L.ptr(foffsets), None,
-                     L.ptr(faces), stream)
-    return {'vertices': vertices, 'normals': normals, 'faces': faces}
-
-
-def _check_faces(faces, num_vertices, what: str):
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{what}: faces must be a (F, 3) tensor")
-    if faces.dtype != torch.int32:
-        raise ValueError(f"{what}: faces must be int32, got {faces.dtype}")
-    v = int(num_vertices)
-    if v < 0 or v > INT32_MAX or faces.shape[0] > INT32_MAX:
-        raise ValueError(f"{what}: {v} vertices / {faces.shape[0]} faces outside 0 .. 2**31 - 1 = {INT32_MAX}")
-    if not faces.is_cuda:
-        raise ValueError(f"{what}: faces must live on the GPU (there is no CPU fallback)")
-    return faces.detach().contiguous(), v
-
-
-@torch.no_grad()
-def mesh_components(faces: torch.Tensor, num_vertices: int, out: Optional[torch.Tensor] = None,
-                    return_rounds: bool = False):
-    """labels (V,) int32 of the mesh faces (F, 3) int32 over V vertices: the SMALLEST vertex id of the vertex's connected
-    component (two vertices are connected when a face holds both; an unreferenced vertex is its own component) — a
-    definition that no scheduling can change, so two runs give the same bits (hn_cc_init / hn_cc_round: hook and
-    pointer-jump rounds with integer atomicMin).  One host read of two ints per round; the loop is capped at V + 1 rounds
-    (min-label propagation needs at most V - 1 that change something, every round here does at least its step) and a
-    RuntimeError names the cap if it is ever exceeded.  A vertex id outside [0, V) is a ValueError; nothing is written
-    outside the label array.  `out`: a contiguous (V,) int32 tensor to label in place.  `return_rounds`: (labels, rounds
-    run, the last one included that changed nothing)."""
-    faces, v = _check_faces(faces, num_vertices, "mesh_components")
-    dev = faces.device
-    if out is None:
-        out = torch.empty(v, dtype=torch.int32, device=dev)
-    elif out.dtype != torch.int32 or out.shape != (v,) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"mesh_components: out must be a contiguous ({v},) int32 tensor on {dev}")
-    n_faces = faces.shape[0]
-    rounds = 0
-    if v == 0 and n_faces == 0:
-        return (out, rounds) if return_rounds else out
-    L.load()
-    cap = v + 1
-    with torch.cuda.device(dev):
-        stream = L.stream_handle()
-        flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        L.launch("hn_cc_init", L.ptr(faces) if n_faces else None, n_faces, L.ptr(out) if v else None, v,
-                 L.ptr(flags), stream)
-        if n_faces == 0:
-            return (out, rounds) if return_rounds else out
-        if v == 0:
-            raise ValueError("mesh_components: faces hold a vertex id outside [0, 0)")
-        while True:
-            rounds += 1
-            if rounds > cap:
-                raise RuntimeError(f"mesh_components: no fixed point after the cap of V + 1 = {cap} rounds")
-            L.launch("hn_cc_round", L.ptr(faces), n_faces, L.ptr(out), v, rounds, L.ptr(flags), stream)
-            err, changed = flags.tolist()
-            if err:
-                raise ValueError(f"mesh_components: faces hold a vertex id outside [0, {v})")
-            if changed != rounds:
-                break
-    return (out, rounds) if return_rounds else out
-
-
-@torch.no_grad()
-def component_sizes(labels: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
-    """(V,) int32: the number of faces of every component at index = its label (mesh_components), zero elsewhere
-    (hn_cc_sizes: integer atomic adds, whose sum does not depend on their order).  No host synchronisation: an id or a
-    label outside [0, V) is skipped (mesh_components refuses such faces first)."""
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype != torch.int32:
-        raise ValueError("component_sizes: labels must be a (V,) int32 tensor")
-    faces, v = _check_faces(faces, labels.shape[0], "component_sizes")
-    L.require_gpu(labels)
-    sizes = torch.zeros(v, dtype=torch.int32, device=faces.device)
-    if v and faces.shape[0]:
-        L.load()
-        with torch.cuda.device(faces.device):
-            flags = torch.zeros(2, dtype=torch.int32, device=faces.device)
-            L.launch("hn_cc_sizes", L.ptr(labels.detach().contiguous()), L.ptr(faces), faces.shape[0], v,
-                     L.ptr(sizes), L.ptr(flags), L.stream_handle())
-    return sizes
-
-
-@torch.no_grad()
-def gather_rows(src: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
-    """src[index] along the first dimension for an int32 index (hn_gather_rows): any dtype, any trailing shape."""
-    L.require_gpu(src, index)
-    src = src.detach().contiguous()
-    n = index.shape[0]
-    out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
-    if out.numel():
-        L.load()
-        row_bytes = out.numel() // n * out.element_size()
-        with torch.cuda.device(src.device):
-            L.launch("hn_gather_rows", L.ptr(src), src.shape[0], L.ptr(index), n, row_bytes, L.ptr(out),
-                     L.stream_handle())
-    return out
-
-
-@torch.no_grad()
-def compact_mesh(faces: torch.Tensor, labels: torch.Tensor, keep_comp: torch.Tensor):
-    """(vertex_index (V',) int32, faces (F', 3) int32): the vertices whose component is kept (keep_comp: (V,) bool or
-    uint8 indexed by label) in their old order, and the faces of those components in their old order, re-indexed
-    (hn_mesh_keep, two torch.cumsum scans, hn_mesh_compact).  One host read (both counts at once) sizes the outputs."""
-    faces, v = _check_faces(faces, labels.shape[0], "compact_mesh")
-    dev = faces.device
-    n_faces = faces.shape[0]
-    if v == 0:
-        return torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
-    L.load()
-    keep_comp = keep_comp.to(torch.uint8).contiguous()
-    with torch.cuda.device(dev):
-        stream = L.stream_handle()
-        vkeep = torch.empty(v, dtype=torch.int32, device=dev)
-        fkeep = torch.empty(max(n_faces, 1), dtype=torch.int32, device=dev)
-        if n_faces == 0:
-            fkeep.zero_()
-        L.launch("hn_mesh_keep", L.ptr(labels.contiguous()), L.ptr(faces) if n_faces else None, L.ptr(keep_comp),
-                 v, n_faces, L.ptr(vkeep), L.ptr(fkeep), stream)
-        vscan = torch.cumsum(vkeep, 0, dtype=torch.int32)
-        fscan = torch.cumsum(fkeep, 0, dtype=torch.int32)
-        n_v, n_f = torch.stack([vscan[-1], fscan[-1]]).tolist()
-        vertex_index = torch.empty(n_v, dtype=torch.int32, device=dev)
-        faces_out = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
-        if n_v:
-            L.launch("hn_mesh_compact", L.ptr(faces) if n_faces else None, L.ptr(vscan), L.ptr(fscan), v, n_faces,
-                     n_v, n_f, L.ptr(vertex_index), L.ptr(faces_out) if n_f else None, stream)
-    return vertex_index, faces_out
-
-
-@torch.no_grad()
-def vertex_viewdirs(vertices: torch.Tensor, normals: Optional[torch.Tensor], start: int, count: int,
-                    camera=None) -> torch.Tensor:
-    """(count, 3) fp32 unit directions for vertices start .. start + count - 1 (hn_vertex_viewdirs; rows past the mesh
-    repeat its last vertex): -normal/|normal| when `camera` is None, else (v - camera)/|v - camera| for the three host
-    floats `camera`; a zero length gives (0, 0, 1).  float32 NumPy gives the same values to a few roundings."""
-    L.require_gpu(vertices, normals)
-    ref = vertices if camera is not None else normals
-    if ref is None or ref.dim() != 2 or ref.shape[1] != 3 or ref.dtype != torch.float32:
-        raise ValueError("vertex_viewdirs: vertices / normals must be (V, 3) float32")
-    v = ref.shape[0]
-    if not 0 <= start < v or not 0 < count <= INT32_MAX:
-        raise ValueError(f"vertex_viewdirs: start {start} / count {count} outside the mesh of {v} vertices")
-    L.load()
-    ref = ref.detach().contiguous()
-    out = torch.empty((count, 3), dtype=torch.float32, device=ref.device)
-    cam = None if camera is None else (C.c_float * 3)(*(float(x) for x in camera))
-    with torch.cuda.device(ref.device):
-        L.launch("hn_vertex_viewdirs", L.ptr(ref) if camera is not None else None,
-                 L.ptr(ref) if camera is None else None, v, start, count, cam, L.ptr(out),
-                 L.stream_handle())
-    return out
-
-
-# --------------------------------------------------------------------------------------------
-# mesh simplification by vertex clustering (csrc/hn_simplify.hip)
-# --------------------------------------------------------------------------------------------
-CELL_BITS = L.HN_SIMPLIFY_BITS    # bits per axis of a cell key: fewer than 2**21 cells along every axis
-
-
-def _float3(x, what: str):
-    try:
-        seq = x.tolist() if hasattr(x, "tolist") else x
-        vals = [float(v) for v in seq] if isinstance(seq, (list, tuple)) else [float(seq)] * 3
-    except (TypeError, ValueError):
-        vals = []
-    if len(vals) != 3:
-        raise ValueError(f"{what} must be a number or three numbers, got {x!r}")
-    return vals
-
-
-def check_cells(cell, origin, what: str):
-    """(cell, origin) as two (c_float * 3) host arrays, or ValueError: every cell side positive and finite (also once
-    rounded to float32), every origin finite."""
-    import math
-    cell = (C.c_float * 3)(*_float3(cell, f"{what}: cell"))
-    origin = (C.c_float * 3)(*_float3(origin, f"{what}: origin"))
-    if not all(math.isfinite(c) and c > 0.0 for c in cell):
-        raise ValueError(f"{what}: every cell side must be positive and finite, got {list(cell)}")
-    if not all(math.isfinite(o) for o in origin):
-        raise ValueError(f"{what}: origin must be finite, got {list(origin)}")
-    return cell, origin
-
-
-def _check_points(t, what: str, name: str, rows=None):
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"{what}: {name} must be a (V, 3) tensor")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
-    if rows is not None and t.shape[0] != rows:
-        raise ValueError(f"{what}: {t.shape[0]} {name} for {rows} vertices")
-    return t.detach().contiguous()
-
-
-EXTENT_TILE = L.HN_EXTENT_TILE    # vertices per workgroup of hn_simplify_extent
-
-
-@torch.no_grad()
-def vertex_extent(vertices: torch.Tensor):
-    """(lo, hi): two lists of three host floats, the per-axis minimum and maximum of vertices (V >= 1, 3) fp32
-    (hn_simplify_extent: one partial per 2048 vertices, the partials reduced by torch; NaN where a coordinate is NaN).
-    One host read.  A CPU tensor is read with torch: simplify_mesh checks its arguments in full before it refuses a mesh
-    that does not live on the GPU."""
-    vertices = _check_points(vertices, "vertex_extent", "vertices")
-    v = vertices.shape[0]
-    if v == 0:
-        raise ValueError("vertex_extent: no vertices")
-    if not vertices.is_cuda:
-        return tuple(t.tolist() for t in torch.aminmax(vertices, dim=0))
-    L.load()
-    blocks = (v + EXTENT_TILE - 1) // EXTENT_TILE
-    partial = torch.empty((blocks, 2, 3), dtype=torch.float32, device=vertices.device)
-    with torch.cuda.device(vertices.device):
-        L.launch("hn_simplify_extent", L.ptr(vertices), v, L.ptr(partial), blocks, L.stream_handle())
-    lo, hi = torch.stack([partial[:, 0].amin(dim=0), partial[:, 1].amax(dim=0)]).tolist()
-    return lo, hi
-
-
-@torch.no_grad()
-def cluster_vertices(vertices: torch.Tensor, cell, origin) -> Dict[str, torch.Tensor]:
-    """The clusters of `vertices` (V, 3) fp32 on the lattice of cells `cell` (a float or three) from `origin` (three
-    floats): {'keys': (V,) int64 = ix | iy << 21 | iz << 42 with idx_c = floorf((v_c - origin_c) / cell_c) in fp32
-    (hn_simplify_keys), 'cluster_keys': (C,) int64, the distinct keys ascending, 'vertex_cluster': (V,) int32, 'order':
-    (V,) int32, the vertex ids by (key, id) — the members of cluster c are order[starts[c] : starts[c + 1]], 'starts':
-    (C + 1,) int32}.  The sort and the run lengths are torch's (a stable sort of integers).  The caller has checked the
-    extent (0 <= idx < 2**21; simplify_mesh does); an index outside is clamped.  One host read: the cluster count."""
-    vertices = _check_points(vertices, "cluster_vertices", "vertices")
-    cell, origin = check_cells(cell, origin, "cluster_vertices")
-    L.require_gpu(vertices)
-    v, dev = vertices.shape[0], vertices.device
-    if v > INT32_MAX:
-        raise ValueError(f"cluster_vertices: {v} vertices exceed 2**31 - 1 = {INT32_MAX}")
-    keys = torch.empty(v, dtype=torch.int64, device=dev)
-    if v == 0:
-        return {'keys': keys, 'cluster_keys': keys, 'vertex_cluster': torch.empty(0, dtype=torch.int32, device=dev),
-                'order': torch.empty(0, dtype=torch.int32, device=dev), 'starts': torch.zeros(1, dtype=torch.int32, device=dev)}
-    L.load()
-    with torch.cuda.device(dev):
-        L.launch("hn_simplify_keys", L.ptr(vertices), v, origin, cell, L.ptr(keys), L.stream_handle())
-    sorted_keys, order = torch.sort(keys, stable=True)
-    cluster_keys, inverse, counts = torch.unique_consecutive(sorted_keys, return_inverse=True, return_counts=True)
-    vertex_cluster = torch.empty(v, dtype=torch.int32, device=dev)
-    vertex_cluster[order] = inverse.to(torch.int32)
-    starts = torch.zeros(cluster_keys.shape[0] + 1, dtype=torch.int32, device=dev)
-    starts[1:] = torch.cumsum(counts, 0)
-    return {'keys': keys, 'cluster_keys': cluster_keys, 'vertex_cluster': vertex_cluster, 'order': order.to(torch.int32),
-            'starts': starts}
-
-
-@torch.no_grad()
-def reduce_clusters(vertices: torch.Tensor, normals: Optional[torch.Tensor], colors: Optional[torch.Tensor],
-                    clusters: Dict[str, torch.Tensor], cell, origin, placement: str = 'quadric',
-                    regularization: float = 0.1) -> Dict[str, torch.Tensor]:
-    """The representative of EVERY cluster of cluster_vertices, before any is dropped (hn_simplify_reduce, one work-item
-    per cluster walking its members in ascending vertex id): {'vertices': (C, 3) fp32, 'normals': (C, 3) fp32 when
-    given, 'colors': (C, 3) uint8 or fp32 when given}.  placement 'mean': the sequential fp32 mean; 'quadric': the mean
-    plus the step that minimises sum (n_i . (x - p_i))^2 + regularization * k * |x - mean|^2, clamped into the cell
-    (needs normals).  Every operation fp32 and rounded on its own, in the order tests/simplify_restated.py states."""
-    if placement not in ('quadric', 'mean'):
-        raise ValueError(f"reduce_clusters: placement must be 'quadric' or 'mean', got {placement!r}")
-    import math
-    regularization = float(regularization)
-    if not (math.isfinite(regularization) and regularization >= 0.0):
-        raise ValueError(f"reduce_clusters: regularization must be finite and not negative, got {regularization}")
-    vertices = _check_points(vertices, "reduce_clusters", "vertices")
-    v, dev = vertices.shape[0], vertices.device
-    if normals is not None:
-        normals = _check_points(normals, "reduce_clusters", "normals", v)
-    elif placement == 'quadric':
-        raise ValueError("reduce_clusters: placement='quadric' needs normals")
-    kind = 0
-    if colors is not None:
-        if not isinstance(colors, torch.Tensor) or colors.shape != (v, 3) or colors.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"reduce_clusters: colors must be a ({v}, 3) uint8 or float32 tensor")
-        colors = colors.detach().contiguous()
-        kind = 1 if colors.dtype == torch.uint8 else 2
-    cell, origin = check_cells(cell, origin, "reduce_clusters")
-    L.require_gpu(vertices, normals, colors)
-    order, starts, cluster_keys = (clusters[k].contiguous() for k in ('order', 'starts', 'cluster_keys'))
-    n_clusters = cluster_keys.shape[0]
-    if order.dtype != torch.int32 or starts.dtype != torch.int32 or cluster_keys.dtype != torch.int64 \
-            or order.shape != (v,) or starts.shape != (n_clusters + 1,) or n_clusters > v:
-        raise ValueError("reduce_clusters: clusters must be what cluster_vertices returned for these vertices")
-    out = {'vertices': torch.empty((n_clusters, 3), dtype=torch.float32, device=dev)}
-    if normals is not None:
-        out['normals'] = torch.empty((n_clusters, 3), dtype=torch.float32, device=dev)
-    if colors is not None:
-        out['colors'] = torch.empty((n_clusters, 3), dtype=colors.dtype, device=dev)
-    if n_clusters:
-        L.load()
-        with torch.cuda.device(dev):
-            L.launch("hn_simplify_reduce", L.ptr(vertices), L.ptr(normals), L.ptr(colors), kind, L.ptr(order), L.ptr(starts),
-                     L.ptr(cluster_keys), n_clusters, v, origin, cell, regularization, 1 if placement == 'quadric' else 0,
-                     L.ptr(out['vertices']), L.ptr(out.get('normals')), L.ptr(out.get('colors')), L.stream_handle())
-    return out
-
-
-@torch.no_grad()
-def cluster_faces(faces: torch.Tensor, vertex_cluster: torch.Tensor, num_clusters: int, return_used: bool = False):
-    """(F', 3) int32 faces over CLUSTER ids: every face of `faces` (F, 3) int32 goes through vertex_cluster (V,) int32; a
-    face with two equal ids is dropped; per set {a < b < c}, net = #(a, b, c) - #(a, c, b) among the rest, and |net| copies
-    leave, wound (a, b, c) when net > 0 and (a, c, b) when net < 0, in ascending order of (a, b, c) — opposite pairs, the
-    folded flaps of a collapse, cancel (hn_simplify_face_keys, two stable torch sorts, hn_simplify_face_net,
-    hn_simplify_face_emit).  `return_used`: also (C,) int32, 1 for every cluster an emitted face uses.  One host read: F'."""
-    faces, v = _check_faces(faces, vertex_cluster.shape[0], "cluster_faces")
-    if vertex_cluster.dtype != torch.int32 or vertex_cluster.dim() != 1:
-        raise ValueError("cluster_faces: vertex_cluster must be a (V,) int32 tensor")
-    L.require_gpu(vertex_cluster)
-    n_clusters = int(num_clusters)
-    if not 0 <= n_clusters <= v:
-        raise ValueError(f"cluster_faces: {n_clusters} clusters for {v} vertices")
-    dev, n_faces = faces.device, faces.shape[0]
-    used = torch.zeros(n_clusters, dtype=torch.int32, device=dev)
-    out = torch.zeros((0, 3), dtype=torch.int32, device=dev)
-    if n_faces and n_clusters:
-        L.load()
-        with torch.cuda.device(dev):
-            stream = L.stream_handle()
-            key_ab = torch.empty(n_faces, dtype=torch.int64, device=dev)
-            key_c = torch.empty(n_faces, dtype=torch.int32, device=dev)
-            sign = torch.empty(n_faces, dtype=torch.int32, device=dev)
-            L.launch("hn_simplify_face_keys", L.ptr(faces), n_faces, L.ptr(vertex_cluster.contiguous()), v, L.ptr(key_ab),
-                     L.ptr(key_c), L.ptr(sign), stream)
-            # lexicographic order of (a, b, c): stable by c, then stable by a << 31 | b
-            by_c = torch.sort(key_c, stable=True).indices
-            sorted_ab, by_ab = torch.sort(key_ab[by_c], stable=True)
-            perm = by_c[by_ab].contiguous()
-            net = torch.empty(n_faces, dtype=torch.int32, device=dev)
-            L.launch("hn_simplify_face_net", L.ptr(sorted_ab), L.ptr(key_c), L.ptr(sign), L.ptr(perm), n_faces, L.ptr(net),
-                     stream)
-            ends = torch.cumsum(net.abs(), 0, dtype=torch.int64)
-            n_out = int(ends[-1])
-            if n_out:
-                out = torch.empty((n_out, 3), dtype=torch.int32, device=dev)
-                L.launch("hn_simplify_face_emit", L.ptr(sorted_ab), L.ptr(key_c), L.ptr(perm), L.ptr(net), L.ptr(ends),
-                         n_faces, n_clusters, n_out, L.ptr(out), L.ptr(used), stream)
-    return (out, used) if return_used else out
-
-
-@torch.no_grad()
-def relabel_vertices(vertex_cluster: torch.Tensor, used: torch.Tensor, scan: torch.Tensor) -> torch.Tensor:
-    """(V,) int32: scan[cluster] - 1 for a vertex whose cluster is used, -1 otherwise (hn_simplify_relabel); scan = the
-    inclusive int32 scan of `used` (C,) int32."""
-    L.require_gpu(vertex_cluster, used, scan)
-    v, n_clusters = vertex_cluster.shape[0], used.shape[0]
-    out = torch.empty(v, dtype=torch.int32, device=vertex_cluster.device)
-    if v:
-        L.load()
-        with torch.cuda.device(vertex_cluster.device):
-            L.launch("hn_simplify_relabel", L.ptr(vertex_cluster.contiguous()), v, L.ptr(used.contiguous()),
-                     L.ptr(scan.contiguous()), n_clusters, L.ptr(out), L.stream_handle())
-    return out
-
-
-# --------------------------------------------------------------------------------------------
-# mesh rendering by ray casting (csrc/hn_mesh_render.hip)
-# --------------------------------------------------------------------------------------------
-MESH_TILE = L.HN_MESH_TILE    # pixels per tile side of hn_mesh_trace
-MESH_MAX_SIDE = L.HN_MESH_MAX_SIDE    # image sides the mesh renderer takes
-
-
-def check_image_wh(image_wh, what: str):
-    """(W, H) as two ints within 1 .. 65535, or ValueError."""
-    try:
-        w, h = (int(v) for v in image_wh)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: image_wh must be (W, H), got {image_wh!r}") from None
-    if not (1 <= w <= MESH_MAX_SIDE and 1 <= h <= MESH_MAX_SIDE):
-        raise ValueError(f"{what}: image sides must be 1 .. {MESH_MAX_SIDE}, got {w} x {h}")
-    return w, h
-
-
-def _check_camera(camera, what: str) -> torch.Tensor:
-    if not isinstance(camera, torch.Tensor) and hasattr(camera, "__array__"):
-        camera = torch.as_tensor(camera)
-    if (not isinstance(camera, torch.Tensor) or tuple(camera.shape) != (NERFIES_CAM_FLOATS,)
-            or camera.dtype != torch.float32):
-        raise ValueError(f"{what}: camera must be a ({NERFIES_CAM_FLOATS},) float32 record")
-    return camera.detach().contiguous()
-
-
-def _check_rays(rays, n_pixels: int, what: str) -> torch.Tensor:
-    if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or rays.shape[1] < 6 or rays.dtype != torch.float32:
-        raise ValueError(f"{what}: rays must be a (H*W, >= 6) float32 tensor")
-    if rays.shape[0] != n_pixels:
-        raise ValueError(f"{what}: {rays.shape[0]} rays for an image of {n_pixels} pixels")
-    return rays.detach().contiguous()
-
-
-def _check_mesh_faces(faces, what: str) -> torch.Tensor:
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-        raise ValueError(f"{what}: faces must be a (F, 3) int32 tensor")
-    return faces.detach().contiguous()
-
-
-@torch.no_grad()
-def mesh_project(vertices: torch.Tensor, camera: torch.Tensor):
-    """(pix (V, 2) fp32, flags (V,) int32) of vertices (V, 3) fp32 through the forward model of the 24-float camera record
-    (hn_mesh_project): pixel coordinates with pixel (i, j) covering [i, i + 1) x [j, j + 1); flag 1 for z <= 1e-6 in the
-    camera frame, 2 where the radial distortion folds or a coordinate is not finite (pix is then (0, 0))."""
-    vertices = _check_points(vertices, "mesh_project", "vertices")
-    camera = _check_camera(camera, "mesh_project")
-    L.require_gpu(vertices)
-    v, dev = vertices.shape[0], vertices.device
-    pix = torch.empty((v, 2), dtype=torch.float32, device=dev)
-    flags = torch.empty(v, dtype=torch.int32, device=dev)
-    if v:
-        L.load()
-        camera = camera.to(dev)
-        with torch.cuda.device(dev):
-            L.launch("hn_mesh_project", L.ptr(vertices), v, L.ptr(camera), L.ptr(pix), L.ptr(flags), L.stream_handle())
-    return pix, flags
-
-
-@torch.no_grad()
-def mesh_tile_pairs(vertices: torch.Tensor, faces: torch.Tensor, camera: torch.Tensor, image_wh, pix: torch.Tensor,
-                    vflags: torch.Tensor, fill: bool = True):
-    """(pair_tile, pair_face): two (n_pairs,) int32 tensors, the (tile, face) pairs of the W x H image in ascending face
-    order, a face's tiles row by row — hn_mesh_bin_count, torch.cumsum, ONE host read (the pair count and the error
-    flag), hn_mesh_bin_fill.  vertices (V >= 1, 3), faces (F >= 1, 3), camera on their device; pix / vflags: mesh_project's.
-    fill=False stops after the read and returns None (the ids are checked).  ValueError: a face holds a vertex id
-    outside [0, V); more than 2**31 - 1 pairs."""
-    w, h = image_wh
-    dev, v, n_faces = vertices.device, vertices.shape[0], faces.shape[0]
-    with torch.cuda.device(dev):
-        stream = L.stream_handle()
-        counts = torch.empty(n_faces, dtype=torch.int32, device=dev)
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-        L.launch("hn_mesh_bin_count", L.ptr(faces), n_faces, L.ptr(vertices), L.ptr(pix), L.ptr(vflags), v, L.ptr(camera),
-                 h, w, L.ptr(counts), L.ptr(err), stream)
-        ends = torch.cumsum(counts, 0, dtype=torch.int64)
-        n_pairs, bad = torch.stack([ends[-1], err[0].to(torch.int64)]).tolist()
-        if bad:
-            raise ValueError(f"mesh_bins: faces hold a vertex id outside [0, {v})")
-        if not fill:
-            return None
-        if n_pairs > INT32_MAX:
-            raise ValueError(f"mesh_bins: {n_pairs} (tile, face) pairs exceed 2**31 - 1 = {INT32_MAX}")
-        pair_tile = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-        pair_face = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-        if n_pairs:
-            L.launch("hn_mesh_bin_fill", L.ptr(faces), n_faces, L.ptr(vertices), L.ptr(pix), L.ptr(vflags), v, L.ptr(camera),
-                     h, w, L.ptr(ends), n_pairs, L.ptr(pair_tile), L.ptr(pair_face), stream)
-    return pair_tile, pair_face
-
-
-@torch.no_grad()
-def group_tile_pairs(pair_tile: torch.Tensor, pair_face: torch.Tensor, n_tiles: int):
-    """(tile_begin, tile_end, pair_face grouped by tile): a stable torch.sort on the tile key — the faces of a tile stay in
-    ascending order — and one torch.searchsorted for where every tile begins, as simplify_faces groups its keys."""
-    sorted_tile, order = torch.sort(pair_tile, stable=True)
-    starts = torch.searchsorted(sorted_tile, torch.arange(n_tiles + 1, dtype=torch.int32, device=pair_tile.device))
-    return starts[:-1].contiguous(), starts[1:].contiguous(), pair_face[order].contiguous()
-
-
-@torch.no_grad()
-def mesh_bins(vertices: torch.Tensor, faces: torch.Tensor, camera: torch.Tensor, image_wh, binning: bool = True):
-    """(tile_begin, tile_end, pair_face): the faces every 16 x 16 tile of the W x H image must test are
-    pair_face[tile_begin[T] : tile_end[T]] (int64 bounds, int32 face ids ascending within a tile), tile T = ty * ceil(W / 16)
-    + tx: mesh_project, mesh_tile_pairs (one host read), group_tile_pairs.  binning=False: every tile gets every face (no
-    fill, no sort; the ids are checked all the same).  ValueError: a face holds a vertex id outside [0, V); more than
-    2**31 - 1 pairs."""
-    what = "mesh_bins"
-    vertices = _check_points(vertices, what, "vertices")
-    faces = _check_mesh_faces(faces, what)
-    camera = _check_camera(camera, what)
-    w, h = check_image_wh(image_wh, what)
-    L.require_gpu(vertices, faces)
-    dev = vertices.device
-    v, n_faces = vertices.shape[0], faces.shape[0]
-    n_tiles = ((w + MESH_TILE - 1) // MESH_TILE) * ((h + MESH_TILE - 1) // MESH_TILE)
-    none = torch.zeros(n_tiles, dtype=torch.int64, device=dev)
-    if n_faces == 0:
-        return none, none, torch.zeros(0, dtype=torch.int32, device=dev)
-    if v == 0:
-        raise ValueError(f"{what}: faces hold a vertex id outside [0, 0)")
-    L.load()
-    camera = camera.to(dev)
-    pix, vflags = mesh_project(vertices, camera)
-    pairs = mesh_tile_pairs(vertices, faces, camera, (w, h), pix, vflags, fill=bool(binning))
-    if pairs is None:
-        return none, torch.full((n_tiles,), n_faces, dtype=torch.int64, device=dev), \
-            torch.arange(n_faces, dtype=torch.int32, device=dev)
-    if pairs[0].numel() == 0:
-        return none, none, pairs[1]
-    return group_tile_pairs(pairs[0], pairs[1], n_tiles)
-
-
-@torch.no_grad()
-def mesh_trace(vertices: torch.Tensor, faces: torch.Tensor, rays: torch.Tensor, camera: torch.Tensor, image_wh,
-               binning: bool = True, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-    """{'face': (H*W,) int32, 'depth': (H*W,) fp32, 'bary': (H*W, 3) fp32} of the mesh seen along rays (H*W, >= 6) fp32
-    (row p = pixel p: origin, unit direction): the nearest face every ray crosses by the ray-casting definition of
-    csrc/hn_mesh_render.hip (-1 / 0 / zeros where it crosses none).  `camera` only bins the faces (mesh_bins);
-    binning=False tests every face at every pixel and gives the same bits (but for stray hits of near-degenerate faces,
-    DESIGN.md 3.11).  `out`: contiguous tensors of those shapes to
-    write into; a ValueError (a vertex id outside [0, V)) leaves them untouched."""
-    what = "mesh_trace"
-    vertices = _check_points(vertices, what, "vertices")
-    faces = _check_mesh_faces(faces, what)
-    w, h = check_image_wh(image_wh, what)
-    n = h * w
-    rays = _check_rays(rays, n, what)
-    L.require_gpu(vertices, faces, rays)
-    dev = vertices.device
-    shapes = {'face': ((n,), torch.int32), 'depth': ((n,), torch.float32), 'bary': ((n, 3), torch.float32)}
-    if out is not None:
-        for k, (shape, dtype) in shapes.items():
-            t = out.get(k)
-            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() \
-                    or t.device != dev:
-                raise ValueError(f"{what}: out['{k}'] must be a contiguous {shape} {dtype} tensor on {dev}")
-    tile_begin, tile_end, pair_face = mesh_bins(vertices, faces, camera, (w, h), binning)
-    if out is None:
-        out = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (shape, dtype) in shapes.items()}
-    n_pairs = pair_face.shape[0]
-    L.load()
-    with torch.cuda.device(dev):
-        L.launch("hn_mesh_trace", L.ptr(vertices) if n_pairs else None, vertices.shape[0], L.ptr(faces) if n_pairs else None,
-                 faces.shape[0], L.ptr(rays), rays.shape[1], h, w, L.ptr(tile_begin), L.ptr(tile_end),
-                 L.ptr(pair_face) if n_pairs else None, n_pairs, L.ptr(out['face']), L.ptr(out['depth']), L.ptr(out['bary']),
-                 L.stream_handle())
-    return {k: out[k] for k in shapes}
-
-
-SHADINGS = ('headlight', 'none')
-
-
-def check_shading(shading, ambient, background, base_color, what: str):
-    """(headlight flag, ambient, background, base_color as (c_float * 3)) or ValueError: colours and ambient in [0, 1]."""
-    if shading not in SHADINGS:
-        raise ValueError(f"{what}: shading must be one of {SHADINGS}, got {shading!r}")
-    try:
-        ambient = float(ambient)
-    except (TypeError, ValueError):
-        ambient = float("nan")
-    if not 0.0 <= ambient <= 1.0:
-        raise ValueError(f"{what}: ambient must lie in [0, 1]")
-    cols = []
-    for name, col in (("background", background), ("base_color", base_color)):
-        try:
-            vals = [float(x) for x in col]
-        except (TypeError, ValueError):
-            vals = []
-        if len(vals) != 3 or not all(0.0 <= x <= 1.0 for x in vals):
-            raise ValueError(f"{what}: {name} must be three numbers in [0, 1], got {col!r}")
-        cols.append((C.c_float * 3)(*vals))
-    return int(shading == 'headlight'), ambient, cols[0], cols[1]
-
-
-@torch.no_grad()
-def mesh_shade(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor], colors: Optional[torch.Tensor],
-               rays: torch.Tensor, face: torch.Tensor, bary: torch.Tensor, shading: str = 'headlight', ambient: float = 0.3,
-               background=(1.0, 1.0, 1.0), base_color=(0.8, 0.8, 0.8)) -> Dict[str, torch.Tensor]:
-    """{'normal': (P, 3) fp32, 'rgb': (P, 3) fp32, 'rgb8': (P, 3) uint8} of the pixels mesh_trace resolved (hn_mesh_shade):
-    the normalised interpolated vertex normal (the face normal without `normals`), the interpolated vertex colour
-    (uint8 / 255, fp32 as it is, `base_color` without `colors`) times ambient + (1 - ambient) |N . d| ('headlight') or 1
-    ('none'), clamped to [0, 1]; rgb8 = floor(255 rgb + 0.5); `background` and a zero normal where face is -1."""
-    what = "mesh_shade"
-    vertices = _check_points(vertices, what, "vertices")
-    faces = _check_mesh_faces(faces, what)
-    v, n_faces = vertices.shape[0], faces.shape[0]
-    if normals is not None:
-        normals = _check_points(normals, what, "normals", v)
-    kind = 0
-    if colors is not None:
-        if not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (v, 3) or colors.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"{what}: colors must be a ({v}, 3) uint8 or float32 tensor")
-        colors = colors.detach().contiguous()
-        kind = 1 if colors.dtype == torch.uint8 else 2
-    headlight, ambient, background, base_color = check_shading(shading, ambient, background, base_color, what)
-    if not isinstance(face, torch.Tensor) or face.dim() != 1 or face.dtype != torch.int32:
-        raise ValueError(f"{what}: face must be a (P,) int32 tensor")
-    n = face.shape[0]
-    if not isinstance(bary, torch.Tensor) or tuple(bary.shape) != (n, 3) or bary.dtype != torch.float32:
-        raise ValueError(f"{what}: bary must be a ({n}, 3) float32 tensor")
-    rays = _check_rays(rays, n, what)
-    face, bary = face.detach().contiguous(), bary.detach().contiguous()
-    L.require_gpu(vertices, faces, normals, colors, rays, face, bary)
-    dev = face.device
-    out = {'normal': torch.empty((n, 3), dtype=torch.float32, device=dev),
-           'rgb': torch.empty((n, 3), dtype=torch.float32, device=dev),
-           'rgb8': torch.empty((n, 3), dtype=torch.uint8, device=dev)}
-    if n:
-        L.load()
-        with torch.cuda.device(dev):
-            L.launch("hn_mesh_shade", L.ptr(vertices) if v else None, v, L.ptr(faces) if n_faces else None, n_faces,
-                     L.ptr(normals) if v else None, L.ptr(colors) if v else None, kind, L.ptr(rays), rays.shape[1], n,
-                     L.ptr(face), L.ptr(bary), headlight, ambient, base_color, background,
-                     L.ptr(out['normal']), L.ptr(out['rgb']), L.ptr(out['rgb8']), L.stream_handle())
-    return out
-
-
-# --------------------------------------------------------------------------------------------
-# on-device ray generation
-# --------------------------------------------------------------------------------------------
-def _generate_rays(entry: str, h: int, w: int, name: str, table: torch.Tensor, shape: tuple, before: tuple, after: tuple,
-                   near: float, far: float, image_id: Optional[int]) -> torch.Tensor:
-    """Allocate the (h*w, 8|9) rows of one image and launch `entry` over them; `table` (the pose or camera record, of
-    `shape`) sits between the entry's own arguments `before` and `after`."""
-    L.require_gpu(table)
-    L.load()
-    if tuple(table.shape) != shape:
-        raise L.HnError(f"{name} must be {shape}")
-    t = table.detach().contiguous().float()
-    cols = 9 if image_id is not None else 8
-    rays = torch.empty(h * w, cols, dtype=torch.float32, device=table.device)
-    L.launch(entry, h, w, *before, L.ptr(t), *after, near, far, float(image_id or 0), cols, L.ptr(rays), L.stream_handle())
-    return rays
-
-
-def generate_rays(h: int, w: int, focal: float, c2w: torch.Tensor, near: float, far: float, ndc: bool = False,
-                  ndc_near: float = 1.0, image_id: Optional[int] = None) -> torch.Tensor:
-    """(h*w, 8|9) ray rows [o, d, near, far(, image id)] of one image, generated on the GPU
-    (reference: datasets/ray_utils.py get_ray_directions / get_rays / get_ndc_rays, datasets/llff.py:244-264)."""
-    return _generate_rays("hn_generate_rays", h, w, "c2w", c2w, (3, 4), (focal,), (int(ndc), ndc_near), near, far,
-                          image_id)
-
-
-def _ray_batch(entry: str, channels: int, table_row: tuple, before: tuple, after: tuple, perm, state, batch, h, w, table,
-               px8, rays, rgbs, near, far, image_ids) -> None:
-    """Validate and launch one gather entry: `table` is the per-image pose or camera table, (n_images, *table_row),
-    between the entry's own arguments `before` and `after`; `px8` the (n_images, h, w, channels) uint8 stack."""
-    L.require_gpu(perm, state, table, px8, rays, rgbs, image_ids)
-    L.load()
-    cols = rays.shape[1]
-    n_img = px8.shape[0]
-    ok = (perm.dtype == torch.int64 and perm.is_contiguous() and state.dtype == torch.int64 and state.numel() >= 3
-          and table.dtype == torch.float32 and table.is_contiguous() and tuple(table.shape) == (n_img,) + table_row
-          and px8.dtype == torch.uint8 and px8.is_contiguous() and tuple(px8.shape[1:]) == (h, w, channels)
-          and rays.dtype == torch.float32 and rays.is_contiguous() and cols in (8, 9) and rays.shape[0] >= batch
-          and rgbs.dtype == torch.float32 and rgbs.is_contiguous() and tuple(rgbs.shape[1:]) == (3,)
-          and rgbs.shape[0] >= batch and 0 < batch and perm.numel() > 0
-          and (cols == 8 or (image_ids is not None and image_ids.dtype == torch.float32 and image_ids.numel() >= n_img)))
-    if not ok:
-        raise L.HnError(f"{entry[3:]}: bad shapes / dtypes")
-    L.launch(entry, L.ptr(perm), perm.numel(), L.ptr(state), batch, px8.numel() // channels, h, w, *before, L.ptr(table),
-             L.ptr(image_ids if cols == 9 else None), *after, near, far, cols, L.ptr(px8), L.ptr(rays), L.ptr(rgbs),
-             L.stream_handle())
-
-
-def ray_batch(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float, c2w: torch.Tensor,
-              rgb8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float, far: float, ndc: bool = False,
-              ndc_near: float = 1.0, image_ids: Optional[torch.Tensor] = None) -> None:
-    """One training batch gathered on the GPU (hn_ray_batch): rows perm[cursor : cursor + batch] of the dataset whose
-    rays are the pixels of `rgb8` ((n_images, h, w, 3) uint8) seen through `c2w` ((n_images, 3, 4) fp32), written into
-    rays[:batch] ((B, 8|9) fp32, column 8 = image_ids[slot] when rays has 9 columns) and rgbs[:batch] ((B, 3) fp32).
-    `state` (3 int64 words: cursor, arrival counter, error flag) is advanced by `batch` on the device: no host sync.
-    A row whose position lies past the permutation, or whose index lies outside the dataset, is written as NaN and sets
-    the error flag."""
-    _ray_batch("hn_ray_batch", 3, (3, 4), (focal,), (int(ndc), ndc_near), perm, state, batch, h, w, c2w, rgb8, rays, rgbs,
-               near, far, image_ids)
-
-
-def ray_batch_rgba(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, focal: float,
-                   c2w: torch.Tensor, rgba8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float,
-                   far: float, ndc: bool = False, ndc_near: float = 1.0,
-                   image_ids: Optional[torch.Tensor] = None) -> None:
-    """`ray_batch` over an RGBA stack ((n_images, h, w, 4) uint8, hn_ray_batch_rgba): rgbs[:batch] is each pixel
-    blended onto white as `blend_white_u8` computes it, in the same launch."""
-    _ray_batch("hn_ray_batch_rgba", 4, (3, 4), (focal,), (int(ndc), ndc_near), perm, state, batch, h, w, c2w, rgba8, rays,
-               rgbs, near, far, image_ids)
-
-
-NERFIES_CAM_FLOATS = L.HN_NERFIES_CAM_FLOATS    # hn_kernels.h: orientation 9, position 3, f, aspect, skew, cx, cy, k1 k2 k3, p1 p2, 2 zeros
-
-
-def generate_rays_nerfies(h: int, w: int, cam: torch.Tensor, near: float, far: float,
-                          image_id: Optional[int] = None) -> torch.Tensor:
-    """(h*w, 8|9) ray rows [o, d, near, far(, image id)] of one image of a Nerfies-format capture, generated on the GPU
-    (hn_generate_rays_nerfies) from its camera record `cam` ((24,) fp32, datasets.nerfies.camera_record): pixel
-    centres at (i + 0.5, j + 0.5), principal point, skew, pixel aspect ratio, and 10 Newton steps that undo the radial
-    and tangential distortion."""
-    return _generate_rays("hn_generate_rays_nerfies", h, w, "cam", cam, (NERFIES_CAM_FLOATS,), (), (), near, far,
-                          image_id)
-
-
-def ray_batch_nerfies(perm: torch.Tensor, state: torch.Tensor, batch: int, h: int, w: int, cams: torch.Tensor,
-                      rgb8: torch.Tensor, rays: torch.Tensor, rgbs: torch.Tensor, near: float, far: float,
-                      image_ids: Optional[torch.Tensor] = None) -> None:
-    """`ray_batch` over a Nerfies-format capture (hn_ray_batch_nerfies): `cams` is the (n_images, 24) fp32 table of
-    camera records and rays[:batch] holds the rows `generate_rays_nerfies` writes for those pixels, bit for bit (one
-    device function); perm, state, rgb8, rgbs, image_ids and the NaN rows are `ray_batch`'s."""
-    _ray_batch("hn_ray_batch_nerfies", 3, (NERFIES_CAM_FLOATS,), (), (), perm, state, batch, h, w, cams, rgb8, rays,
-               rgbs, near, far, image_ids)
-
-
-def blend_white_u8(rgba8: torch.Tensor, with_mask: bool = False):
-    """(..., 4) uint8 RGBA -> (N, 3) fp32 `rgb * a + (1 - a)` on u8 / 255 values, bit for bit the reference's blend
-    (datasets/blender.py:58; hn_blend_white_u8: a multiply, a subtraction and an addition, each rounded).  With
-    `with_mask` also the (N,) bool mask a > 0 (blender.py:93): returns (rgbs, mask)."""
-    L.require_gpu(rgba8)
-    L.load()
-    if rgba8.dtype != torch.uint8 or rgba8.dim() < 1 or rgba8.shape[-1] != 4 or rgba8.numel() == 0:
-        raise L.HnError("blend_white_u8: (..., 4) uint8")
-    x = rgba8.contiguous()
-    n = x.numel() // 4
-    rgbs = torch.empty((n, 3), dtype=torch.float32, device=x.device)
-    mask = torch.empty(n, dtype=torch.bool, device=x.device) if with_mask else None
-    L.launch("hn_blend_white_u8", L.ptr(x), n, L.ptr(rgbs), L.ptr(mask), L.stream_handle())
-    return (rgbs, mask) if with_mask else rgbs
-
-
-_RESAMPLE_TABLES: Dict[tuple, tuple] = {}
-
-
-def _resample_tables(in_size: int, out_size: int, device):
-    key = (in_size, out_size, str(device))
-    t = _RESAMPLE_TABLES.get(key)
-    if t is None:
-        from .datasets.image_io import lanczos_tables
-        bounds, kk, ksize = lanczos_tables(in_size, out_size)
-        if not ((bounds[:, 0] >= 0).all() and (bounds[:, 1] >= 0).all() and (bounds.sum(1) <= in_size).all()
-                and (bounds[:, 1] <= ksize).all()):
-            raise L.HnError("resize: coefficient bounds outside the input")
-        t = _RESAMPLE_TABLES[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize)
-    return t
-
-
-def resize_lanczos_u8(img: torch.Tensor, size) -> torch.Tensor:
-    """Pillow's `Image.resize(size, Image.LANCZOS)` of an 8-bit (H, W, C) image on the GPU, byte for byte: the
-    horizontal pass first (uint8 intermediate), then the vertical one; a pass whose axis keeps its length is skipped.
-    size = (width, height) as Pillow takes it."""
-    L.require_gpu(img)
-    L.load()
-    if img.dtype != torch.uint8 or img.dim() != 3 or not 1 <= img.shape[2] <= 4:
-        raise L.HnError("resize_lanczos_u8: (H, W, C) uint8, C <= 4")
-    out_w, out_h = int(size[0]), int(size[1])
-    if out_w <= 0 or out_h <= 0:
-        raise L.HnError("resize_lanczos_u8: the size must be positive")
-    x = img.contiguous()
-    h, w, c = x.shape
-    if out_w != w:
-        bounds, kk, ksize = _resample_tables(w, out_w, x.device)
-        y = torch.empty((h, out_w, c), dtype=torch.uint8, device=x.device)
-        L.launch("hn_resample_u8", L.ptr(x), h, w, c, out_w, 0, L.ptr(bounds), L.ptr(kk), ksize, L.ptr(y), L.stream_handle())
-        x, w = y, out_w
-    if out_h != h:
-        bounds, kk, ksize = _resample_tables(h, out_h, x.device)
-        y = torch.empty((out_h, w, c), dtype=torch.uint8, device=x.device)
-        L.launch("hn_resample_u8", L.ptr(x), h, w, c, out_h, 1, L.ptr(bounds), L.ptr(kk), ksize, L.ptr(y), L.stream_handle())
-        x = y
-    return x if x is not img else x.clone()
-
-
-def premultiply_u8(img: torch.Tensor, inverse: bool = False) -> torch.Tensor:
-    """Pillow's RGBA -> RGBa conversion of an (H, W, 4) uint8 image (hn_premultiply_u8), or with `inverse` RGBa ->
-    RGBA: both round, alpha stays."""
-    L.require_gpu(img)
-    L.load()
-    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 4 or img.numel() == 0:
-        raise L.HnError("premultiply_u8: (H, W, 4) uint8")
-    x = img.contiguous()
-    out = torch.empty_like(x)
-    L.launch("hn_premultiply_u8", L.ptr(x), x.numel() // 4, int(inverse), L.ptr(out),
-             L.stream_handle())
-    return out
-
-
-def resize_lanczos_rgba8(img: torch.Tensor, size) -> torch.Tensor:
-    """Pillow's `Image.resize(size, Image.LANCZOS)` of an 8-bit RGBA (H, W, 4) image on the GPU, byte for byte: Pillow
-    resamples such an image in premultiplied alpha, so the colour bytes are premultiplied, the four channels go
-    through the passes of `resize_lanczos_u8`, and the colours are divided by the new alpha.  At equal size Pillow
-    returns a copy, without that round trip (it would change bytes).  size = (width, height)."""
-    L.require_gpu(img)
-    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 4:
-        raise L.HnError("resize_lanczos_rgba8: (H, W, 4) uint8")
-    out_w, out_h = int(size[0]), int(size[1])
-    if (out_h, out_w) == tuple(img.shape[:2]):
-        return img.clone(memory_format=torch.contiguous_format)
-    return premultiply_u8(resize_lanczos_u8(premultiply_u8(img), (out_w, out_h)), inverse=True)
-
-
-# --------------------------------------------------------------------------------------------
-# GIF of the evaluated frames, depth image of the validation step (csrc/hn_gif.hip)
-# --------------------------------------------------------------------------------------------
-HIST_BINS = L.HN_HIST_BINS
-
-
-def _check_pixels(pixels, what: str) -> torch.Tensor:
-    if not isinstance(pixels, torch.Tensor) or pixels.dtype != torch.uint8 or pixels.dim() < 1 or pixels.shape[-1] != 3:
-        raise ValueError(f"{what}: pixels must be a (..., 3) uint8 tensor")
-    if pixels.numel() == 0 or pixels.numel() // 3 > 2 ** 31:
-        raise ValueError(f"{what}: 1 .. 2**31 pixels, got {pixels.numel() // 3}")
-    L.require_gpu(pixels)
-    return pixels.detach().contiguous()
-
-
-@torch.no_grad()
-def color_histogram(pixels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """(2^18, 4) int64 table of the packed 8-bit RGB `pixels` (..., 3): cell (r>>2)<<12 | (g>>2)<<6 | b>>2 holds
-    [pixels, sum r, sum g, sum b] (hn_color_hist: integer adds, exact and independent of their order).  `out`: a table to
-    ADD to (several frames, one table); a fresh zeroed one otherwise."""
-    px = _check_pixels(pixels, "color_histogram")
-    if out is None:
-        out = torch.zeros((HIST_BINS, 4), dtype=torch.int64, device=px.device)
-    elif (out.dtype != torch.int64 or tuple(out.shape) != (HIST_BINS, 4) or not out.is_contiguous()
-          or out.device != px.device):
-        raise ValueError(f"color_histogram: out must be a contiguous ({HIST_BINS}, 4) int64 tensor on {px.device}")
-    L.load()
-    with torch.cuda.device(px.device):
-        L.launch("hn_color_hist", L.ptr(px), px.numel() // 3, L.ptr(out), L.stream_handle())
-    return out
-
-
-@torch.no_grad()
-def palette_map(pixels: torch.Tensor, palette: torch.Tensor) -> torch.Tensor:
-    """(...,) uint8: for every packed RGB pixel of `pixels` (..., 3) the index of the nearest of the 1..256 entries of
-    `palette` (K, 3) uint8 in squared RGB distance, the smallest index among equals (hn_palette_map)."""
-    if (not isinstance(palette, torch.Tensor) or palette.dtype != torch.uint8 or palette.dim() != 2
-            or palette.shape[1] != 3 or not 1 <= palette.shape[0] <= 256):
-        raise ValueError("palette_map: palette must be a (1..256, 3) uint8 tensor")
-    px = _check_pixels(pixels, "palette_map")
-    pal = palette.detach().to(px.device).contiguous()
-    out = torch.empty(px.shape[:-1], dtype=torch.uint8, device=px.device)
-    L.load()
-    with torch.cuda.device(px.device):
-        L.launch("hn_palette_map", L.ptr(px), px.numel() // 3, L.ptr(pal), pal.shape[0], L.ptr(out), L.stream_handle())
-    return out
-
-
-def gif_lzw(indices) -> bytes:
-    """The raw code bytes of GIF's LZW (minimum code size 8) of a uint8 index stream — array, tensor or bytes, on the
-    host (hn_gif_lzw: host C++ in the library; no GPU is involved)."""
-    import numpy as np
-    if isinstance(indices, torch.Tensor):
-        indices = indices.detach().cpu().numpy()
-    if isinstance(indices, (bytes, bytearray)):
-        indices = np.frombuffer(bytes(indices), dtype=np.uint8)
-    a = np.asarray(indices)
-    if a.dtype != np.uint8:
-        raise ValueError(f"gif_lzw: indices must be uint8, got {a.dtype}")
-    a = np.ascontiguousarray(a).reshape(-1)
-    n = a.size
-    # at most n + 2 codes and one clear per 3838 of them, 12 bits each
-    cap = ((n + 3 + n // 3838 + 1) * 12 + 7) // 8
-    out = np.empty(cap, dtype=np.uint8)
-    out_len = C.c_longlong(0)
-    L.check(L.load().hn_gif_lzw(a.ctypes.data if n else None, n, out.ctypes.data, cap, C.byref(out_len)), "hn_gif_lzw")
-    return out[:out_len.value].tobytes()
-
-
-@torch.no_grad()
-def depth_colormap(depth: torch.Tensor, lut: torch.Tensor, return_range: bool = False):
-    """(H, W, 3) uint8 = lut[(uint8)(255 * (d - min) / (max - min + 1e-8))] of d = nan_to_num(depth), depth (H, W) fp32
-    and lut (256, 3) uint8: the array visualize_depth colours (utils/visualization.py:10-16) — hn_depth_range, then
-    hn_depth_colormap reading the range from the device, no host synchronisation.  A NaN quotient (both infinities in
-    one map) gives index 0.  `return_range`: also the (2,) fp32 device tensor [min, max]."""
-    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2 or depth.numel() == 0:
-        raise ValueError("depth_colormap: depth must be a non-empty (H, W) float32 tensor")
-    if (not isinstance(lut, torch.Tensor) or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3)):
-        raise ValueError("depth_colormap: lut must be a (256, 3) uint8 tensor")
-    L.require_gpu(depth)
-    d = depth.detach().contiguous()
-    table = lut.detach().to(d.device).contiguous()
-    rng = torch.empty(2, dtype=torch.float32, device=d.device)
-    out = torch.empty(tuple(d.shape) + (3,), dtype=torch.uint8, device=d.device)
-    L.load()
-    with torch.cuda.device(d.device):
-        stream = L.stream_handle()
-        L.launch("hn_depth_range", L.ptr(d), d.numel(), L.ptr(rng), stream)
-        L.launch("hn_depth_colormap", L.ptr(d), d.numel(), L.ptr(rng), L.ptr(table), L.ptr(out), stream)
-    return (out, rng) if return_range else out
 
 
 # --------------------------------------------------------------------------------------------

@@ -43,7 +43,8 @@ from typing import Dict, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import functional as F
+from . import _lib as L
+from . import ops
 
 ROW = 64      # lattice points per row of a query: one row = one "ray" of the programs (one id, one view direction)
 
@@ -63,7 +64,7 @@ def density_grid(model, bounds, resolution, frame_id: int, level: str = 'fine', 
     column 8 of a ray row does.  `resolution`: an int or (nx, ny, nz).  The lattice is queried `chunk` points at a time
     (rounded up to whole rows of 64 points; the last chunk is padded with copies of the last point, which are dropped), in
     the model's current precision; the values do not depend on `chunk`."""
-    shape, bounds = F.check_lattice(_resolution(resolution), bounds, "density_grid")
+    shape, bounds = ops.mesh.check_lattice(_resolution(resolution), bounds, "density_grid")
     if int(chunk) < 1:
         raise ValueError(f"density_grid: chunk must be positive, got {chunk}")
     device = next(model.parameters()).device
@@ -74,7 +75,7 @@ def density_grid(model, bounds, resolution, frame_id: int, level: str = 'fine', 
     viewdirs = torch.tensor([0.0, 0.0, 1.0], device=device).expand(rows_per_chunk, 3).contiguous()
     for start in range(0, n, rows_per_chunk * ROW):
         rows = min(rows_per_chunk, (n - start + ROW - 1) // ROW)
-        points = F.grid_points(shape, bounds, start, rows * ROW, device).view(rows, ROW, 3)
+        points = ops.mesh.grid_points(shape, bounds, start, rows * ROW, device).view(rows, ROW, 3)
         metadata = {k: ids[:rows] for k in ('warp', 'camera', 'appearance', 'time')}
         sigma = model.query_points(points, metadata, level=level, viewdirs=viewdirs[:rows], render_opts=render_opts)['sigma']
         valid = min(rows * ROW, n - start)
@@ -84,19 +85,19 @@ def density_grid(model, bounds, resolution, frame_id: int, level: str = 'fine', 
 
 def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torch.Tensor]:
     """{'vertices': (V, 3) fp32, 'normals': (V, 3) fp32, 'faces': (F, 3) int32} of the surface grid = iso (marching
-    tetrahedra, functional.extract_isosurface): grid (nx, ny, nz) fp32 on the GPU over `bounds`.  Normals point from
+    tetrahedra, ops.mesh.extract_isosurface): grid (nx, ny, nz) fp32 on the GPU over `bounds`.  Normals point from
     grid >= iso towards lower values, faces wind accordingly; an empty surface gives zero-length tensors."""
-    return F.extract_isosurface(grid, iso, bounds)
+    return ops.mesh.extract_isosurface(grid, iso, bounds)
 
 
 def mesh_components(faces: torch.Tensor, num_vertices: int) -> torch.Tensor:
-    """labels (V,) int32: the smallest vertex id of every vertex's connected component (functional.mesh_components)."""
-    return F.mesh_components(faces, num_vertices)
+    """labels (V,) int32: the smallest vertex id of every vertex's connected component (ops.mesh.mesh_components)."""
+    return ops.mesh.mesh_components(faces, num_vertices)
 
 
 def component_sizes(labels: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
-    """(V,) int32: faces per component at index = label, zero elsewhere (functional.component_sizes)."""
-    return F.component_sizes(labels, faces)
+    """(V,) int32: faces per component at index = label, zero elsewhere (ops.mesh.component_sizes)."""
+    return ops.mesh.component_sizes(labels, faces)
 
 
 @torch.no_grad()
@@ -117,8 +118,8 @@ def filter_mesh(mesh: Dict[str, torch.Tensor], min_faces: Optional[int] = None,
     dev = faces.device
     per_vertex = [k for k, t in mesh.items() if k not in ('faces', 'vertex_index') and isinstance(t, torch.Tensor)
                   and t.dim() >= 1 and t.shape[0] == v]
-    labels = F.mesh_components(faces, v)
-    sizes = F.component_sizes(labels, faces)
+    labels = ops.mesh.mesh_components(faces, v)
+    sizes = ops.mesh.component_sizes(labels, faces)
     keep = sizes >= max(int(min_faces or 0), 1)
     if keep_largest is not None:
         k = int(keep_largest)
@@ -129,10 +130,10 @@ def filter_mesh(mesh: Dict[str, torch.Tensor], min_faces: Optional[int] = None,
             t = torch.topk(sizes, k).values[-1]
             above, at = sizes > t, sizes == t
             keep &= above | (at & (torch.cumsum(at, 0) <= k - above.sum()))
-    vertex_index, new_faces = F.compact_mesh(faces, labels, keep)
+    vertex_index, new_faces = ops.mesh.compact_mesh(faces, labels, keep)
     out = dict(mesh)
     for name in per_vertex:
-        out[name] = F.gather_rows(mesh[name], vertex_index)
+        out[name] = ops.mesh.gather_rows(mesh[name], vertex_index)
     out['faces'] = new_faces
     out['vertex_index'] = vertex_index
     return out
@@ -174,7 +175,7 @@ def vertex_colors(model, vertices: torch.Tensor, normals: Optional[torch.Tensor]
     ids = torch.full((chunk,), int(frame_id), dtype=torch.int64, device=device)
     for start in range(0, v, chunk):
         n = min(chunk, v - start)
-        dirs = F.vertex_viewdirs(vertices, normals, start, n, camera)
+        dirs = ops.mesh.vertex_viewdirs(vertices, normals, start, n, camera)
         metadata = {k: ids[:n] for k in ('warp', 'camera', 'appearance', 'time')}
         rgb = model.query_points(vertices[start:start + n].view(n, 1, 3), metadata, level=level, viewdirs=dirs,
                                  render_opts=render_opts)['rgb'].view(n, 3)
@@ -184,7 +185,7 @@ def vertex_colors(model, vertices: torch.Tensor, normals: Optional[torch.Tensor]
 
 def _simplify_factor(simplify):
     """Three positive finite floats from extract_mesh's `simplify`, or ValueError."""
-    k = F._float3(simplify, "extract_mesh: simplify")
+    k = ops.checks.float3(simplify, "extract_mesh: simplify")
     if not all(np.isfinite(x) and x > 0.0 for x in k):
         raise ValueError(f"extract_mesh: simplify must be positive and finite, got {simplify!r}")
     return k
@@ -213,14 +214,14 @@ def simplify_mesh(mesh: Dict[str, torch.Tensor], cell, origin=None, placement: s
     what = "simplify_mesh"
     if placement not in ('quadric', 'mean'):
         raise ValueError(f"{what}: placement must be 'quadric' or 'mean', got {placement!r}")
-    vertices = F._check_points(mesh.get('vertices'), what, "vertices")
+    vertices = ops.checks.check_points(mesh.get('vertices'), what, "vertices")
     v = vertices.shape[0]
     faces = mesh.get('faces')
     if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
         raise ValueError(f"{what}: faces must be a (F, 3) int32 tensor")
     normals, colors = mesh.get('normals'), mesh.get('colors')
     if normals is not None:
-        normals = F._check_points(normals, what, "normals", v)
+        normals = ops.checks.check_points(normals, what, "normals", v)
     elif placement == 'quadric':
         raise ValueError(f"{what}: placement='quadric' needs the mesh's 'normals'")
     if colors is not None and (not isinstance(colors, torch.Tensor) or colors.shape != (v, 3)
@@ -229,7 +230,7 @@ def simplify_mesh(mesh: Dict[str, torch.Tensor], cell, origin=None, placement: s
     regularization = float(regularization)
     if not (np.isfinite(regularization) and regularization >= 0.0):
         raise ValueError(f"{what}: regularization must be finite and not negative, got {regularization}")
-    cell_c, _ = F.check_cells(cell, (0.0, 0.0, 0.0) if origin is None else origin, what)
+    cell_c, _ = ops.simplify.check_cells(cell, (0.0, 0.0, 0.0) if origin is None else origin, what)
     dev = vertices.device
 
     def empty():
@@ -244,41 +245,42 @@ def simplify_mesh(mesh: Dict[str, torch.Tensor], cell, origin=None, placement: s
 
     if v:
         # host read 1: the extent, which the key layout (21 bits per axis, no negative index) must hold
-        lo, hi = (np.asarray(t, dtype=np.float32) for t in F.vertex_extent(vertices))
+        lo, hi = (np.asarray(t, dtype=np.float32) for t in ops.simplify.vertex_extent(vertices))
         if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
             raise ValueError(f"{what}: the vertices are not finite")
-        origin_f = lo if origin is None else np.asarray(F._float3(origin, f"{what}: origin"), dtype=np.float32)
+        origin_f = lo if origin is None else np.asarray(ops.checks.float3(origin, f"{what}: origin"), dtype=np.float32)
         cell_f = np.asarray(list(cell_c), dtype=np.float32)
         if (origin_f > lo).any():
             raise ValueError(f"{what}: origin {origin_f.tolist()} lies above the vertices' minimum {lo.tolist()}")
         with np.errstate(all="ignore"):
             cells = np.floor((hi - origin_f) / cell_f)
-        if not (cells < 2 ** F.CELL_BITS).all():
+        if not (cells < 2 ** ops.simplify.CELL_BITS).all():
             raise ValueError(f"{what}: the vertices span {cells.tolist()} cells from the origin; the keys hold fewer than "
-                             f"2**{F.CELL_BITS} = {2 ** F.CELL_BITS} per axis")
+                             f"2**{ops.simplify.CELL_BITS} = {2 ** ops.simplify.CELL_BITS} per axis")
         origin = origin_f.tolist()
     if not vertices.is_cuda or not faces.is_cuda:
         raise ValueError(f"{what}: the mesh must live on the GPU (there is no CPU fallback)")
     if v == 0 or faces.shape[0] == 0:
         return empty()
-    clusters = F.cluster_vertices(vertices, cell, origin)                                   # host read 2: the cluster count
+    clusters = ops.simplify.cluster_vertices(vertices, cell, origin)                        # host read 2: the cluster count
     n_clusters = clusters['cluster_keys'].shape[0]
-    cfaces, used = F.cluster_faces(faces, clusters['vertex_cluster'], n_clusters, return_used=True)    # host read 3: F'
+    cfaces, used = ops.simplify.cluster_faces(faces, clusters['vertex_cluster'], n_clusters,
+                                              return_used=True)                             # host read 3: F'
     n_faces = cfaces.shape[0]
     if n_faces == 0:
         return empty()
-    rep = F.reduce_clusters(vertices, normals, colors, clusters, cell, origin, placement, regularization)
+    rep = ops.simplify.reduce_clusters(vertices, normals, colors, clusters, cell, origin, placement, regularization)
     scan = torch.cumsum(used, 0, dtype=torch.int32)
     n_out = int(scan[-1])                                                                   # host read 4: V'
     kept = torch.empty(n_out, dtype=torch.int32, device=dev)
     out_faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
     every_face = torch.arange(1, n_faces + 1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        F.L.launch("hn_mesh_compact", F.L.ptr(cfaces), F.L.ptr(scan), F.L.ptr(every_face), n_clusters, n_faces, n_out,
-                   n_faces, F.L.ptr(kept), F.L.ptr(out_faces), F.L.stream_handle())
-    out = {name: F.gather_rows(t, kept) for name, t in rep.items()}
+        L.launch("hn_mesh_compact", L.ptr(cfaces), L.ptr(scan), L.ptr(every_face), n_clusters, n_faces, n_out,
+                 n_faces, L.ptr(kept), L.ptr(out_faces), L.stream_handle())
+    out = {name: ops.mesh.gather_rows(t, kept) for name, t in rep.items()}
     out['faces'] = out_faces
-    out['vertex_cluster'] = F.relabel_vertices(clusters['vertex_cluster'], used, scan)
+    out['vertex_cluster'] = ops.simplify.relabel_vertices(clusters['vertex_cluster'], used, scan)
     return out
 
 
@@ -294,7 +296,7 @@ def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, co
     mesh = extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds)
     mesh = filter_mesh(mesh, min_faces=min_faces, keep_largest=keep_largest)
     if factor is not None:
-        shape, b = F.check_lattice(_resolution(resolution), bounds, "extract_mesh")
+        shape, b = ops.mesh.check_lattice(_resolution(resolution), bounds, "extract_mesh")
         cell = [k * (b[2 * c + 1] - b[2 * c]) / (shape[c] - 1) for c, k in enumerate(factor)]
         mesh = simplify_mesh(mesh, cell, origin=(b[0], b[2], b[4]))
     if colors is not None:
@@ -308,12 +310,12 @@ def _check_render_mesh(mesh, what: str):
     """(vertices, faces, normals, colors) of a mesh dict, checked as far as the host can, or ValueError."""
     if not isinstance(mesh, dict):
         raise ValueError(f"{what}: mesh must be a dict with 'vertices' and 'faces'")
-    vertices = F._check_points(mesh.get('vertices'), what, "vertices")
-    faces = F._check_mesh_faces(mesh.get('faces'), what)
+    vertices = ops.checks.check_points(mesh.get('vertices'), what, "vertices")
+    faces = ops.checks.check_mesh_faces(mesh.get('faces'), what)
     v = vertices.shape[0]
     normals, colors = mesh.get('normals'), mesh.get('colors')
     if normals is not None:
-        normals = F._check_points(normals, what, "normals", v)
+        normals = ops.checks.check_points(normals, what, "normals", v)
     if colors is not None and (not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (v, 3)
                                or colors.dtype not in (torch.uint8, torch.float32)):
         raise ValueError(f"{what}: colors must be a ({v}, 3) uint8 or float32 tensor")
@@ -342,21 +344,21 @@ def render_mesh(mesh: Dict[str, torch.Tensor], rays: torch.Tensor, camera, image
     ValueError: a face with a vertex id outside [0, V); more than 2**31 - 1 (tile, face) pairs.  One host read."""
     what = "render_mesh"
     vertices, faces, normals, colors = _check_render_mesh(mesh, what)
-    w, h = F.check_image_wh(image_wh, what)
-    camera = F._check_camera(camera, what)
-    rays = F._check_rays(rays, h * w, what)
-    F.check_shading(shading, ambient, background, base_color, what)
+    w, h = ops.mesh_render.check_image_wh(image_wh, what)
+    camera = ops.checks.check_camera(camera, what)
+    rays = ops.checks.check_rays(rays, h * w, what)
+    ops.mesh_render.check_shading(shading, ambient, background, base_color, what)
     if not vertices.is_cuda or not faces.is_cuda or not rays.is_cuda:
         raise ValueError(f"{what}: the mesh and the rays must live on the GPU (there is no CPU fallback)")
-    out = F.mesh_trace(vertices, faces, rays, camera, (w, h), binning=bool(binning))
-    out.update(F.mesh_shade(vertices, faces, normals, colors, rays, out['face'], out['bary'], shading, ambient, background,
-                            base_color))
+    out = ops.mesh_render.mesh_trace(vertices, faces, rays, camera, (w, h), binning=bool(binning))
+    out.update(ops.mesh_render.mesh_shade(vertices, faces, normals, colors, rays, out['face'], out['bary'], shading,
+                                          ambient, background, base_color))
     return {k: t.view((h, w) + tuple(t.shape[1:])) for k, t in out.items()}
 
 
 def camera_from_c2w(c2w, focal: float, W: int, H: int, ndc: bool = False) -> np.ndarray:
     """The (24,) fp32 camera record whose rays are the LLFF / Blender rays of the pose c2w (3, 4) with `focal`
-    (functional.generate_rays without NDC): orientation rows c2w[:, 0], -c2w[:, 1], -c2w[:, 2] (the pose looks along -z
+    (ops.data.generate_rays without NDC): orientation rows c2w[:, 0], -c2w[:, 1], -c2w[:, 2] (the pose looks along -z
     with y up, the record along +z with y down), position c2w[:, 3], principal point (W/2 + 0.5, H/2 + 0.5) (a pixel
     index there is a pixel centre here), no skew, no distortion.  The pose's rotation must be orthonormal, as a pose is.
     NDC scenes are refused: a mesh in NDC space is not seen through a pinhole camera."""
@@ -369,7 +371,7 @@ def camera_from_c2w(c2w, focal: float, W: int, H: int, ndc: bool = False) -> np.
     focal, W, H = float(focal), int(W), int(H)
     if not (np.isfinite(focal) and focal > 0.0) or W < 1 or H < 1:
         raise ValueError("camera_from_c2w: focal, W and H must be positive")
-    rec = np.zeros(F.NERFIES_CAM_FLOATS, dtype=np.float64)
+    rec = np.zeros(ops.data.NERFIES_CAM_FLOATS, dtype=np.float64)
     rec[0:3], rec[3:6], rec[6:9], rec[9:12] = c2w[:, 0], -c2w[:, 1], -c2w[:, 2], c2w[:, 3]
     rec[12:17] = (focal, 1.0, 0.0, W / 2 + 0.5, H / 2 + 0.5)
     return rec.astype(np.float32)
@@ -382,9 +384,9 @@ def orbit_cameras(center, radius: float, n: int, elevation: float = 0.0, up=(0.0
     `up` appears up in the image (the record's y axis points down).  focal in pixels, the principal point at the image
     centre (W/2, H/2), no skew, no distortion.  NumPy float64, rounded to fp32 at the end."""
     what = "orbit_cameras"
-    c = np.asarray(F._float3(center, f"{what}: center"), dtype=np.float64)
-    u = np.asarray(F._float3(up, f"{what}: up"), dtype=np.float64)
-    w, h = F.check_image_wh(image_wh, what)
+    c = np.asarray(ops.checks.float3(center, f"{what}: center"), dtype=np.float64)
+    u = np.asarray(ops.checks.float3(up, f"{what}: up"), dtype=np.float64)
+    w, h = ops.mesh_render.check_image_wh(image_wh, what)
     radius, focal, elevation, n = float(radius), float(focal), float(elevation), int(n)
     if n < 1:
         raise ValueError(f"{what}: n must be at least 1, got {n}")
@@ -399,7 +401,7 @@ def orbit_cameras(center, radius: float, n: int, elevation: float = 0.0, up=(0.0
     e1 /= np.linalg.norm(e1)
     e2 = np.cross(u, e1)
     el = np.deg2rad(elevation)
-    out = np.zeros((n, F.NERFIES_CAM_FLOATS), dtype=np.float64)
+    out = np.zeros((n, ops.data.NERFIES_CAM_FLOATS), dtype=np.float64)
     for k in range(n):
         az = 2.0 * np.pi * k / n
         pos = c + radius * (np.cos(el) * (np.cos(az) * e1 + np.sin(az) * e2) + np.sin(el) * u)
@@ -414,18 +416,18 @@ def orbit_cameras(center, radius: float, n: int, elevation: float = 0.0, up=(0.0
 
 def camera_rays(record, W: int, H: int, near: float, far: float, device=None) -> torch.Tensor:
     """(H*W, 8) fp32 ray rows [o, d, near, far] of a (24,) camera record, generated on the GPU
-    (functional.generate_rays_nerfies); `device`: where, the record's own device by default (a host record goes to the
+    (ops.data.generate_rays_nerfies); `device`: where, the record's own device by default (a host record goes to the
     current GPU)."""
-    cam = F._check_camera(record, "camera_rays")
-    w, h = F.check_image_wh((W, H), "camera_rays")
+    cam = ops.checks.check_camera(record, "camera_rays")
+    w, h = ops.mesh_render.check_image_wh((W, H), "camera_rays")
     if device is None and not cam.is_cuda:
         if not torch.cuda.is_available():
-            F.L.require_gpu(cam)
+            L.require_gpu(cam)
         device = torch.device("cuda", torch.cuda.current_device())
     if device is not None:
         cam = cam.to(device)
     with torch.cuda.device(cam.device):
-        return F.generate_rays_nerfies(h, w, cam, float(near), float(far))
+        return ops.data.generate_rays_nerfies(h, w, cam, float(near), float(far))
 
 
 @torch.no_grad()
@@ -439,12 +441,12 @@ def mesh_turntable(mesh: Dict[str, torch.Tensor], path, n: int = 60, image_wh=(2
     from . import inference
     what = "mesh_turntable"
     vertices, _, _, _ = _check_render_mesh(mesh, what)
-    w, h = F.check_image_wh(image_wh, what)
+    w, h = ops.mesh_render.check_image_wh(image_wh, what)
     if vertices.shape[0] == 0:
         raise ValueError(f"{what}: the mesh has no vertices")
     if not vertices.is_cuda:
         raise ValueError(f"{what}: the mesh must live on the GPU (there is no CPU fallback)")
-    lo, hi = (np.asarray(t, dtype=np.float64) for t in F.vertex_extent(vertices))
+    lo, hi = (np.asarray(t, dtype=np.float64) for t in ops.simplify.vertex_extent(vertices))
     if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
         raise ValueError(f"{what}: the vertices are not finite")
     half = max(0.5 * float(np.linalg.norm(hi - lo)), 1e-6)
@@ -496,7 +498,7 @@ def mesh_depth_error(model, mesh: Dict[str, torch.Tensor], rays: torch.Tensor, c
     same rays.  Tells whether the iso level, min_faces and the simplification cell left the surface where the field
     renders it."""
     from . import inference
-    w, h = F.check_image_wh(image_wh, "mesh_depth_error")
+    w, h = ops.mesh_render.check_image_wh(image_wh, "mesh_depth_error")
     field = inference.render_image(model, rays, chunk=chunk, level=level, keys=(depth_key, 'acc'))
     seen = render_mesh(mesh, rays, camera, (w, h), shading='none')
     return depth_agreement(seen['depth'], seen['face'], field[depth_key], field['acc'], acc_min=acc_min)

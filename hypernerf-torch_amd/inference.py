@@ -15,6 +15,7 @@ import torch
 
 from . import dist as hdist
 from .hypernerf import model_utils
+from .ops import gif
 
 _EXTRA = {'nerf_alpha': None, 'warp_alpha': None, 'hyper_alpha': None, 'hyper_sheet_alpha': None}
 
@@ -170,15 +171,15 @@ def read_pfm(path: str):
 
 # ------------------------------------------------------------------------------------------------------------------
 # The GIF of the evaluated frames (eval.py:172, imageio.mimsave(..., fps=30)).  A GIF colour table has at most 256
-# entries: the frames are quantised on the device (functional.color_histogram / palette_map), the palette is cut on the
-# host from the 2^18-cell table, the index maps are LZW-coded by the library's host code (functional.gif_lzw) and the
+# entries: the frames are quantised on the device (ops.gif.color_histogram / palette_map), the palette is cut on the
+# host from the 2^18-cell table, the index maps are LZW-coded by the library's host code (ops.gif.gif_lzw) and the
 # container is written with the standard library.
 # ------------------------------------------------------------------------------------------------------------------
 GIF_COLORS = 256
 
 
 def palette_from_histogram(hist, colors: int = GIF_COLORS):
-    """(palette (256, 3) uint8 array, n_colors) from a colour table of functional.color_histogram: a pure, deterministic
+    """(palette (256, 3) uint8 array, n_colors) from a colour table of ops.gif.color_histogram: a pure, deterministic
     function of the table (`colors`: fewer boxes than a GIF table holds, 1..256).  Entries are its non-empty cells: key k, count c, mean colour sums / c in float64.  With at
     most 256 entries the palette is floor(mean + 0.5) of each, in key order.  Otherwise median cut: one box holds all
     entries; until there are 256 boxes the box with more than one entry and the largest count_sum * range is cut (range:
@@ -260,7 +261,6 @@ def quantize_frames(frames, palette: str = "global"):
     indices: one (H, W) uint8 host tensor per frame, each pixel the nearest USED palette entry (squared RGB distance,
     the smaller index among equals).  No dithering."""
     from . import _lib as L
-    from . import functional as F
     if palette not in ("global", "frame"):
         raise ValueError("palette: 'global' or 'frame'")
     frames = _check_frames(frames, "quantize_frames")
@@ -274,16 +274,16 @@ def quantize_frames(frames, palette: str = "global"):
     if palette == "global":
         table = None
         for f in frames:
-            table = F.color_histogram(f, out=table)
+            table = gif.color_histogram(f, out=table)
         pal, n_colors = palette_from_histogram(table)
         palettes.append(torch.from_numpy(pal))
         pal_dev = palettes[0][:n_colors].to(dev)
-        indices = [F.palette_map(f, pal_dev).cpu() for f in frames]
+        indices = [gif.palette_map(f, pal_dev).cpu() for f in frames]
     else:
         for f in frames:
-            pal, n_colors = palette_from_histogram(F.color_histogram(f))
+            pal, n_colors = palette_from_histogram(gif.color_histogram(f))
             palettes.append(torch.from_numpy(pal))
-            indices.append(F.palette_map(f, palettes[-1][:n_colors].to(dev)).cpu())
+            indices.append(gif.palette_map(f, palettes[-1][:n_colors].to(dev)).cpu())
     return palettes, indices
 
 
@@ -295,10 +295,9 @@ def write_gif(path: str, frames, fps: float = 30, loop: int = 0, palette: str = 
     front of every image, always 256 entries; the NETSCAPE2.0 application block with `loop` repetitions (0 = for ever);
     per frame a graphic control extension with the delay max(1, round(100 / fps)) centiseconds (fps=30 gives 3, as
     imageio and Pillow write it), no disposal, no transparency; an image descriptor covering the whole screen; LZW
-    minimum code size 8 and the code bytes of functional.gif_lzw in sub-blocks of at most 255.  ValueError: no frames,
+    minimum code size 8 and the code bytes of ops.gif.gif_lzw in sub-blocks of at most 255.  ValueError: no frames,
     frames of differing size, a side above 65535."""
     import struct
-    from . import functional as F
     if palette not in ("global", "frame"):
         raise ValueError("palette: 'global' or 'frame'")
     if not fps > 0:
@@ -340,7 +339,7 @@ def write_gif(path: str, frames, fps: float = 30, loop: int = 0, palette: str = 
         out.append(b"\x2c" + struct.pack("<HHHHB", 0, 0, w, h, 0x00 if palette == "global" else 0x87))
         if palette == "frame":
             out.append(table(palettes[i]))
-        codes = F.gif_lzw(idx.cpu().contiguous())
+        codes = gif.gif_lzw(idx.cpu().contiguous())
         out.append(b"\x08")
         out.extend(bytes([len(codes[s:s + 255])]) + codes[s:s + 255] for s in range(0, len(codes), 255))
         out.append(b"\x00")
@@ -490,12 +489,11 @@ def _unit_u8(device) -> torch.Tensor:
 @torch.no_grad()
 def visualize_depth(depth: torch.Tensor, lut=None) -> torch.Tensor:
     """(H, W) depth on the device -> the (3, H, W) float32 picture of utils/visualization.py:visualize_depth, on the
-    device: nan_to_num, min-max normalisation, (255 x).astype(uint8), the colour table (functional.depth_colormap: HIP,
+    device: nan_to_num, min-max normalisation, (255 x).astype(uint8), the colour table (ops.gif.depth_colormap: HIP,
     no host read) and ToTensor's uint8 / 255.  `lut`: a (256, 3) uint8 table, jet_lut() by default."""
-    from . import functional as F
     if not isinstance(depth, torch.Tensor) or depth.dim() != 2:
         raise ValueError("visualize_depth: depth must be an (H, W) tensor")
-    img8 = F.depth_colormap(depth.detach().float(), jet_lut() if lut is None else lut)
+    img8 = gif.depth_colormap(depth.detach().float(), jet_lut() if lut is None else lut)
     return _unit_u8(img8.device)[img8.long()].permute(2, 0, 1).contiguous()
 
 
@@ -534,7 +532,7 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     'bytes' — the reference writes that file into the current directory (eval.py:157), this port into `save_dir`.
     `save_gif='scene'` writes the reference's GIF of all frames (eval.py:172, imageio.mimsave(..., fps=30)) as
     `save_dir/scene.gif` from the 8-bit frames formed here, quantised on the device (`write_gif` with `gif_fps` and
-    `gif_palette`); `save_depth_gif` writes the colour-mapped depths (functional.depth_colormap with jet_lut(), the
+    `gif_palette`); `save_depth_gif` writes the colour-mapped depths (ops.gif.depth_colormap with jet_lut(), the
     picture of visualize_depth) as `scene_depth.gif` (`depth.gif` without `save_gif`).  Both need `save_dir`; without
     them the files written, the result and the work done are unchanged.
     `white_back` is accepted and ignored as in the reference's batched_inference (eval.py:77-85).
@@ -559,7 +557,6 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     imgs, depths, psnrs, ssims, ms_ssims = [], [], [], [], []
     gif_frames, depth_frames = [], []
     if save_depth_gif:
-        from .functional import depth_colormap
         lut = jet_lut()
     for i, sample in enumerate(images):
         rays = sample['rays']
@@ -573,7 +570,7 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
         if save_gif is not None:
             gif_frames.append(img8_dev)
         if save_depth_gif:
-            depth_frames.append(depth_colormap(res['depth'].view(h, w).float(), lut))
+            depth_frames.append(gif.depth_colormap(res['depth'].view(h, w).float(), lut))
         depths.append(torch.nan_to_num(res['depth'].view(h, w)).cpu())
         if sample.get('rgbs') is not None:
             gt = sample['rgbs'].to(img.device).view(h, w, 3)

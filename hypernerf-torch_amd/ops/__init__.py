@@ -1,0 +1,16 @@
+"""The host halves of the kernels outside the training step, one module per kernel source file:
+
+    metrics      csrc/hn_metrics.hip, csrc/hn_msssim.hip    SSIM (differentiable) and multi-scale SSIM
+    mesh         csrc/hn_geometry.hip                        lattice points, isosurface, components, compaction
+    simplify     csrc/hn_simplify.hip                        vertex clustering
+    mesh_render  csrc/hn_mesh_render.hip                     projection, binning, ray casting, shading
+    data         csrc/hn_data.hip                            ray generation, batch gathers, blend, Pillow-exact resize
+    gif          csrc/hn_gif.hip                             colour histogram, palette map, LZW, depth colour map
+    checks       —                                           argument validators more than one of them uses
+
+They import the binding (_lib), torch, numpy and each other, never functional, machine or arena: functional imports
+them and re-exports their public names.
+"""
+from . import checks, data, gif, mesh, mesh_render, metrics, simplify
+
+__all__ = ["checks", "data", "gif", "mesh", "mesh_render", "metrics", "simplify"]

@@ -1,0 +1,273 @@
+"""Geometry out of a trained field (csrc/hn_geometry.hip): lattice points, the isosurface by marching tetrahedra,
+connected components of a mesh and its compaction, view directions of its vertices."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import torch
+
+from .. import _lib as L
+from .checks import INT32_MAX, check_faces
+
+__all__ = ["ISO_BLOCK", "check_lattice", "grid_points", "density_activate", "extract_isosurface", "mesh_components",
+           "component_sizes", "gather_rows", "compact_mesh", "vertex_viewdirs"]
+
+ISO_BLOCK = L.HN_ISO_BLOCK    # lattice points (cells) per workgroup of the hn_iso_* passes
+
+
+def check_lattice(shape, bounds, what: str):
+    """(nx, ny, nz) and the six bounds of a lattice as the hn_geometry entry points accept them, or ValueError."""
+    try:
+        nx, ny, nz = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the lattice must have three sides, got {shape!r}") from None
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"{what}: every side of the lattice needs at least 2 points, got {(nx, ny, nz)}")
+    if 7 * nx * ny * nz > INT32_MAX:
+        raise ValueError(f"{what}: 7 * {nx} * {ny} * {nz} = {7 * nx * ny * nz} edge slots exceed the int32 limit "
+                         f"2**31 - 1 = {INT32_MAX} of the mesh indices")
+    try:
+        bounds = tuple(float(v) for v in bounds)
+    except (TypeError, ValueError):
+        bounds = ()
+    if len(bounds) != 6:
+        raise ValueError(f"{what}: bounds must be (xmin, xmax, ymin, ymax, zmin, zmax), got {bounds!r}")
+    if not all(hi > lo for lo, hi in zip(bounds[0::2], bounds[1::2])):
+        raise ValueError(f"{what}: bounds need hi > lo on every axis, got {bounds}")
+    return (nx, ny, nz), bounds
+
+
+@torch.no_grad()
+def grid_points(shape, bounds, start: int, count: int, device) -> torch.Tensor:
+    """(count, 3) fp32: lattice points start .. start + count - 1 of the (nx, ny, nz) lattice over `bounds`
+    (hn_grid_points), p = (i*ny + j)*nz + k at lo + (i, j, k) * (hi - lo)/(n - 1); indices past the lattice repeat its last
+    point.  float32 NumPy gives the same bits."""
+    (nx, ny, nz), bounds = check_lattice(shape, bounds, "grid_points")
+    if not 0 <= start < nx * ny * nz or not 0 < count <= INT32_MAX:
+        raise ValueError(f"grid_points: start {start} / count {count} outside the lattice of {nx * ny * nz} points")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.HnError("hypernerf_torch_amd runs on MI355X only: grid_points needs a GPU device")
+    L.load()
+    out = torch.empty((count, 3), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        L.launch("hn_grid_points", nx, ny, nz, (C.c_float * 6)(*bounds), start, count, L.ptr(out),
+                 L.stream_handle())
+    return out
+
+
+@torch.no_grad()
+def density_activate(raw: torch.Tensor, points: torch.Tensor, render_opts=None) -> torch.Tensor:
+    """Raw densities (...,) of points (..., 3) -> Softplus, then filter_sigma (dust threshold, bounding box) exactly as the
+    compositing kernel applies them (hn_density_activate), as fp32 of raw's shape."""
+    L.require_gpu(raw, points)
+    L.load()
+    raw = raw.detach().float().contiguous()
+    has_dust, dust, box = 0, 0.0, None
+    if render_opts is not None:
+        if 'dust_threshold' in render_opts:
+            has_dust, dust = 1, float(render_opts.get('dust_threshold', 0.0))
+        if 'bounding_box' in render_opts:
+            box = (C.c_float * 6)(*(float(v) for v in render_opts['bounding_box']))
+            points = points.detach().float().contiguous()
+            if points.shape != raw.shape + (3,):
+                raise ValueError(f"density_activate: points {tuple(points.shape)} do not match raw {tuple(raw.shape)}")
+    out = torch.empty_like(raw)
+    if raw.numel():
+        L.launch("hn_density_activate", L.ptr(raw), L.ptr(points) if box is not None else None, raw.numel(),
+                 has_dust, dust, box, L.ptr(out), L.stream_handle())
+    return out
+
+
+@torch.no_grad()
+def extract_isosurface(grid: torch.Tensor, iso: float, bounds) -> Dict[str, torch.Tensor]:
+    """Indexed triangle mesh of the surface grid = iso by marching tetrahedra (hn_iso_*): grid (nx, ny, nz) fp32,
+    C-contiguous, on the GPU, its points spread over bounds (xmin, xmax, ymin, ymax, zmin, zmax) ->
+    {'vertices': (V, 3) fp32, 'normals': (V, 3) fp32 unit (from inside, grid >= iso, to outside), 'faces': (F, 3) int32}.
+    Vertices ascend with their edge slot, faces with cell, tetrahedron, triangle: the same grid gives the same arrays on
+    every run.  An empty surface gives zero-length tensors.  Working memory: 28 bytes of edge slots + 1 of marks per
+    lattice point.  Two host synchronisations (the vertex and the face count size the outputs)."""
+    if not isinstance(grid, torch.Tensor) or grid.dim() != 3:
+        raise ValueError("extract_isosurface: grid must be a (nx, ny, nz) tensor")
+    (nx, ny, nz), bounds = check_lattice(grid.shape, bounds, "extract_isosurface")
+    if grid.dtype != torch.float32:
+        raise ValueError(f"extract_isosurface: grid must be float32, got {grid.dtype}")
+    if not grid.is_contiguous():
+        raise ValueError("extract_isosurface: grid must be C-contiguous")
+    if not grid.is_cuda:
+        raise ValueError("extract_isosurface: grid must live on the GPU (there is no CPU fallback)")
+    L.load()
+    f = grid.detach()
+    dev = f.device
+    empty = {'vertices': torch.zeros((0, 3), dtype=torch.float32, device=dev),
+             'normals': torch.zeros((0, 3), dtype=torch.float32, device=dev),
+             'faces': torch.zeros((0, 3), dtype=torch.int32, device=dev)}
+    n = nx * ny * nz
+    iso = float(iso)
+    with torch.cuda.device(dev):
+        stream = L.stream_handle()
+        # pass A: marks and per-workgroup counts; the scan of the counts is torch's
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        counts = torch.empty((n + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
+        L.launch("hn_iso_mark", L.ptr(f), nx, ny, nz, iso, L.ptr(mask), L.ptr(counts), stream)
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        n_vertices = int(ends[-1])
+        if n_vertices == 0:
+            return empty
+        # pass B
+        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+        slots = torch.empty(7 * n, dtype=torch.int32, device=dev)
+        offsets = ends - counts
+        L.launch("hn_iso_vertices", L.ptr(f), nx, ny, nz, (C.c_float * 6)(*bounds), iso, L.ptr(mask),
+                 L.ptr(offsets), L.ptr(vertices), L.ptr(normals), L.ptr(slots), stream)
+        # pass C: count, scan, emit
+        n_cells = (nx - 1) * (ny - 1) * (nz - 1)
+        fcounts = torch.empty((n_cells + ISO_BLOCK - 1) // ISO_BLOCK, dtype=torch.int32, device=dev)
+        L.launch("hn_iso_faces", L.ptr(f), nx, ny, nz, iso, None, None, L.ptr(fcounts), None, stream)
+        fends = torch.cumsum(fcounts, 0, dtype=torch.int64)
+        n_faces = int(fends[-1])
+        if n_faces > INT32_MAX:
+            raise ValueError(f"extract_isosurface: {n_faces} faces exceed the int32 limit 2**31 - 1 = {INT32_MAX}")
+        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+        if n_faces:
+            foffsets = fends - fcounts
+            L.launch("hn_iso_faces", L.ptr(f), nx, ny, nz, iso, L.ptr(slots), L.ptr(foffsets), None,
+                     L.ptr(faces), stream)
+    return {'vertices': vertices, 'normals': normals, 'faces': faces}
+
+
+@torch.no_grad()
+def mesh_components(faces: torch.Tensor, num_vertices: int, out: Optional[torch.Tensor] = None,
+                    return_rounds: bool = False):
+    """labels (V,) int32 of the mesh faces (F, 3) int32 over V vertices: the SMALLEST vertex id of the vertex's connected
+    component (two vertices are connected when a face holds both; an unreferenced vertex is its own component) — a
+    definition that no scheduling can change, so two runs give the same bits (hn_cc_init / hn_cc_round: hook and
+    pointer-jump rounds with integer atomicMin).  One host read of two ints per round; the loop is capped at V + 1 rounds
+    (min-label propagation needs at most V - 1 that change something, every round here does at least its step) and a
+    RuntimeError names the cap if it is ever exceeded.  A vertex id outside [0, V) is a ValueError; nothing is written
+    outside the label array.  `out`: a contiguous (V,) int32 tensor to label in place.  `return_rounds`: (labels, rounds
+    run, the last one included that changed nothing)."""
+    faces, v = check_faces(faces, num_vertices, "mesh_components")
+    dev = faces.device
+    if out is None:
+        out = torch.empty(v, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.shape != (v,) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"mesh_components: out must be a contiguous ({v},) int32 tensor on {dev}")
+    n_faces = faces.shape[0]
+    rounds = 0
+    if v == 0 and n_faces == 0:
+        return (out, rounds) if return_rounds else out
+    L.load()
+    cap = v + 1
+    with torch.cuda.device(dev):
+        stream = L.stream_handle()
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        L.launch("hn_cc_init", L.ptr(faces) if n_faces else None, n_faces, L.ptr(out) if v else None, v,
+                 L.ptr(flags), stream)
+        if n_faces == 0:
+            return (out, rounds) if return_rounds else out
+        if v == 0:
+            raise ValueError("mesh_components: faces hold a vertex id outside [0, 0)")
+        while True:
+            rounds += 1
+            if rounds > cap:
+                raise RuntimeError(f"mesh_components: no fixed point after the cap of V + 1 = {cap} rounds")
+            L.launch("hn_cc_round", L.ptr(faces), n_faces, L.ptr(out), v, rounds, L.ptr(flags), stream)
+            err, changed = flags.tolist()
+            if err:
+                raise ValueError(f"mesh_components: faces hold a vertex id outside [0, {v})")
+            if changed != rounds:
+                break
+    return (out, rounds) if return_rounds else out
+
+
+@torch.no_grad()
+def component_sizes(labels: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """(V,) int32: the number of faces of every component at index = its label (mesh_components), zero elsewhere
+    (hn_cc_sizes: integer atomic adds, whose sum does not depend on their order).  No host synchronisation: an id or a
+    label outside [0, V) is skipped (mesh_components refuses such faces first)."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 1 or labels.dtype != torch.int32:
+        raise ValueError("component_sizes: labels must be a (V,) int32 tensor")
+    faces, v = check_faces(faces, labels.shape[0], "component_sizes")
+    L.require_gpu(labels)
+    sizes = torch.zeros(v, dtype=torch.int32, device=faces.device)
+    if v and faces.shape[0]:
+        L.load()
+        with torch.cuda.device(faces.device):
+            flags = torch.zeros(2, dtype=torch.int32, device=faces.device)
+            L.launch("hn_cc_sizes", L.ptr(labels.detach().contiguous()), L.ptr(faces), faces.shape[0], v,
+                     L.ptr(sizes), L.ptr(flags), L.stream_handle())
+    return sizes
+
+
+@torch.no_grad()
+def gather_rows(src: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """src[index] along the first dimension for an int32 index (hn_gather_rows): any dtype, any trailing shape."""
+    L.require_gpu(src, index)
+    src = src.detach().contiguous()
+    n = index.shape[0]
+    out = torch.empty((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    if out.numel():
+        L.load()
+        row_bytes = out.numel() // n * out.element_size()
+        with torch.cuda.device(src.device):
+            L.launch("hn_gather_rows", L.ptr(src), src.shape[0], L.ptr(index), n, row_bytes, L.ptr(out),
+                     L.stream_handle())
+    return out
+
+
+@torch.no_grad()
+def compact_mesh(faces: torch.Tensor, labels: torch.Tensor, keep_comp: torch.Tensor):
+    """(vertex_index (V',) int32, faces (F', 3) int32): the vertices whose component is kept (keep_comp: (V,) bool or
+    uint8 indexed by label) in their old order, and the faces of those components in their old order, re-indexed
+    (hn_mesh_keep, two torch.cumsum scans, hn_mesh_compact).  One host read (both counts at once) sizes the outputs."""
+    faces, v = check_faces(faces, labels.shape[0], "compact_mesh")
+    dev = faces.device
+    n_faces = faces.shape[0]
+    if v == 0:
+        return torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev)
+    L.load()
+    keep_comp = keep_comp.to(torch.uint8).contiguous()
+    with torch.cuda.device(dev):
+        stream = L.stream_handle()
+        vkeep = torch.empty(v, dtype=torch.int32, device=dev)
+        fkeep = torch.empty(max(n_faces, 1), dtype=torch.int32, device=dev)
+        if n_faces == 0:
+            fkeep.zero_()
+        L.launch("hn_mesh_keep", L.ptr(labels.contiguous()), L.ptr(faces) if n_faces else None, L.ptr(keep_comp),
+                 v, n_faces, L.ptr(vkeep), L.ptr(fkeep), stream)
+        vscan = torch.cumsum(vkeep, 0, dtype=torch.int32)
+        fscan = torch.cumsum(fkeep, 0, dtype=torch.int32)
+        n_v, n_f = torch.stack([vscan[-1], fscan[-1]]).tolist()
+        vertex_index = torch.empty(n_v, dtype=torch.int32, device=dev)
+        faces_out = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
+        if n_v:
+            L.launch("hn_mesh_compact", L.ptr(faces) if n_faces else None, L.ptr(vscan), L.ptr(fscan), v, n_faces,
+                     n_v, n_f, L.ptr(vertex_index), L.ptr(faces_out) if n_f else None, stream)
+    return vertex_index, faces_out
+
+
+@torch.no_grad()
+def vertex_viewdirs(vertices: torch.Tensor, normals: Optional[torch.Tensor], start: int, count: int,
+                    camera=None) -> torch.Tensor:
+    """(count, 3) fp32 unit directions for vertices start .. start + count - 1 (hn_vertex_viewdirs; rows past the mesh
+    repeat its last vertex): -normal/|normal| when `camera` is None, else (v - camera)/|v - camera| for the three host
+    floats `camera`; a zero length gives (0, 0, 1).  float32 NumPy gives the same values to a few roundings."""
+    L.require_gpu(vertices, normals)
+    ref = vertices if camera is not None else normals
+    if ref is None or ref.dim() != 2 or ref.shape[1] != 3 or ref.dtype != torch.float32:
+        raise ValueError("vertex_viewdirs: vertices / normals must be (V, 3) float32")
+    v = ref.shape[0]
+    if not 0 <= start < v or not 0 < count <= INT32_MAX:
+        raise ValueError(f"vertex_viewdirs: start {start} / count {count} outside the mesh of {v} vertices")
+    L.load()
+    ref = ref.detach().contiguous()
+    out = torch.empty((count, 3), dtype=torch.float32, device=ref.device)
+    cam = None if camera is None else (C.c_float * 3)(*(float(x) for x in camera))
+    with torch.cuda.device(ref.device):
+        L.launch("hn_vertex_viewdirs", L.ptr(ref) if camera is not None else None,
+                 L.ptr(ref) if camera is None else None, v, start, count, cam, L.ptr(out),
+                 L.stream_handle())
+    return out
