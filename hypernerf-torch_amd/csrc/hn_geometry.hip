@@ -20,29 +20,9 @@
 // Ranks inside a block come from wave64 ballots (one per bit plane) and four wave totals in LDS: the same input gives the
 // same arrays on every run.  All four kernels stream the grid once (neighbours come out of L2) and are HBM bound:
 // 28 bytes of slots per lattice point are the largest term.
-#include "hn_common.h"
+#include "hn_camera.h"
 
-struct HnLattice {
-  int nx, ny, nz;
-  float lo[3], step[3];
-};
-
-// host: lo and step of a lattice; false when a side has fewer than 2 points, hi <= lo, or 7 * points overflow int32
-static bool hn_lattice(int nx, int ny, int nz, const float* bounds, HnLattice* out) {
-  if (nx < 2 || ny < 2 || nz < 2) return false;
-  if ((long long)nx * ny * nz * 7 > 2147483647ll) return false;
-  out->nx = nx; out->ny = ny; out->nz = nz;
-  const int n[3] = {nx, ny, nz};
-  for (int c = 0; c < 3; ++c) {
-    const float lo = bounds != nullptr ? bounds[2 * c] : 0.0f, hi = bounds != nullptr ? bounds[2 * c + 1] : 1.0f;
-    if (!(hi > lo)) return false;
-    out->lo[c] = lo;
-    out->step[c] = (hi - lo) / (float)(n[c] - 1);
-  }
-  return true;
-}
-
-HN_DEV float hn_lattice_pos(const HnLattice& g, int c, int idx) { return __fadd_rn(g.lo[c], __fmul_rn((float)idx, g.step[c])); }
+// HnLattice, hn_lattice (host) and hn_lattice_pos (device) live in hn_camera.h, shared with hn_fusion.hip
 
 // ------------------------------------------------------------------------------------------------
 // hn_grid_points: out[r] = position of lattice point min(start + r, N - 1), r < count — a chunk of the lattice as the

@@ -19,11 +19,9 @@
 // conservative: the picture does not depend on it — but for a near-degenerate sliver face, whose edge values are rounding
 // noise for every ray on the extension of its line: the definition can report a hit there, which binning confines to the
 // face's own tiles (limits).
-#include "hn_common.h"
+#include "hn_camera.h"
 
 #define HN_MESH_BATCH 64           // faces staged through LDS at a time
-#define HN_MESH_BEHIND 1           // vertex flag: z <= 1e-6 in the camera frame
-#define HN_MESH_UNPROJECTABLE 2    // vertex flag: the radial map folds at its radius, or a coordinate is not finite
 
 HN_DEV float hn_mr_dot(const float* a, const float* b) {
   return __fadd_rn(__fadd_rn(__fmul_rn(a[0], b[0]), __fmul_rn(a[1], b[1])), __fmul_rn(a[2], b[2]));
@@ -46,35 +44,8 @@ HN_DEV float hn_mr_edge(const float* d, const float* P, const float* Q, int32_t 
   return -hn_mr_dot(d, c);
 }
 
-// ------------------------------------------------------------------------------------------------
-// The forward camera model (the closed form of the system hn_nerfies_pixel_ray inverts by Newton steps): a world point
-// to pixel coordinates (u, v), pixel (col i, row j) covering [i, i + 1) x [j, j + 1).  Returns the flags of the point.
-// It feeds the bins only, so its rounding is of no consequence to the picture.
-// ------------------------------------------------------------------------------------------------
-HN_DEV int hn_mr_project(const float* __restrict__ cam, float px, float py, float pz, float* u, float* v) {
-  const float qx = px - cam[9], qy = py - cam[10], qz = pz - cam[11];
-  const float xc = cam[0] * qx + cam[1] * qy + cam[2] * qz;
-  const float yc = cam[3] * qx + cam[4] * qy + cam[5] * qz;
-  const float zc = cam[6] * qx + cam[7] * qy + cam[8] * qz;
-  *u = 0.0f;
-  *v = 0.0f;
-  if (zc <= 1e-6f) return HN_MESH_BEHIND;
-  if (!(zc <= 3.402823466e38f)) return HN_MESH_UNPROJECTABLE;      // NaN or +inf
-  const float f = cam[12], aspect = cam[13], skew = cam[14], cx = cam[15], cy = cam[16];
-  const float k1 = cam[17], k2 = cam[18], k3 = cam[19], p1 = cam[20], p2 = cam[21];
-  const float x = xc / zc, y = yc / zc;
-  const float r = x * x + y * y;
-  if (!(1.0f + r * (3.0f * k1 + r * (5.0f * k2 + r * 7.0f * k3)) > 0.0f)) return HN_MESH_UNPROJECTABLE;
-  const float radial = 1.0f + r * (k1 + r * (k2 + k3 * r));
-  const float xd = x * radial + 2.0f * p1 * x * y + p2 * (r + 2.0f * x * x);
-  const float yd = y * radial + 2.0f * p2 * x * y + p1 * (r + 2.0f * y * y);
-  const float uu = f * xd + skew * yd + cx, vv = f * aspect * yd + cy;
-  if (!(fabsf(uu) <= 3.402823466e38f) || !(fabsf(vv) <= 3.402823466e38f)) return HN_MESH_UNPROJECTABLE;
-  *u = uu;
-  *v = vv;
-  return 0;
-}
-
+// hn_mesh_project: the forward camera model (hn_mr_project, hn_camera.h) per vertex.  It feeds the bins only, so its
+// rounding is of no consequence to the picture.
 __global__ __launch_bounds__(256) void hn_mesh_project_kernel(const float* __restrict__ vertices, long long n_vertices,
                                                               const float* __restrict__ cam, float* __restrict__ pix,
                                                               int32_t* __restrict__ flags) {

@@ -35,6 +35,14 @@ compare its depth with the field's along the same rays, and `mesh_turntable` wri
     img = render_mesh(mesh, rays, cam, (W, H))          # img['rgb8'] (H, W, 3) uint8, img['depth'] (H, W)
     mesh_depth_error(model, mesh, rays, cam, (W, H))    # {'abs_mean', 'rmse', 'iou', 'n'}
     mesh_turntable(mesh, "turntable.gif", n=60)
+
+Depth fusion: a level set of the density needs an `iso`, and a NeRF's density is no distance.  `extract_mesh_fused`
+renders depth from cameras around the frame (`depth_images_from_field`), integrates the depth maps into a truncated
+signed distance volume (`fuse_depth`, csrc/hn_fusion.hip) and meshes its zero level set
+(`tsdf_isosurface`): what is visible defines the surface, and rays that pass through carve the floaters away.
+
+    cams = orbit_cameras((0, 0, 0), 3.0, 60, 20.0, focal=400.0, image_wh=(W, H))
+    mesh = extract_mesh_fused(model, bounds, 256, 12, cams, (W, H), near, far, keep_largest=1)
 """
 from __future__ import annotations
 
@@ -284,6 +292,20 @@ def simplify_mesh(mesh: Dict[str, torch.Tensor], cell, origin=None, placement: s
     return out
 
 
+def _finish_mesh(mesh, model, bounds, resolution, frame_id, factor, colors, min_faces, keep_largest, kw):
+    """The tail extract_mesh and extract_mesh_fused share: filter_mesh, simplify_mesh by `factor` lattice spacings (None: not
+    at all), vertex_colors(view=colors) on what survived."""
+    mesh = filter_mesh(mesh, min_faces=min_faces, keep_largest=keep_largest)
+    if factor is not None:
+        shape, b = ops.mesh.check_lattice(_resolution(resolution), bounds, "extract_mesh")
+        cell = [k * (b[2 * c + 1] - b[2 * c]) / (shape[c] - 1) for c, k in enumerate(factor)]
+        mesh = simplify_mesh(mesh, cell, origin=(b[0], b[2], b[4]))
+    if colors is not None:
+        mesh = dict(mesh)
+        mesh['colors'] = vertex_colors(model, mesh['vertices'], mesh['normals'], frame_id, view=colors, **kw)
+    return mesh
+
+
 def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, colors=None, min_faces: Optional[int] = None,
                  keep_largest: Optional[int] = None, simplify=None, **kw) -> Dict[str, torch.Tensor]:
     """extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds), then
@@ -294,15 +316,147 @@ def extract_mesh(model, bounds, resolution, frame_id: int, iso: float = 10.0, co
     render_opts."""
     factor = None if simplify is None else _simplify_factor(simplify)
     mesh = extract_isosurface(density_grid(model, bounds, resolution, frame_id, **kw), iso, bounds)
-    mesh = filter_mesh(mesh, min_faces=min_faces, keep_largest=keep_largest)
-    if factor is not None:
-        shape, b = ops.mesh.check_lattice(_resolution(resolution), bounds, "extract_mesh")
-        cell = [k * (b[2 * c + 1] - b[2 * c]) / (shape[c] - 1) for c, k in enumerate(factor)]
-        mesh = simplify_mesh(mesh, cell, origin=(b[0], b[2], b[4]))
-    if colors is not None:
-        mesh = dict(mesh)
-        mesh['colors'] = vertex_colors(model, mesh['vertices'], mesh['normals'], frame_id, view=colors, **kw)
-    return mesh
+    return _finish_mesh(mesh, model, bounds, resolution, frame_id, factor, colors, min_faces, keep_largest, kw)
+
+
+# ---- depth fusion: a surface where the field RENDERS it (csrc/hn_fusion.hip, DESIGN.md 3.12) ----------------------------
+def _refuse_ndc(ndc, what: str):
+    if ndc:
+        raise ValueError(f"{what}: NDC rays have no pinhole camera (the NDC transform moves origins and bends directions "
+                         "per pixel) and their depth is no distance; fuse depth in world space with ndc=False rays")
+
+
+def _check_cameras(cameras, what: str) -> torch.Tensor:
+    """(N >= 1, 24) float32 camera records as a tensor (a host array is copied and stays on the host), or ValueError."""
+    if not isinstance(cameras, torch.Tensor) and hasattr(cameras, "__array__"):
+        cameras = torch.from_numpy(np.array(cameras))      # a copy: the array may be read-only
+    n_floats = ops.data.NERFIES_CAM_FLOATS
+    if (not isinstance(cameras, torch.Tensor) or cameras.dim() != 2 or cameras.shape[1] != n_floats
+            or cameras.dtype != torch.float32 or cameras.shape[0] < 1):
+        raise ValueError(f"{what}: cameras must be (N >= 1, {n_floats}) float32 camera records")
+    return cameras.detach()
+
+
+@torch.no_grad()
+def fuse_depth(depths: torch.Tensor, cameras, bounds, resolution, trunc: Optional[float] = None,
+               volume: Optional[Dict[str, torch.Tensor]] = None, *, ndc: bool = False) -> Dict[str, torch.Tensor]:
+    """{'tsdf', 'weight'}: two (nx, ny, nz) fp32 volumes on the device of `depths`, the depth images (N, H, W) fp32 seen
+    through `cameras` (N, 24) (camera_from_c2w, orbit_cameras, NerfiesDataset.camera_record; NDC scenes have no such
+    camera) integrated into a truncated signed distance volume on the lattice of `resolution` points over `bounds`
+    (ops.mesh.tsdf_integrate).  A depth is the distance along the unit ray from the camera position — what
+    render_image's and render_mesh's depth are —, +inf where the ray hit nothing, anything not > 0 where nothing is
+    known.  tsdf is positive in front of the surface (1 = at least `trunc` in front), negative behind it down to -1,
+    and means nothing where weight (the number of views that saw the point) is 0.  trunc: 4 times the largest lattice
+    spacing by default.  volume: an earlier result on the same lattice, continued IN PLACE and returned.  ndc=True (the
+    scene's rays are NDC rays) is refused, as camera_from_c2w refuses it."""
+    what = "fuse_depth"
+    _refuse_ndc(ndc, what)
+    shape, bounds = ops.mesh.check_lattice(_resolution(resolution), bounds, what)
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 3 or depths.dtype != torch.float32:
+        raise ValueError(f"{what}: depths must be a (N, H, W) float32 tensor")
+    cameras = _check_cameras(cameras, what)
+    if cameras.shape[0] != depths.shape[0]:
+        raise ValueError(f"{what}: {depths.shape[0]} depth images for {cameras.shape[0]} cameras")
+    if trunc is None:
+        trunc = 4.0 * max((bounds[2 * c + 1] - bounds[2 * c]) / (shape[c] - 1) for c in range(3))
+    trunc = float(trunc)
+    if not (np.isfinite(trunc) and trunc > 0.0):
+        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
+    if volume is not None:
+        if not isinstance(volume, dict) or 'tsdf' not in volume or 'weight' not in volume:
+            raise ValueError(f"{what}: volume must be a dict with 'tsdf' and 'weight', as fuse_depth returns it")
+        for k in ('tsdf', 'weight'):
+            ops.mesh.check_volume(volume[k], what, f"volume['{k}']", shape)
+    if not depths.is_cuda:
+        raise ValueError(f"{what}: depths must live on the GPU (there is no CPU fallback)")
+    if volume is None:
+        volume = {k: torch.zeros(shape, dtype=torch.float32, device=depths.device) for k in ('tsdf', 'weight')}
+    ops.mesh.tsdf_integrate(volume['tsdf'], volume['weight'], bounds, cameras.to(depths.device), depths, trunc)
+    return {'tsdf': volume['tsdf'], 'weight': volume['weight']}
+
+
+@torch.no_grad()
+def depth_images_from_field(model, cameras, image_wh, frame_id: int, near: float, far: float, acc_min: float = 0.5,
+                            acc_free: float = 0.05, normalize: bool = True, level: str = 'fine',
+                            chunk: int = 16384, *, ndc: bool = False) -> torch.Tensor:
+    """(N, H, W) fp32 depth images of the field at frame `frame_id` through `cameras` (N, 24), in fuse_depth's convention.
+    Per camera: camera_rays(near, far), a ninth column holding frame_id (as the rays of a dataset carry it), then
+    inference.render_image(keys=('depth', 'acc')).  Where acc >= acc_min the pixel is a surface at depth / acc
+    (`normalize`: the expected distance of the mass the ray did meet) or at depth; where acc <= acc_free the ray hit
+    nothing: +inf; in between nothing is known: 0.  The two thresholds are the caller's to set: they decide what counts
+    as seen, and no value suits every scene.  ndc=True (a model trained on NDC rays) is refused."""
+    from . import inference
+    what = "depth_images_from_field"
+    _refuse_ndc(ndc, what)
+    cameras = _check_cameras(cameras, what)
+    w, h = ops.mesh_render.check_image_wh(image_wh, what)
+    acc_min, acc_free = float(acc_min), float(acc_free)
+    if not 0.0 <= acc_free < acc_min <= 1.0:
+        raise ValueError(f"{what}: the thresholds need 0 <= acc_free < acc_min <= 1, got acc_free {acc_free}, acc_min {acc_min}")
+    device = next(model.parameters()).device
+    out = torch.empty((cameras.shape[0], h, w), dtype=torch.float32, device=device)
+    for n, cam in enumerate(cameras.to(device)):
+        rays = camera_rays(cam, w, h, near, far)
+        rays = torch.cat([rays, torch.full((rays.shape[0], 1), float(int(frame_id)), device=device)], dim=1)
+        field = inference.render_image(model, rays, chunk=chunk, level=level, keys=('depth', 'acc'))
+        depth, acc = field['depth'].reshape(h, w).float(), field['acc'].reshape(h, w).float()
+        surface = depth / acc if normalize else depth
+        out[n] = torch.where(acc >= acc_min, surface,
+                             torch.where(acc <= acc_free, torch.full_like(depth, float('inf')), torch.zeros_like(depth)))
+    return out
+
+
+@torch.no_grad()
+def tsdf_isosurface(volume: Dict[str, torch.Tensor], bounds, observed_only: bool = True) -> Dict[str, torch.Tensor]:
+    """The mesh dict of the zero level set of a fuse_depth volume: extract_isosurface(g, 0.0, bounds) of the lattice
+    g = -tsdf where weight > 0 and +1 elsewhere.  Space no view ever saw counts as solid, so the inside of an object
+    stays filled, and the normals point out of the surface, towards the cameras.  That puts faces between seen free
+    space and unseen space too (the walls of the viewing frusta); observed_only=True drops every face whose centroid
+    lies in a lattice cell with a never-observed corner (ops.mesh.tsdf_face_keep), compacts the mesh as filter_mesh
+    does ('vertices' and 'normals' gathered, faces re-indexed) and adds 'vertex_index' (V',) int32: the id each kept
+    vertex had before.  The surface then has holes where nothing was observed.  One more host read (both counts)."""
+    what = "tsdf_isosurface"
+    if not isinstance(volume, dict) or 'tsdf' not in volume or 'weight' not in volume:
+        raise ValueError(f"{what}: volume must be a dict with 'tsdf' and 'weight', as fuse_depth returns it")
+    tsdf = ops.mesh.check_volume(volume['tsdf'], what, "volume['tsdf']")
+    weight = ops.mesh.check_volume(volume['weight'], what, "volume['weight']", tsdf.shape)
+    _, bounds = ops.mesh.check_lattice(tsdf.shape, bounds, what)
+    if not (tsdf.is_cuda and weight.is_cuda):
+        raise ValueError(f"{what}: the volume must live on the GPU (there is no CPU fallback)")
+    mesh = ops.mesh.extract_isosurface(torch.where(weight > 0, -tsdf, torch.ones_like(tsdf)), 0.0, bounds)
+    if not observed_only:
+        return mesh
+    faces, v = mesh['faces'], mesh['vertices'].shape[0]
+    dev = faces.device
+    if v == 0 or faces.shape[0] == 0:
+        return {'vertices': mesh['vertices'][:0], 'normals': mesh['normals'][:0], 'faces': faces[:0],
+                'vertex_index': torch.zeros(0, dtype=torch.int32, device=dev)}
+    fkeep, vkeep = ops.mesh.tsdf_face_keep(mesh['vertices'], faces, weight, bounds)
+    vertex_index, faces_out = ops.mesh.compact_kept(faces, vkeep, fkeep)
+    return {'vertices': ops.mesh.gather_rows(mesh['vertices'], vertex_index),
+            'normals': ops.mesh.gather_rows(mesh['normals'], vertex_index), 'faces': faces_out,
+            'vertex_index': vertex_index}
+
+
+def extract_mesh_fused(model, bounds, resolution, frame_id: int, cameras, image_wh, near: float, far: float,
+                       trunc: Optional[float] = None, min_faces: Optional[int] = None, keep_largest: Optional[int] = None,
+                       simplify=None, colors=None, *, ndc: bool = False, **kw) -> Dict[str, torch.Tensor]:
+    """The surface of frame `frame_id` where the field renders it, with no iso level to guess:
+    tsdf_isosurface(fuse_depth(depth_images_from_field(model, cameras, image_wh, frame_id, near, far), cameras, bounds,
+    resolution, trunc), bounds), then extract_mesh's tail: filter_mesh(min_faces, keep_largest), simplify_mesh by
+    `simplify` lattice spacings, 'colors' = vertex_colors(view=colors).  Of **kw, acc_min / acc_free / normalize go to
+    depth_images_from_field, level / chunk to it and to vertex_colors, render_opts to vertex_colors.  ndc=True is
+    refused."""
+    _refuse_ndc(ndc, "extract_mesh_fused")
+    factor = None if simplify is None else _simplify_factor(simplify)
+    field_kw = {k: kw[k] for k in ('acc_min', 'acc_free', 'normalize', 'level', 'chunk') if k in kw}
+    color_kw = {k: kw[k] for k in ('level', 'chunk', 'render_opts') if k in kw}
+    unknown = set(kw) - set(field_kw) - set(color_kw)
+    if unknown:
+        raise TypeError(f"extract_mesh_fused: unexpected keyword arguments {sorted(unknown)}")
+    depths = depth_images_from_field(model, cameras, image_wh, frame_id, near, far, **field_kw)
+    mesh = tsdf_isosurface(fuse_depth(depths, cameras, bounds, resolution, trunc), bounds)
+    return _finish_mesh(mesh, model, bounds, resolution, frame_id, factor, colors, min_faces, keep_largest, color_kw)
 
 
 # ---- looking at a mesh: ray casting through the cameras the field is rendered with (csrc/hn_mesh_render.hip) ------------

@@ -1,7 +1,8 @@
 """The host halves of the kernels outside the training step, one module per kernel source file:
 
     metrics      csrc/hn_metrics.hip, csrc/hn_msssim.hip    SSIM (differentiable) and multi-scale SSIM
-    mesh         csrc/hn_geometry.hip                        lattice points, isosurface, components, compaction
+    mesh         csrc/hn_geometry.hip, csrc/hn_fusion.hip    lattice points, isosurface, components, compaction; depth
+                                                             fusion into a TSDF volume, its observed faces
     simplify     csrc/hn_simplify.hip                        vertex clustering
     mesh_render  csrc/hn_mesh_render.hip                     projection, binning, ray casting, shading
     data         csrc/hn_data.hip                            ray generation, batch gathers, blend, Pillow-exact resize

@@ -1,17 +1,21 @@
 """Geometry out of a trained field (csrc/hn_geometry.hip): lattice points, the isosurface by marching tetrahedra,
-connected components of a mesh and its compaction, view directions of its vertices."""
+connected components of a mesh and its compaction, view directions of its vertices; and depth fusion on the same lattice
+(csrc/hn_fusion.hip): depth images into a TSDF volume, the faces of its mesh that lie in observed cells."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Optional
 
 import torch
 
 from .. import _lib as L
-from .checks import INT32_MAX, check_faces
+from .checks import INT32_MAX, check_faces, check_points
+from .data import NERFIES_CAM_FLOATS
 
 __all__ = ["ISO_BLOCK", "check_lattice", "grid_points", "density_activate", "extract_isosurface", "mesh_components",
-           "component_sizes", "gather_rows", "compact_mesh", "vertex_viewdirs"]
+           "component_sizes", "gather_rows", "compact_mesh", "compact_kept", "vertex_viewdirs", "check_volume", "tsdf_integrate",
+           "tsdf_face_keep"]
 
 ISO_BLOCK = L.HN_ISO_BLOCK    # lattice points (cells) per workgroup of the hn_iso_* passes
 
@@ -238,6 +242,16 @@ def compact_mesh(faces: torch.Tensor, labels: torch.Tensor, keep_comp: torch.Ten
             fkeep.zero_()
         L.launch("hn_mesh_keep", L.ptr(labels.contiguous()), L.ptr(faces) if n_faces else None, L.ptr(keep_comp),
                  v, n_faces, L.ptr(vkeep), L.ptr(fkeep), stream)
+    return compact_kept(faces, vkeep, fkeep)
+
+
+@torch.no_grad()
+def compact_kept(faces: torch.Tensor, vkeep: torch.Tensor, fkeep: torch.Tensor):
+    """(vertex_index (V',) int32, faces (F', 3) int32) of faces (F, 3) int32 and the 0 / 1 int32 marks vkeep (V >= 1,) and
+    fkeep (max(F, 1),): the kept vertices and faces in their old order, the faces re-indexed (two torch.cumsum scans,
+    hn_mesh_compact).  Every vertex of a kept face must be kept.  One host read (both counts at once) sizes the outputs."""
+    dev, v, n_faces = faces.device, vkeep.shape[0], faces.shape[0]
+    with torch.cuda.device(dev):
         vscan = torch.cumsum(vkeep, 0, dtype=torch.int32)
         fscan = torch.cumsum(fkeep, 0, dtype=torch.int32)
         n_v, n_f = torch.stack([vscan[-1], fscan[-1]]).tolist()
@@ -245,7 +259,7 @@ def compact_mesh(faces: torch.Tensor, labels: torch.Tensor, keep_comp: torch.Ten
         faces_out = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
         if n_v:
             L.launch("hn_mesh_compact", L.ptr(faces) if n_faces else None, L.ptr(vscan), L.ptr(fscan), v, n_faces,
-                     n_v, n_f, L.ptr(vertex_index), L.ptr(faces_out) if n_f else None, stream)
+                     n_v, n_f, L.ptr(vertex_index), L.ptr(faces_out) if n_f else None, L.stream_handle())
     return vertex_index, faces_out
 
 
@@ -271,3 +285,92 @@ def vertex_viewdirs(vertices: torch.Tensor, normals: Optional[torch.Tensor], sta
                  L.ptr(ref) if camera is None else None, v, start, count, cam, L.ptr(out),
                  L.stream_handle())
     return out
+
+
+# ---- depth fusion (csrc/hn_fusion.hip) -----------------------------------------------------------------------------------
+def check_volume(t, what: str, name: str, shape=None) -> torch.Tensor:
+    """A (nx, ny, nz) float32 C-contiguous volume as the hn_tsdf entry points take it (of `shape` when given), or
+    ValueError.  The device is the caller's to check, after its other arguments."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError(f"{what}: {name} must be a (nx, ny, nz) tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, the lattice {tuple(shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be C-contiguous")
+    return t.detach()
+
+
+@torch.no_grad()
+def tsdf_integrate(tsdf: torch.Tensor, weight: torch.Tensor, bounds, cams: torch.Tensor, depths: torch.Tensor,
+                   trunc: float) -> None:
+    """Folds depths (N, H, W) fp32 seen through the camera records cams (N, 24) fp32 into the volumes tsdf and weight
+    ((nx, ny, nz) fp32, C-contiguous, zeroed before the first batch), IN PLACE (hn_tsdf_integrate; DESIGN.md 3.12 holds the
+    definition): per lattice point and view, in the order of the views, the point is projected by the forward camera
+    model, the depth D of the pixel it falls into is read (nearest pixel; +inf = the ray hit nothing, not > 0 = nothing
+    known), s = D - |x - camera|, and unless s < -trunc, tsdf = (weight * tsdf + min(1, s / trunc)) / (weight + 1) and
+    weight += 1.  Depths are distances along the unit ray from the camera position.  Everything on the GPU of the volumes;
+    no host synchronisation; two runs, and the same views in several batches, give the same bits."""
+    what = "tsdf_integrate"
+    tsdf = check_volume(tsdf, what, "tsdf")
+    weight = check_volume(weight, what, "weight", tsdf.shape)
+    (nx, ny, nz), bounds = check_lattice(tsdf.shape, bounds, what)
+    if not isinstance(cams, torch.Tensor) or cams.dim() != 2 or cams.shape[1] != NERFIES_CAM_FLOATS \
+            or cams.dtype != torch.float32:
+        raise ValueError(f"{what}: cams must be a (N, {NERFIES_CAM_FLOATS}) float32 tensor of camera records")
+    n = cams.shape[0]
+    if n < 1:
+        raise ValueError(f"{what}: cams holds no camera")
+    if not isinstance(depths, torch.Tensor) or depths.dim() != 3 or depths.dtype != torch.float32:
+        raise ValueError(f"{what}: depths must be a (N, H, W) float32 tensor")
+    if depths.shape[0] != n:
+        raise ValueError(f"{what}: depths holds {depths.shape[0]} images for {n} cameras")
+    h, w = int(depths.shape[1]), int(depths.shape[2])
+    if not (1 <= w <= L.HN_MESH_MAX_SIDE and 1 <= h <= L.HN_MESH_MAX_SIDE):
+        raise ValueError(f"{what}: the image sides of depths must be 1 .. {L.HN_MESH_MAX_SIDE}, got {w} x {h}")
+    try:
+        trunc = float(trunc)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: trunc must be a number, got {trunc!r}") from None
+    if not (math.isfinite(trunc) and trunc > 0.0):
+        raise ValueError(f"{what}: trunc must be positive and finite, got {trunc}")
+    if not (tsdf.is_cuda and weight.is_cuda and cams.is_cuda and depths.is_cuda):
+        raise ValueError(f"{what}: tsdf, weight, cams and depths must live on the GPU (there is no CPU fallback)")
+    if cams.device != tsdf.device or depths.device != tsdf.device or weight.device != tsdf.device:
+        raise ValueError(f"{what}: tsdf, weight, cams and depths must live on one device")
+    L.load()
+    cams, depths = cams.detach().contiguous(), depths.detach().contiguous()
+    with torch.cuda.device(tsdf.device):
+        L.launch("hn_tsdf_integrate", L.ptr(tsdf), L.ptr(weight), nx, ny, nz, (C.c_float * 6)(*bounds), L.ptr(cams),
+                 L.ptr(depths), n, h, w, trunc, L.stream_handle())
+
+
+@torch.no_grad()
+def tsdf_face_keep(vertices: torch.Tensor, faces: torch.Tensor, weight: torch.Tensor, bounds):
+    """(fkeep (F,) int32, vkeep (V,) int32), 0 / 1: a face of a mesh extracted on the lattice of `weight` ((nx, ny, nz)
+    fp32 over `bounds`) is kept iff all eight lattice points of the cell that holds its centroid ((a + b) + c) / 3 have
+    weight > 0, a vertex iff a kept face references it (hn_tsdf_face_keep).  A face with a vertex id outside [0, V) is
+    dropped.  No host synchronisation; the scans and hn_mesh_compact that follow are the caller's."""
+    what = "tsdf_face_keep"
+    vertices = check_points(vertices, what, "vertices")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{what}: faces must be a (F, 3) int32 tensor")
+    weight = check_volume(weight, what, "weight")
+    (nx, ny, nz), bounds = check_lattice(weight.shape, bounds, what)
+    if not (vertices.is_cuda and faces.is_cuda and weight.is_cuda):
+        raise ValueError(f"{what}: vertices, faces and weight must live on the GPU (there is no CPU fallback)")
+    faces, v = check_faces(faces, vertices.shape[0], what)
+    if vertices.device != faces.device or weight.device != faces.device:
+        raise ValueError(f"{what}: vertices, faces and weight must live on one device")
+    dev, n_faces = faces.device, faces.shape[0]
+    fkeep = torch.empty(n_faces, dtype=torch.int32, device=dev)
+    vkeep = torch.zeros(v, dtype=torch.int32, device=dev)
+    if n_faces and v:
+        L.load()
+        with torch.cuda.device(dev):
+            L.launch("hn_tsdf_face_keep", L.ptr(faces), n_faces, L.ptr(vertices), v, L.ptr(weight), nx, ny, nz,
+                     (C.c_float * 6)(*bounds), L.ptr(fkeep), L.ptr(vkeep), L.stream_handle())
+    else:
+        fkeep.zero_()
+    return fkeep, vkeep

@@ -801,6 +801,36 @@ int hn_mesh_shade(const float* vertices_dev, long long n_vertices, const int32_t
                   const float* base_color_host, const float* background_host, float* normal_out_dev, float* rgb_out_dev,
                   uint8_t* rgb8_out_dev, hnStream_t stream);
 
+/* Depth fusion (csrc/hn_fusion.hip; DESIGN.md 3.12 holds the definition, tests/tsdf_restated.py restates it in NumPy float32).
+ * The lattice is hn_grid_points' (nx, ny, nz over bounds_host, six HOST floats); cams_dev holds 24-float camera records of
+ * hn_generate_rays_nerfies, on the device.
+ *   hn_tsdf_integrate  folds depths (n_views, H, W) fp32 seen through cams (n_views, 24) into tsdf and weight, both (nx, ny, nz)
+ *                fp32, z fastest, zeroed by the caller before the first batch (later batches continue them).  A depth is the
+ *                distance along the unit ray from the camera position; +inf: the ray hit nothing (everything along it is
+ *                free); a value that is not > 0 (zero, negative, NaN): nothing is known.  One work-item per lattice point x
+ *                (the position hn_grid_points gives it, bit for bit) walks the views in order 0 .. n_views - 1; every
+ *                operation is fp32, rounded on its own, in this order:
+ *                  q = x - cam[9:12];  (u, v, flag) = the forward camera model of hn_mesh_project;  flag != 0 skips the view
+ *                  skip unless 0 <= u < W and 0 <= v < H, compared as floats;  col = (int)floorf(u), row = (int)floorf(v)
+ *                  D = depths[view][row][col];  skip unless D > 0
+ *                  r = sqrt((qx*qx + qy*qy) + qz*qz);  s = D - r;  skip if s < -trunc
+ *                  t = fminf(1, s / trunc);  tsdf = (weight * tsdf + t) / (weight + 1);  weight = weight + 1
+ *                No atomics, no reductions: two runs, and the same views in several batches, give the same bits.
+ *   hn_tsdf_face_keep  for a mesh extracted on that lattice (faces (F, 3) int32, vertices (V, 3) fp32) and the weight volume:
+ *                fkeep[f] (int32) = 1 iff all eight lattice points of the cell that holds the face's centroid have weight > 0,
+ *                centroid = ((a + b) + c) / 3 per axis, cell index per axis = min(n - 2, max(0, (int)floorf((centroid - lo) /
+ *                step))) with step = (hi - lo) / (n - 1) as hn_grid_points takes it; a face with an id outside [0, V): 0.
+ *                vkeep[v] (int32, V entries zeroed by the caller) = 1 iff a kept face references v (plain stores of the
+ *                same value, no atomics).  Both are what hn_mesh_compact takes after two inclusive scans.
+ * Status, before any launch: -2 for a size out of range (a lattice hn_grid_points refuses, n_views < 1, an image side outside
+ * 1 .. 65535, trunc not positive and finite, F or V <= 0 or above 2^31 - 1, bounds_host NULL), -3 for a NULL device pointer. */
+int hn_tsdf_integrate(float* tsdf_dev, float* weight_dev, int nx, int ny, int nz, const float* bounds_host,
+                      const float* cams_dev, const float* depths_dev, int n_views, int H, int W, float trunc,
+                      hnStream_t stream);
+int hn_tsdf_face_keep(const int32_t* faces_dev, long long n_faces, const float* vertices_dev, long long n_vertices,
+                      const float* weight_dev, int nx, int ny, int nz, const float* bounds_host, int32_t* fkeep_dev,
+                      int32_t* vkeep_dev, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *
