@@ -43,6 +43,16 @@ signed distance volume (`fuse_depth`, csrc/hn_fusion.hip) and me
 
     cams = orbit_cameras((0, 0, 0), 3.0, 60, 20.0, focal=400.0, image_wh=(W, H))
     mesh = extract_mesh_fused(model, bounds, 256, 12, cams, (W, H), near, far, keep_largest=1)
+
+Comparing meshes: `mesh_distance` samples both surfaces by area (`sample_surface`, reproducible bit for bit), finds every
+sample's exact nearest point on the other mesh (`point_mesh_distance`, csrc/hn_mesh_distance.hip, DESIGN.md 3.13: a grid
+of cells prunes the search, the result is that of testing every face) and reports Chamfer, Hausdorff and precision /
+recall / F-score at thresholds; `distance_colors` turns per-vertex distances into colours for write_ply.
+
+    small = simplify_mesh(mesh, cell=0.02)
+    mesh_distance(mesh, small, n_samples=1_000_000, thresholds=[0.01])    # what the simplification cost
+    d = point_mesh_distance(small['vertices'], mesh)['distance']
+    write_ply("error.ply", small['vertices'], small['faces'], colors=distance_colors(d, vmax=0.02))
 """
 from __future__ import annotations
 
@@ -656,6 +666,142 @@ def mesh_depth_error(model, mesh: Dict[str, torch.Tensor], rays: torch.Tensor, c
     field = inference.render_image(model, rays, chunk=chunk, level=level, keys=(depth_key, 'acc'))
     seen = render_mesh(mesh, rays, camera, (w, h), shading='none')
     return depth_agreement(seen['depth'], seen['face'], field[depth_key], field['acc'], acc_min=acc_min)
+
+
+# ---- distance between meshes (csrc/hn_mesh_distance.hip) ----------------------------------------------------
+def _mesh_arrays(mesh, what: str):
+    """(vertices, faces) of a mesh dict as the distance ops take them, or ValueError."""
+    if not isinstance(mesh, dict) or 'vertices' not in mesh or 'faces' not in mesh:
+        raise ValueError(f"{what}: a mesh is a dict with 'vertices' (V, 3) float32 and 'faces' (F, 3) int32")
+    return (ops.checks.check_points(mesh['vertices'], what, "vertices"), ops.checks.check_mesh_faces(mesh['faces'], what))
+
+
+@torch.no_grad()
+def sample_surface(mesh: Dict[str, torch.Tensor], n: int, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """n independent points of the mesh's surface, uniform by area: {'points': (n, 3) fp32, 'face': (n,) int32, 'bary':
+    (n, 3) fp32} with points = (b0*A + b1*B) + b2*C of the face's corners.  Sample k is a pure function of (seed, k) and
+    the mesh — splitmix64 hashes, an integer table of face weights (each face's area over the largest, in 2**-24 steps:
+    a face below 2**-24 of the largest, or without a finite area, is never drawn) — so every run and every machine gives
+    the same bits (tests/mesh_distance_restated.py restates them in NumPy).  One host read.  ValueError: n < 1, a mesh
+    without faces or without area, a vertex id outside [0, V)."""
+    what = "sample_surface"
+    vertices, faces = _mesh_arrays(mesh, what)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= ops.checks.INT32_MAX:
+        raise ValueError(f"{what}: n must be an int in 1 .. 2**31 - 1, got {n!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"{what}: seed must be an int, got {seed!r}")
+    if faces.shape[0] == 0:
+        raise ValueError(f"{what}: the mesh has no faces")
+    cdf = ops.mesh.surface_cdf(vertices, faces)
+    return ops.mesh.sample_faces(vertices, faces, cdf, int(n), int(seed))
+
+
+@torch.no_grad()
+def build_distance_grid(mesh: Dict[str, torch.Tensor], grid_resolution=None) -> Dict:
+    """The search structure of point_mesh_distance for `mesh`, which takes it in place of the mesh: build once, query several
+    point sets.  grid_resolution: cells per axis, an int or three in 1 .. 256; 1 = one cell holding every face (brute
+    force); None = round(sqrt(F) / 2) cells along the longest side of the mesh's box and cubic cells on the others
+    (ops.mesh.default_grid_resolution; DESIGN.md 3.13 has the measurements behind it).  Two host reads."""
+    what = "build_distance_grid"
+    vertices, faces = _mesh_arrays(mesh, what)
+    if grid_resolution is not None:
+        ops.mesh.check_grid_resolution(grid_resolution, what)
+    return ops.mesh.distance_grid(vertices, faces, grid_resolution)
+
+
+@torch.no_grad()
+def point_mesh_distance(points: torch.Tensor, mesh, max_distance: Optional[float] = None, grid_resolution=None,
+                        sort_queries: bool = True) -> Dict[str, torch.Tensor]:
+    """For every point of points (N, 3) fp32 the nearest point of the triangle mesh: {'distance': (N,) fp32, 'face': (N,)
+    int32, 'closest': (N, 3) fp32} — the exact closest point of each candidate triangle by Voronoi regions, fp32 with every
+    operation rounded on its own, the minimum over (squared distance, face id): ties go to the smallest face id, and the
+    result is bit for bit that of testing every face, whatever the grid.  mesh: a mesh dict, or
+    build_distance_grid's result (grid_resolution is then ignored).  A point that is not finite gives NaN, -1, NaN; a mesh
+    without faces +inf, -1, NaN; with max_distance (>= 0) so does a point farther than that from the mesh, and the search
+    stops at that radius.  sort_queries=False skips sorting the queries by cell (same bits, slower on large sets).
+    Cost: a query near the surface visits a few cells; one far outside the mesh's box visits most of the grid."""
+    what = "point_mesh_distance"
+    points = ops.checks.check_points(points, what, "points")
+    ops.mesh.check_max_distance(max_distance, what)
+    if isinstance(mesh, dict) and 'cell_begin' in mesh:
+        grid = mesh
+    else:
+        grid = build_distance_grid(mesh, grid_resolution)
+    return ops.mesh.grid_query(points, grid, max_distance, bool(sort_queries))
+
+
+def _distance_stats(d: torch.Tensor, taus) -> torch.Tensor:
+    """[mean, mean of squares, max, share within tau ...] of fp32 distances, as float64 on their device."""
+    d64 = d.double()
+    parts = [d64.mean(), (d64 * d64).mean(), d64.max()] + [(d64 <= t).double().mean() for t in taus]
+    return torch.stack(parts)
+
+
+@torch.no_grad()
+def mesh_distance(a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], n_samples: int = 100_000, seed: int = 0,
+                  thresholds=None, with_vertices: bool = False, return_distances: bool = False) -> Dict:
+    """Sampled distances between two meshes: n_samples points of a (sample_surface, `seed`) to their nearest points on b, and
+    n_samples of b (`seed + 1`) to a.  with_vertices appends every vertex of the sampled mesh to its samples, so that
+    corners count for the maximum.  {'a_to_b': {'mean', 'rms', 'max'}, 'b_to_a': likewise, 'chamfer': (mean_ab + mean_ba)
+    / 2, 'chamfer_l2': (mean(d_ab^2) + mean(d_ba^2)) / 2, 'hausdorff': max(max_ab, max_ba), 'n': (samples of a, samples of
+    b)}, and with thresholds (a number or several) 'thresholds': {tau: {'precision': the share of a's samples within tau of
+    b, 'recall': the share of b's within tau of a, 'fscore': 2PR / (P + R), 0 when P + R == 0}}.  Python floats: the
+    reductions are torch's, float64 over the fp32 distances, read in one host read at the end.  return_distances adds
+    'distances_ab' / 'distances_ba', the fp32 tensors reduced.  ValueError: a mesh without faces, n_samples < 1."""
+    what = "mesh_distance"
+    meshes = [_mesh_arrays(m, what) for m in (a, b)]
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or int(n_samples) < 1:
+        raise ValueError(f"{what}: n_samples must be an int >= 1, got {n_samples!r}")
+    if thresholds is None:
+        taus = []
+    else:
+        try:
+            taus = [float(t) for t in (thresholds if hasattr(thresholds, '__iter__') else [thresholds])]
+        except (TypeError, ValueError):
+            taus = [float("nan")]
+        if not all(t >= 0.0 for t in taus):
+            raise ValueError(f"{what}: thresholds must be numbers >= 0, got {thresholds!r}")
+    for vertices, faces in meshes:
+        if faces.shape[0] == 0 or vertices.shape[0] == 0:
+            raise ValueError(f"{what}: a mesh without faces has no distance")
+    dists = []
+    for k, (src, dst) in enumerate(((a, b), (b, a))):
+        pts = sample_surface(src, int(n_samples), int(seed) + k)['points']
+        if with_vertices:
+            pts = torch.cat([pts, meshes[k][0]], 0)
+        dists.append(point_mesh_distance(pts, dst)['distance'])
+    stats = torch.stack([_distance_stats(d, taus) for d in dists]).tolist()       # the one host read
+    (mean_ab, sq_ab, max_ab), (mean_ba, sq_ba, max_ba) = stats[0][:3], stats[1][:3]
+    out = {'a_to_b': {'mean': mean_ab, 'rms': float(np.sqrt(sq_ab)), 'max': max_ab},
+           'b_to_a': {'mean': mean_ba, 'rms': float(np.sqrt(sq_ba)), 'max': max_ba},
+           'chamfer': (mean_ab + mean_ba) / 2, 'chamfer_l2': (sq_ab + sq_ba) / 2, 'hausdorff': max(max_ab, max_ba),
+           'n': (dists[0].shape[0], dists[1].shape[0])}
+    if thresholds is not None:
+        out['thresholds'] = {}
+        for j, tau in enumerate(taus):
+            p, r = stats[0][3 + j], stats[1][3 + j]
+            out['thresholds'][tau] = {'precision': p, 'recall': r, 'fscore': 2 * p * r / (p + r) if p + r > 0 else 0.0}
+    if return_distances:
+        out['distances_ab'], out['distances_ba'] = dists
+    return out
+
+
+@torch.no_grad()
+def distance_colors(distance: torch.Tensor, vmax: float) -> torch.Tensor:
+    """(N, 3) uint8 RGB of distances (N,): inference.jet_lut() (its blue-first rows turned to red-first) at index
+    (int)(255 * min(d / vmax, 1)) — 0 is the table's first entry (dark blue), vmax and above its last (dark red), and so are NaN
+    and inf.  For write_ply(path, v, f, colors=distance_colors(point_mesh_distance(v, other)['distance'], vmax)): where
+    two meshes differ.  Plain torch indexing, on the device of `distance`."""
+    from . import inference
+    if not isinstance(distance, torch.Tensor) or distance.dim() != 1 or not distance.dtype.is_floating_point:
+        raise ValueError("distance_colors: distance must be a (N,) floating point tensor")
+    vmax = float(vmax)
+    if not (np.isfinite(vmax) and vmax > 0.0):
+        raise ValueError(f"distance_colors: vmax must be positive and finite, got {vmax}")
+    x = distance.detach().float() / vmax
+    x = torch.where(x <= 1.0, x.clamp(min=0.0), torch.ones_like(x))          # NaN, inf and above vmax -> 1
+    index = (x * 255.0).to(torch.int64)
+    return inference.jet_lut().flip(1).to(distance.device)[index]
 
 
 def _host(a, dtype):

@@ -3,6 +3,7 @@
     metrics      csrc/hn_metrics.hip, csrc/hn_msssim.hip    SSIM (differentiable) and multi-scale SSIM
     mesh         csrc/hn_geometry.hip, csrc/hn_fusion.hip    lattice points, isosurface, components, compaction; depth
                                                              fusion into a TSDF volume, its observed faces
+                 csrc/hn_mesh_distance.hip                   surface samples, the distance grid, nearest points of a mesh
     simplify     csrc/hn_simplify.hip                        vertex clustering
     mesh_render  csrc/hn_mesh_render.hip                     projection, binning, ray casting, shading
     data         csrc/hn_data.hip                            ray generation, batch gathers, blend, Pillow-exact resize

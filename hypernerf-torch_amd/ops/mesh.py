@@ -1,21 +1,27 @@
 """Geometry out of a trained field (csrc/hn_geometry.hip): lattice points, the isosurface by marching tetrahedra,
 connected components of a mesh and its compaction, view directions of its vertices; and depth fusion on the same lattice
-(csrc/hn_fusion.hip): depth images into a TSDF volume, the faces of its mesh that lie in observed cells."""
+(csrc/hn_fusion.hip): depth images into a TSDF volume, the faces of its mesh that lie in observed cells; and the distance
+between meshes (csrc/hn_mesh_distance.hip): area-weighted surface samples, a grid of cells over a mesh, the nearest point
+of the mesh from query points."""
 from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
 from .. import _lib as L
-from .checks import INT32_MAX, check_faces, check_points
+from .checks import INT32_MAX, check_faces, check_mesh_faces, check_points
 from .data import NERFIES_CAM_FLOATS
+from .simplify import vertex_extent
 
 __all__ = ["ISO_BLOCK", "check_lattice", "grid_points", "density_activate", "extract_isosurface", "mesh_components",
            "component_sizes", "gather_rows", "compact_mesh", "compact_kept", "vertex_viewdirs", "check_volume", "tsdf_integrate",
-           "tsdf_face_keep"]
+           "tsdf_face_keep", "MD_MAX_RES", "MD_TRI_FLOATS", "MD_WEIGHT_BITS", "GRID_DENSITY", "check_grid_resolution", "check_max_distance",
+           "default_grid_resolution", "surface_cdf", "sample_faces", "distance_grid", "grid_query"]
 
 ISO_BLOCK = L.HN_ISO_BLOCK    # lattice points (cells) per workgroup of the hn_iso_* passes
 
@@ -374,3 +380,246 @@ def tsdf_face_keep(vertices: torch.Tensor, faces: torch.Tensor, weight: torch.Te
     else:
         fkeep.zero_()
     return fkeep, vkeep
+
+
+# ---- mesh-to-mesh distance (csrc/hn_mesh_distance.hip) ---------------------------------------------------------------------
+# mirrors of csrc/hn_mesh_distance.hip's limits (no macros in the header: its set of constants is that of ABI 340)
+MD_MAX_RES = 256          # grid cells per axis of the distance grid
+MD_TRI_FLOATS = 12        # floats per packed triangle
+MD_WEIGHT_BITS = 24       # the largest face has the integer weight 2**24
+GRID_DENSITY = 0.5    # default_grid_resolution: cells along the longest axis per sqrt(faces) (DESIGN.md 3.13 has the numbers)
+
+
+def check_grid_resolution(resolution, what: str):
+    """(rx, ry, rz) from an int or three ints, each 1 .. MD_MAX_RES, or ValueError."""
+    if isinstance(resolution, numbers.Integral) and not isinstance(resolution, bool):
+        res = (int(resolution),) * 3
+    else:
+        try:
+            vals = list(resolution)
+        except TypeError:
+            vals = []
+        res = tuple(int(r) for r in vals) if all(isinstance(r, numbers.Integral) and not isinstance(r, bool) for r in vals) \
+            else ()
+    if len(res) != 3 or not all(1 <= r <= MD_MAX_RES for r in res):
+        raise ValueError(f"{what}: grid_resolution must be an int or three ints in 1 .. {MD_MAX_RES}, got {resolution!r}")
+    return res
+
+
+def check_max_distance(max_distance, what: str) -> float:
+    """max_distance as the float hn_md_query takes (-1.0 for None: no limit), or ValueError when negative or NaN."""
+    if max_distance is None:
+        return -1.0
+    try:
+        d = float(max_distance)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if not d >= 0.0:
+        raise ValueError(f"{what}: max_distance must be a number >= 0 or None, got {max_distance!r}")
+    return d
+
+
+def default_grid_resolution(n_faces: int, lo, hi):
+    """(rx, ry, rz): round(GRID_DENSITY * sqrt(F)) cells along the longest side of the box lo .. hi, the other axes in
+    proportion to their sides (cells about cubic), each clamped to 1 .. MD_MAX_RES; a side of zero length gets 1."""
+    ext = [max(float(h) - float(l), 0.0) for l, h in zip(lo, hi)]
+    longest = max(ext)
+    along = GRID_DENSITY * math.sqrt(max(int(n_faces), 1))
+    if not longest > 0.0:
+        return (1, 1, 1)
+    return tuple(min(MD_MAX_RES, max(1, int(round(along * e / longest)))) for e in ext)
+
+
+def _check_mesh(vertices, faces, what: str):
+    vertices = check_points(vertices, what, "vertices")
+    faces = check_mesh_faces(faces, what)
+    if vertices.shape[0] > INT32_MAX or faces.shape[0] > INT32_MAX:
+        raise ValueError(f"{what}: {vertices.shape[0]} vertices / {faces.shape[0]} faces exceed 2**31 - 1 = {INT32_MAX}")
+    return vertices, faces
+
+
+@torch.no_grad()
+def surface_cdf(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """(F,) int64: the inclusive scan of the integer face weights w_f = (int64)((a2_f / max a2) * 2**24), a2_f = twice the
+    area of face f in fp32 (hn_md_face_weights; 0 where not finite) — what sample_faces draws its faces from.  The maximum,
+    the quotient and the scan are torch's: an fp32 maximum and integer sums are exact, the quotient one correctly rounded
+    division.  One host read (the total weight and the error flag).  ValueError: a face holds a vertex id outside
+    [0, V); the total weight is 0 (no face, or none with a positive finite area)."""
+    what = "surface_cdf"
+    vertices, faces = _check_mesh(vertices, faces, what)
+    L.require_gpu(vertices, faces)
+    v, n_faces, dev = vertices.shape[0], faces.shape[0], faces.device
+    if n_faces == 0:
+        raise ValueError(f"{what}: the mesh has no faces")
+    if v == 0:
+        raise ValueError(f"{what}: faces hold a vertex id outside [0, 0)")
+    L.load()
+    a2 = torch.empty(n_faces, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.launch("hn_md_face_weights", L.ptr(vertices), v, L.ptr(faces), n_faces, L.ptr(a2), L.ptr(err), L.stream_handle())
+    m = a2.amax()      # stays on the device: a tensor divisor is divided by, a host scalar would be multiplied by its inverse
+    w = torch.where(m > 0, (a2 / m) * float(1 << MD_WEIGHT_BITS), torch.zeros_like(a2)).to(torch.int64)
+    cdf = torch.cumsum(w, 0)
+    total, bad = torch.stack([cdf[-1], err[0].to(torch.int64)]).tolist()
+    if bad:
+        raise ValueError(f"{what}: faces hold a vertex id outside [0, {v})")
+    if total == 0:
+        raise ValueError(f"{what}: no face has a positive finite area")
+    return cdf
+
+
+@torch.no_grad()
+def sample_faces(vertices: torch.Tensor, faces: torch.Tensor, cdf: torch.Tensor, n: int, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """{'points': (n, 3) fp32, 'face': (n,) int32, 'bary': (n, 3) fp32}: n independent area-weighted points of the surface
+    (hn_md_sample; cdf: surface_cdf's).  Sample k hashes (seed, k) with splitmix64 into a face (through the integer cdf)
+    and two 24-bit uniforms: any machine gives the same bits, and tests/mesh_distance_restated.py restates them."""
+    what = "sample_faces"
+    vertices, faces = _check_mesh(vertices, faces, what)
+    n_faces, v = faces.shape[0], vertices.shape[0]
+    n = int(n)
+    if not 1 <= n <= INT32_MAX:
+        raise ValueError(f"{what}: n must be 1 .. 2**31 - 1, got {n}")
+    if not isinstance(cdf, torch.Tensor) or cdf.dtype != torch.int64 or tuple(cdf.shape) != (n_faces,) or n_faces == 0:
+        raise ValueError(f"{what}: cdf must be the ({n_faces},) int64 tensor surface_cdf returned for this mesh")
+    L.require_gpu(vertices, faces, cdf)
+    dev = faces.device
+    out = {'points': torch.empty((n, 3), dtype=torch.float32, device=dev),
+           'face': torch.empty(n, dtype=torch.int32, device=dev),
+           'bary': torch.empty((n, 3), dtype=torch.float32, device=dev)}
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    L.load()
+    with torch.cuda.device(dev):
+        L.launch("hn_md_sample", L.ptr(vertices), v, L.ptr(faces), n_faces, L.ptr(cdf.contiguous()), n,
+                 seed - (1 << 64) if seed >= 1 << 63 else seed, L.ptr(out['points']), L.ptr(out['face']), L.ptr(out['bary']),
+                 L.stream_handle())
+    return out
+
+
+@torch.no_grad()
+def distance_grid(vertices: torch.Tensor, faces: torch.Tensor, resolution=None) -> Dict:
+    """The acceleration grid grid_query searches: rx x ry x rz cells over the box of the vertices (vertex_extent), every
+    face listed in the cells of [idx(its min corner), idx(its max corner)] — hn_md_pack, hn_md_cell_count, torch.cumsum, one
+    host read (the pair count and the error flag), hn_md_cell_fill, a stable torch.sort on the cell and torch.searchsorted,
+    as mesh_bins builds its tiles; face ids ascend within a cell.  resolution: an int or three, None =
+    default_grid_resolution; 1 lists every face in one cell (brute force).  More than 2**31 - 1 pairs halve the
+    resolution and count again.  {'tri': (F, 12) fp32 packed triangles, 'cell_begin': (cells + 1,) int32, 'pair_face':
+    (pairs,) int32, 'lo', 'cell': three host floats each, 'resolution': (rx, ry, rz), 'num_faces': F}.  An empty mesh
+    gives a grid without pairs.  ValueError: a vertex id outside [0, V), vertices that are not finite.  Two host reads."""
+    what = "distance_grid"
+    vertices, faces = _check_mesh(vertices, faces, what)
+    res = None if resolution is None else check_grid_resolution(resolution, what)
+    L.require_gpu(vertices, faces)
+    v, n_faces, dev = vertices.shape[0], faces.shape[0], faces.device
+    if n_faces == 0:
+        return {'tri': torch.zeros((0, MD_TRI_FLOATS), dtype=torch.float32, device=dev),
+                'cell_begin': torch.zeros(2, dtype=torch.int32, device=dev),
+                'pair_face': torch.zeros(0, dtype=torch.int32, device=dev), 'lo': [0.0] * 3, 'cell': [1.0] * 3,
+                'resolution': (1, 1, 1), 'num_faces': 0}
+    if v == 0:
+        raise ValueError(f"{what}: faces hold a vertex id outside [0, 0)")
+    lo, hi = (np.asarray(t, dtype=np.float32) for t in vertex_extent(vertices))      # host read 1
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and np.isfinite(hi - lo).all()):
+        raise ValueError(f"{what}: the vertices are not finite")
+    if res is None:
+        res = default_grid_resolution(n_faces, lo.tolist(), hi.tolist())
+    res = tuple(1 if not h > l else r for r, l, h in zip(res, lo, hi))      # an axis of zero extent has one cell
+    L.load()
+    with torch.cuda.device(dev):
+        stream = L.stream_handle()
+        tri = torch.empty((n_faces, MD_TRI_FLOATS), dtype=torch.float32, device=dev)
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+        L.launch("hn_md_pack", L.ptr(vertices), v, L.ptr(faces), n_faces, L.ptr(tri), L.ptr(err), stream)
+        counts = torch.empty(n_faces, dtype=torch.int32, device=dev)
+        while True:
+            # fp32 cell sides: the quotient of the side and the cell count, 1 where the side is zero
+            cell = [float(np.float32(h - l) / np.float32(r)) if r > 1 or h > l else 1.0 for r, l, h in zip(res, lo, hi)]
+            if not all(c > 0.0 for c in cell):      # a side below the smallest float32 times R
+                res = tuple(1 if not c > 0.0 else r for r, c in zip(res, cell))
+                continue
+            lo_c, cell_c = (C.c_float * 3)(*lo.tolist()), (C.c_float * 3)(*cell)
+            L.launch("hn_md_cell_count", L.ptr(tri), n_faces, lo_c, cell_c, res[0], res[1], res[2], L.ptr(counts), stream)
+            ends = torch.cumsum(counts, 0, dtype=torch.int64)
+            n_pairs, bad = torch.stack([ends[-1], err[0].to(torch.int64)]).tolist()      # host read 2
+            if bad:
+                raise ValueError(f"{what}: faces hold a vertex id outside [0, {v})")
+            if n_pairs <= INT32_MAX:
+                break
+            if max(res) == 1:
+                raise ValueError(f"{what}: {n_pairs} (cell, face) pairs exceed 2**31 - 1 = {INT32_MAX}")
+            res = tuple(max(1, r // 2) for r in res)
+        n_cells = res[0] * res[1] * res[2]
+        if n_pairs == 0:
+            raise ValueError(f"{what}: the vertices of the faces are not finite")
+        pair_cell = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        pair_face = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+        L.launch("hn_md_cell_fill", L.ptr(tri), n_faces, lo_c, cell_c, res[0], res[1], res[2], L.ptr(ends), n_pairs,
+                 L.ptr(pair_cell), L.ptr(pair_face), stream)
+        if n_cells > 1:
+            sorted_cell, order = torch.sort(pair_cell, stable=True)
+            cell_begin = torch.searchsorted(sorted_cell, torch.arange(n_cells + 1, dtype=torch.int32, device=dev))
+            cell_begin, pair_face = cell_begin.to(torch.int32), pair_face[order].contiguous()
+        else:
+            cell_begin = torch.tensor([0, n_pairs], dtype=torch.int32, device=dev)
+    return {'tri': tri, 'cell_begin': cell_begin.contiguous(), 'pair_face': pair_face, 'lo': lo.tolist(), 'cell': cell,
+            'resolution': res, 'num_faces': n_faces}
+
+
+def _check_grid(grid, what: str):
+    try:
+        res = check_grid_resolution(grid['resolution'], what)
+        tri, cell_begin, pair_face = grid['tri'], grid['cell_begin'], grid['pair_face']
+        lo, cell, n_faces = [float(x) for x in grid['lo']], [float(x) for x in grid['cell']], int(grid['num_faces'])
+        ok = (tri.dtype == torch.float32 and tuple(tri.shape) == (n_faces, MD_TRI_FLOATS) and tri.is_contiguous()
+              and cell_begin.dtype == torch.int32 and cell_begin.is_contiguous() and pair_face.dtype == torch.int32
+              and pair_face.dim() == 1 and pair_face.is_contiguous() and len(lo) == 3 and len(cell) == 3
+              and tuple(cell_begin.shape) == ((res[0] * res[1] * res[2] if n_faces else 1) + 1,))
+    except (KeyError, TypeError, ValueError, AttributeError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: grid must be what distance_grid returned")
+    return res, tri, cell_begin, pair_face, lo, cell, n_faces
+
+
+@torch.no_grad()
+def grid_query(points: torch.Tensor, grid: Dict, max_distance=None, sort_queries: bool = True) -> Dict[str, torch.Tensor]:
+    """{'distance': (N,) fp32, 'face': (N,) int32, 'closest': (N, 3) fp32}: for every point of points (N, 3) fp32 the
+    nearest point of the mesh behind `grid` (distance_grid's), its face (ties to the smallest id) and the distance
+    (hn_md_query; DESIGN.md 3.13 holds the definition): the same bits as testing every face, whatever the resolution.
+    A point that is not finite gives NaN, -1, NaN; a mesh without faces +inf, -1, NaN; with max_distance, so does every
+    point farther than that from the mesh, and the search stops at that radius.  sort_queries: the queries are sorted by
+    their cell (hn_md_cell_keys, torch.sort) and the kernel reads them through the permutation, so that the lanes of a wave
+    walk the same cells; the results are the same bits, in the caller's order, either way.  No host synchronisation."""
+    what = "grid_query"
+    points = check_points(points, what, "points")
+    max_d = check_max_distance(max_distance, what)
+    res, tri, cell_begin, pair_face, lo, cell, n_faces = _check_grid(grid, what)
+    n = points.shape[0]
+    if n > INT32_MAX:
+        raise ValueError(f"{what}: {n} points exceed 2**31 - 1 = {INT32_MAX}")
+    L.require_gpu(points, tri)
+    dev = points.device
+    if tri.device != dev:
+        raise ValueError(f"{what}: points and grid must live on one device")
+    out = {'distance': torch.empty(n, dtype=torch.float32, device=dev), 'face': torch.empty(n, dtype=torch.int32, device=dev),
+           'closest': torch.empty((n, 3), dtype=torch.float32, device=dev)}
+    if n == 0:
+        return out
+    if n_faces == 0:
+        out['distance'].fill_(float("inf"))
+        out['face'].fill_(-1)
+        out['closest'].fill_(float("nan"))
+        return out
+    L.load()
+    lo_c, cell_c = (C.c_float * 3)(*lo), (C.c_float * 3)(*cell)
+    with torch.cuda.device(dev):
+        stream = L.stream_handle()
+        perm = None
+        if sort_queries and res != (1, 1, 1) and n > 1:
+            keys = torch.empty(n, dtype=torch.int32, device=dev)
+            L.launch("hn_md_cell_keys", L.ptr(points), n, lo_c, cell_c, res[0], res[1], res[2], L.ptr(keys), stream)
+            perm = torch.sort(keys).indices
+        L.launch("hn_md_query", L.ptr(points), n, L.ptr(perm), L.ptr(tri), n_faces, L.ptr(cell_begin), L.ptr(pair_face),
+                 pair_face.shape[0], lo_c, cell_c, res[0], res[1], res[2], max_d, L.ptr(out['distance']), L.ptr(out['face']),
+                 L.ptr(out['closest']), stream)
+    return out

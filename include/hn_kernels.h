@@ -831,6 +831,58 @@ int hn_tsdf_face_keep(const int32_t* faces_dev, long long n_faces, const float* 
                       const float* weight_dev, int nx, int ny, int nz, const float* bounds_host, int32_t* fkeep_dev,
                       int32_t* vkeep_dev, hnStream_t stream);
 
+/* Mesh-to-mesh distance (csrc/hn_mesh_distance.hip; DESIGN.md 3.13 holds the definition, tests/mesh_distance_restated.py
+ * restates it in NumPy float32).  Vertices (V, 3) fp32, faces (F, 3) int32; every fp32 operation that decides a result is
+ * rounded on its own, dot(u, v) = (ux*vx + uy*vy) + uz*vz.  lo_host / cell_host: three HOST floats each, the low corner
+ * and the cell sides of a grid of rx x ry x rz cells (1 .. 256 each: a cell index fits 24 bits, a face's cell count an
+ * int32); idx_c(x) = floorf((x - lo_c) / cell_c) clamped to [0, R_c - 1], a NaN giving 0; cell = (iz * ry + iy) * rx + ix.
+ *   hn_md_face_weights  a2[f] = |(B - A) x (C - A)|, twice the area: each component of the cross product one product minus
+ *                another, the length sqrt(dot(n, n)); 0 unless finite.  A face with an id outside [0, V) gets 0 and stores 1
+ *                into err[0] (int32, zeroed by the caller).
+ *   hn_md_sample        sample k < n of the surface: h_j = splitmix64(key + 3 k + j), key = splitmix64(seed) (64-bit wrap-around);
+ *                t = the high 64 bits of h_0 * W with W = cdf[F - 1]; face = the first f with cdf[f] > t (cdf (F) int64: the
+ *                inclusive scan of the caller's integer weights, W > 0); u1 = (h_1 >> 40) * 2^-24, u2 likewise from h_2;
+ *                s = sqrt(u1); bary (n, 3) = (1 - s, s * (1 - u2), s * u2); points (n, 3) = (b0*A + b1*B) + b2*C per
+ *                coordinate (NaN when the face holds an id outside [0, V)); face (n) int32.
+ *   hn_md_pack          tri (F, 12) fp32 = A, B, C and three zeros of padding, so that a candidate is three
+ *                16-byte loads and no index; NaN in all nine for a face with an id outside [0, V), which stores 1 into err[0].
+ *   hn_md_cell_count    counts[f] (int32) = the cells of [idx(min corner), idx(max corner)] of packed triangle f, 0 when it
+ *                holds a NaN.
+ *   hn_md_cell_fill     ends = the inclusive scan (int64) of counts, n_pairs its last entry: face f writes its (cell, face)
+ *                pairs, x fastest, to the rows ends[f] - counts[f] .. ends[f] - 1 of pair_cell / pair_face (int32).  A row
+ *                outside [0, n_pairs) is not written.
+ *   hn_md_cell_keys     keys[i] (int32) = the cell of query point i (the key the caller sorts the queries by).
+ *   hn_md_query         one work-item per query slot j < n: point i = perm[j] (perm (n) int64, NULL: i = j; an entry outside
+ *                [0, n) is skipped) gets the lexicographic minimum of (d2, face id) over the faces with d2 < +inf, d2 the
+ *                squared distance to the closest point of the triangle by Voronoi regions (operation order: DESIGN.md 3.13):
+ *                distance (n) fp32 = sqrt(d2), face (n) int32, closest (n, 3) fp32; +inf, -1, NaN without such a face; NaN,
+ *                -1, NaN for a point that is not finite.  The faces of cell c are pair_face[cell_begin[c] .. cell_begin[c +
+ *                1]) (cell_begin: rx * ry * rz + 1 int32, clamped to [0, n_pairs]; an entry of pair_face outside [0, F) is
+ *                skipped).  The walk goes through Chebyshev shells of cells around the point's cell and stops when every
+ *                cell was visited or no unvisited face can come closer: the result is that of testing every face.
+ *                max_distance >= 0: a result with distance > max_distance becomes +inf, -1, NaN and the walk may stop at
+ *                that radius; max_distance < 0: no limit.
+ * Status, before any launch: -2 for a size out of range (a count <= 0 or above 2^31 - 1, a resolution outside 1 .. 256,
+ * a cell side that is not positive and finite, a NaN max_distance), -3 for a NULL pointer that must not be. */
+int hn_md_face_weights(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces,
+                       float* a2_dev, int32_t* err_dev, hnStream_t stream);
+int hn_md_sample(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces,
+                 const int64_t* cdf_dev, long long n, long long seed, float* points_dev, int32_t* face_dev, float* bary_dev,
+                 hnStream_t stream);
+int hn_md_pack(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces, float* tri_dev,
+               int32_t* err_dev, hnStream_t stream);
+int hn_md_cell_count(const float* tri_dev, long long n_faces, const float* lo_host, const float* cell_host, int rx, int ry,
+                     int rz, int32_t* counts_dev, hnStream_t stream);
+int hn_md_cell_fill(const float* tri_dev, long long n_faces, const float* lo_host, const float* cell_host, int rx, int ry,
+                    int rz, const int64_t* ends_dev, long long n_pairs, int32_t* pair_cell_dev, int32_t* pair_face_dev,
+                    hnStream_t stream);
+int hn_md_cell_keys(const float* points_dev, long long n, const float* lo_host, const float* cell_host, int rx, int ry, int rz,
+                    int32_t* keys_dev, hnStream_t stream);
+int hn_md_query(const float* points_dev, long long n, const int64_t* perm_dev, const float* tri_dev, long long n_faces,
+                const int32_t* cell_begin_dev, const int32_t* pair_face_dev, long long n_pairs, const float* lo_host,
+                const float* cell_host, int rx, int ry, int rz, float max_distance, float* distance_dev, int32_t* face_dev,
+                float* closest_dev, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *
