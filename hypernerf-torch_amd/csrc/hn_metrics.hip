@@ -18,23 +18,16 @@
 // to p: d/dx = A^ + 2 x B^ + y C^, d/dy = A'^ + 2 y B^ + x C^.  Every tap that reaches p comes from a map pixel within
 // the window radius of p (reflection only brings coordinates closer), so a tile needs the maps on its tile + R halo
 // and the inputs on tile + 2R.
-#include "hn_common.h"
-
-#define HN_SSIM_TW 32
-#define HN_SSIM_TH 16
-#define HN_SSIM_THREADS 256
+//
+// The tile, the image pair, the two passes and the sums are hn_window.h's, shared with hn_msssim.hip.
+#include "hn_window.h"
 
 struct HnSsimWin {
   float w[2 * HN_SSIM_MAX_R + 1];
 };
 
-struct HnSsimShape {
-  const float* x;
-  const float* y;
-  long long xs[4], ys[4];   // element strides of (n, c, h, w)
-  int n, c, h, w;
-  int tiles_x, tiles_y;
-  float c1, c2, eps;
+struct HnSsimShape : HnWinPair {
+  float eps;
 };
 
 // reflect padding's source coordinate for t in [-(n-1), 2(n-1)] (F.pad mode='reflect': the edge is not repeated),
@@ -47,24 +40,6 @@ HN_DEV int hn_reflect(int t, int n) {
 
 HN_DEV float hn_ld(const float* p, const long long* s, int n, int c, int yy, int xx) {
   return p[n * s[0] + c * s[1] + yy * s[2] + xx * s[3]];
-}
-
-struct HnSsimTile {
-  int plane, n, c, y0, x0;
-};
-
-HN_DEV HnSsimTile hn_ssim_tile(const HnSsimShape& a) {
-  HnSsimTile t;
-  int b = blockIdx.x;
-  const int tx = b % a.tiles_x;
-  b /= a.tiles_x;
-  const int ty = b % a.tiles_y;
-  t.plane = b / a.tiles_y;
-  t.n = t.plane / a.c;
-  t.c = t.plane % a.c;
-  t.y0 = ty * HN_SSIM_TH;
-  t.x0 = tx * HN_SSIM_TW;
-  return t;
 }
 
 // kornia 0.6.1 metrics.ssim for one pixel from its five filtered moments
@@ -97,9 +72,9 @@ HN_DEV float hn_dssim(float s) { return fminf(fmaxf((1.0f - s) / 2.0f, 0.0f), 1.
 // Stage x and y of rows [y0 - HALO, y0 + TH + HALO) x cols [x0 - HALO, x0 + TW + HALO) with reflect indexing.  With
 // `zero_far`, coordinates beyond the reflect range [-R, n-1+R] load 0 (they only feed map pixels outside the image).
 template <int R, int HALO>
-HN_DEV void hn_ssim_stage(const HnSsimShape& a, const HnSsimTile& t, float* sx, float* sy, bool zero_far) {
-  constexpr int SW = HN_SSIM_TW + 2 * HALO, SH = HN_SSIM_TH + 2 * HALO;
-  for (int i = threadIdx.x; i < SH * SW; i += HN_SSIM_THREADS) {
+HN_DEV void hn_ssim_stage(const HnSsimShape& a, const HnWinTile& t, float* sx, float* sy, bool zero_far) {
+  constexpr int SW = HN_WIN_TW + 2 * HALO, SH = HN_WIN_TH + 2 * HALO;
+  for (int i = threadIdx.x; i < SH * SW; i += HN_WIN_THREADS) {
     const int gy = t.y0 - HALO + i / SW, gx = t.x0 - HALO + i % SW;
     float vx = 0.0f, vy = 0.0f;
     if (!zero_far || (gy >= -R && gy <= a.h - 1 + R && gx >= -R && gx <= a.w - 1 + R)) {
@@ -112,95 +87,40 @@ HN_DEV void hn_ssim_stage(const HnSsimShape& a, const HnSsimTile& t, float* sx, 
   }
 }
 
-// horizontal pass of the five moments: hm[k][row][col] for rows [0, SH) and OW output cols, the window starting at
-// staged col `col`
 template <int R>
-HN_DEV void hn_ssim_hpass(const HnSsimWin& win, const float* sx, const float* sy, float* hm, int SH, int SW, int OW) {
-  const int plane = SH * OW;
-  for (int i = threadIdx.x; i < plane; i += HN_SSIM_THREADS) {
-    const int row = i / OW, col = i % OW;
-    const float* px = sx + row * SW + col;
-    const float* py = sy + row * SW + col;
-    float m0 = 0.0f, m1 = 0.0f, m2 = 0.0f, m3 = 0.0f, m4 = 0.0f;
-#pragma unroll
-    for (int k = 0; k <= 2 * R; ++k) {
-      const float wk = win.w[k], xv = px[k], yv = py[k];
-      m0 += wk * xv;
-      m1 += wk * yv;
-      m2 += wk * (xv * xv);
-      m3 += wk * (yv * yv);
-      m4 += wk * (xv * yv);
-    }
-    hm[i] = m0;
-    hm[plane + i] = m1;
-    hm[2 * plane + i] = m2;
-    hm[3 * plane + i] = m3;
-    hm[4 * plane + i] = m4;
-  }
-}
-
-// vertical pass for one pixel: the five moments at (row + R, col) of the horizontal planes
-template <int R>
-HN_DEV void hn_ssim_vpass(const HnSsimWin& win, const float* hm, int plane, int OW, int row, int col, float m[5]) {
-#pragma unroll
-  for (int j = 0; j < 5; ++j) m[j] = 0.0f;
-#pragma unroll
-  for (int k = 0; k <= 2 * R; ++k) {
-    const float wk = win.w[k];
-    const float* p = hm + (row + k) * OW + col;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) m[j] += wk * p[j * plane];
-  }
-}
-
-// fixed-order workgroup sum (wave butterfly, then the four wave totals in order); the result is valid in thread 0
-HN_DEV float hn_ssim_block_sum(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.0f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < HN_SSIM_THREADS / 64; ++i) s += red[i];
-  return s;
-}
-
-template <int R>
-__global__ __launch_bounds__(HN_SSIM_THREADS) void hn_ssim_forward_kernel(HnSsimShape a, HnSsimWin win, float* map,
+__global__ __launch_bounds__(HN_WIN_THREADS) void hn_ssim_forward_kernel(HnSsimShape a, HnSsimWin win, float* map,
                                                                            float* partials) {
-  constexpr int SW = HN_SSIM_TW + 2 * R, SH = HN_SSIM_TH + 2 * R;
+  constexpr int SW = HN_WIN_TW + 2 * R, SH = HN_WIN_TH + 2 * R;
   __shared__ float sx[SH * SW], sy[SH * SW];
-  __shared__ float hm[5 * SH * HN_SSIM_TW];
-  __shared__ float red[HN_SSIM_THREADS / 64];
-  const HnSsimTile t = hn_ssim_tile(a);
+  __shared__ float hm[5 * SH * HN_WIN_TW];
+  __shared__ float red[HN_WIN_THREADS / 64];
+  const HnWinTile t = hn_win_tile(a);
   hn_ssim_stage<R, R>(a, t, sx, sy, false);
   __syncthreads();
-  hn_ssim_hpass<R>(win, sx, sy, hm, SH, SW, HN_SSIM_TW);
+  hn_win_row_pass<2 * R + 1>(win.w, 0, sx, sy, SW, hm, SH, HN_WIN_TW, SH * HN_WIN_TW);
   __syncthreads();
-  const int col = threadIdx.x % HN_SSIM_TW, gx = t.x0 + col;
+  const int col = threadIdx.x % HN_WIN_TW, gx = t.x0 + col;
   float acc = 0.0f;
-  for (int row = threadIdx.x / HN_SSIM_TW; row < HN_SSIM_TH; row += HN_SSIM_THREADS / HN_SSIM_TW) {
+  for (int row = threadIdx.x / HN_WIN_TW; row < HN_WIN_TH; row += HN_WIN_THREADS / HN_WIN_TW) {
     const int gy = t.y0 + row;
     if (gy >= a.h || gx >= a.w) continue;
     float m[5];
-    hn_ssim_vpass<R>(win, hm, SH * HN_SSIM_TW, HN_SSIM_TW, row, col, m);
+    hn_win_col_pass<2 * R + 1>(win.w, 0, hm, HN_WIN_TW, SH * HN_WIN_TW, row, col, m);
     const float l = hn_dssim(hn_ssim_pix(m, a.c1, a.c2, a.eps).s);
     if (map != nullptr) map[((long long)t.plane * a.h + gy) * a.w + gx] = l;
     acc += l;
   }
   if (partials != nullptr) {
-    const float s = hn_ssim_block_sum(acc, red);
+    const float s = hn_block_sum<HN_WIN_THREADS>(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
   }
 }
 
-__global__ __launch_bounds__(HN_SSIM_THREADS) void hn_ssim_sum_kernel(const float* partials, int n, float* out) {
-  __shared__ float red[HN_SSIM_THREADS / 64];
+__global__ __launch_bounds__(HN_WIN_THREADS) void hn_ssim_sum_kernel(const float* partials, int n, float* out) {
+  __shared__ float red[HN_WIN_THREADS / 64];
   float v = 0.0f;
-  for (int i = threadIdx.x; i < n; i += HN_SSIM_THREADS) v += partials[i];
-  const float s = hn_ssim_block_sum(v, red);
+  for (int i = threadIdx.x; i < n; i += HN_WIN_THREADS) v += partials[i];
+  const float s = hn_block_sum<HN_WIN_THREADS>(v, red);
   if (threadIdx.x == 0) out[0] = s;
 }
 
@@ -228,28 +148,28 @@ HN_DEV float hn_ssim_adjoint(const HnSsimWin& win, int p, int n, F at) {
 }
 
 template <int R>
-__global__ __launch_bounds__(HN_SSIM_THREADS) void hn_ssim_backward_kernel(HnSsimShape a, HnSsimWin win,
+__global__ __launch_bounds__(HN_WIN_THREADS) void hn_ssim_backward_kernel(HnSsimShape a, HnSsimWin win,
                                                                             const float* g_scalar, const float* g_map,
                                                                             float* d_x, float* d_y) {
-  constexpr int SW = HN_SSIM_TW + 4 * R, SH = HN_SSIM_TH + 4 * R;    // inputs: tile + 2R
-  constexpr int GW = HN_SSIM_TW + 2 * R, GH = HN_SSIM_TH + 2 * R;    // maps: tile + R
-  constexpr int HM = 5 * SH * GW, HA = 4 * GH * HN_SSIM_TW;
+  constexpr int SW = HN_WIN_TW + 4 * R, SH = HN_WIN_TH + 4 * R;    // inputs: tile + 2R
+  constexpr int GW = HN_WIN_TW + 2 * R, GH = HN_WIN_TH + 2 * R;    // maps: tile + R
+  constexpr int HM = 5 * SH * GW, HA = 4 * GH * HN_WIN_TW;
   __shared__ float sx[SH * SW], sy[SH * SW];
   __shared__ float hm[HM > HA ? HM : HA];    // horizontal moments, then the horizontal adjoint of the four maps
   __shared__ float gm[4 * GH * GW];          // A, A', B, C
-  const HnSsimTile t = hn_ssim_tile(a);
+  const HnWinTile t = hn_win_tile(a);
   hn_ssim_stage<R, 2 * R>(a, t, sx, sy, true);
   __syncthreads();
-  hn_ssim_hpass<R>(win, sx, sy, hm, SH, SW, GW);
+  hn_win_row_pass<2 * R + 1>(win.w, 0, sx, sy, SW, hm, SH, GW, SH * GW);
   __syncthreads();
   const float gs = g_scalar != nullptr ? g_scalar[0] : 0.0f;
-  for (int i = threadIdx.x; i < GH * GW; i += HN_SSIM_THREADS) {
+  for (int i = threadIdx.x; i < GH * GW; i += HN_WIN_THREADS) {
     const int row = i / GW, col = i % GW;
     const int qy = t.y0 - R + row, qx = t.x0 - R + col;
     float ga = 0.0f, gb = 0.0f, gbb = 0.0f, gc = 0.0f;
     if (qy >= 0 && qy < a.h && qx >= 0 && qx < a.w) {
       float m[5];
-      hn_ssim_vpass<R>(win, hm, SH * GW, GW, row, col, m);
+      hn_win_col_pass<2 * R + 1>(win.w, 0, hm, GW, SH * GW, row, col, m);
       const HnSsimPix p = hn_ssim_pix(m, a.c1, a.c2, a.eps);
       const float l = (1.0f - p.s) / 2.0f;
       const float up = g_map != nullptr ? g_map[((long long)t.plane * a.h + qy) * a.w + qx] : gs;
@@ -272,8 +192,8 @@ __global__ __launch_bounds__(HN_SSIM_THREADS) void hn_ssim_backward_kernel(HnSsi
   }
   __syncthreads();
   // horizontal adjoint: rows of the map region, the tile's columns
-  for (int i = threadIdx.x; i < GH * HN_SSIM_TW; i += HN_SSIM_THREADS) {
-    const int row = i / HN_SSIM_TW, col = i % HN_SSIM_TW, gx = t.x0 + col;
+  for (int i = threadIdx.x; i < GH * HN_WIN_TW; i += HN_WIN_THREADS) {
+    const int row = i / HN_WIN_TW, col = i % HN_WIN_TW, gx = t.x0 + col;
     float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (gx < a.w) {
       const int base = t.x0 - R;      // image column of map col 0; |q - gx| <= R for every tap that is read
@@ -284,20 +204,20 @@ __global__ __launch_bounds__(HN_SSIM_THREADS) void hn_ssim_backward_kernel(HnSsi
       }
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) hm[k * GH * HN_SSIM_TW + i] = v[k];
+    for (int k = 0; k < 4; ++k) hm[k * GH * HN_WIN_TW + i] = v[k];
   }
   __syncthreads();
   // vertical adjoint and the products with the inputs
-  const int col = threadIdx.x % HN_SSIM_TW, gx = t.x0 + col;
-  for (int row = threadIdx.x / HN_SSIM_TW; row < HN_SSIM_TH; row += HN_SSIM_THREADS / HN_SSIM_TW) {
+  const int col = threadIdx.x % HN_WIN_TW, gx = t.x0 + col;
+  for (int row = threadIdx.x / HN_WIN_TW; row < HN_WIN_TH; row += HN_WIN_THREADS / HN_WIN_TW) {
     const int gy = t.y0 + row;
     if (gy >= a.h || gx >= a.w) continue;
     const int base = t.y0 - R;
     float v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float* h = hm + k * GH * HN_SSIM_TW + col;
-      v[k] = hn_ssim_adjoint<R>(win, gy, a.h, [&](int q) { return h[(q - base) * HN_SSIM_TW]; });
+      const float* h = hm + k * GH * HN_WIN_TW + col;
+      v[k] = hn_ssim_adjoint<R>(win, gy, a.h, [&](int q) { return h[(q - base) * HN_WIN_TW]; });
     }
     const int s = (row + 2 * R) * SW + col + 2 * R;
     const float xv = sx[s], yv = sy[s];
@@ -307,42 +227,31 @@ __global__ __launch_bounds__(HN_SSIM_THREADS) void hn_ssim_backward_kernel(HnSsi
   }
 }
 
+// the window and shape checks of every entry point: the launch's workgroups, or 0 for arguments that are refused
+static long long hn_ssim_blocks(int n, int c, int h, int w, int window) {
+  if (window < 3 || window > 2 * HN_SSIM_MAX_R + 1 || (window & 1) == 0) return 0;
+  if (h <= window / 2 || w <= window / 2) return 0;      // reflect padding needs more than the radius
+  return hn_win_blocks(n, c, h, w);
+}
+
 static int hn_ssim_setup(const float* x, const int64_t* xs, const float* y, const int64_t* ys, int n, int c, int h, int w,
                          const float* window_host, int window, float c1, float c2, float eps, HnSsimShape* a,
                          HnSsimWin* win, long long* blocks) {
-  if (window < 3 || window > 2 * HN_SSIM_MAX_R + 1 || (window & 1) == 0) return -2;
-  const int r = window / 2;
-  if (n < 1 || c < 1 || h <= r || w <= r) return -2;
-  const long long tiles = (long long)((w + HN_SSIM_TW - 1) / HN_SSIM_TW) * ((h + HN_SSIM_TH - 1) / HN_SSIM_TH);
-  if (tiles * n * c > 0x7fffffffLL || (long long)n * c * h * w > (1LL << 40)) return -2;
+  *blocks = hn_ssim_blocks(n, c, h, w, window);
+  if (*blocks == 0) return -2;
   if (x == nullptr || y == nullptr || xs == nullptr || ys == nullptr || window_host == nullptr) return -3;
-  a->x = x;
-  a->y = y;
-  for (int i = 0; i < 4; ++i) {
-    a->xs[i] = xs[i];
-    a->ys[i] = ys[i];
-  }
-  a->n = n;
-  a->c = c;
-  a->h = h;
-  a->w = w;
-  a->tiles_x = (w + HN_SSIM_TW - 1) / HN_SSIM_TW;
-  a->tiles_y = (h + HN_SSIM_TH - 1) / HN_SSIM_TH;
+  hn_win_pair(a, x, xs, y, ys, c, h, w);
   a->c1 = c1;
   a->c2 = c2;
   a->eps = eps;
   for (int i = 0; i < 2 * HN_SSIM_MAX_R + 1; ++i) win->w[i] = i < window ? window_host[i] : 0.0f;
-  *blocks = tiles * n * c;
   return 0;
 }
 
 extern "C" int hn_ssim_workspace_bytes(int n, int c, int h, int w, int window, int64_t* bytes) {
   if (bytes == nullptr) return -3;
-  if (window < 3 || window > 2 * HN_SSIM_MAX_R + 1 || (window & 1) == 0 || n < 1 || c < 1 || h <= window / 2 ||
-      w <= window / 2)
-    return -2;
-  const long long blocks =
-      (long long)n * c * ((w + HN_SSIM_TW - 1) / HN_SSIM_TW) * ((h + HN_SSIM_TH - 1) / HN_SSIM_TH);
+  const long long blocks = hn_ssim_blocks(n, c, h, w, window);
+  if (blocks == 0) return -2;
   *bytes = (blocks * 4 + 15) / 16 * 16;
   return 0;
 }
@@ -370,11 +279,11 @@ extern "C" int hn_ssim_forward(const float* pred, const int64_t* pred_strides, c
   if (dssim_map == nullptr && sum_out == nullptr) return -3;
   if (sum_out != nullptr && workspace == nullptr) return -3;
   float* partials = sum_out != nullptr ? static_cast<float*>(workspace) : nullptr;
-  HN_SSIM_DISPATCH(hn_ssim_forward_kernel, dim3((unsigned)blocks), dim3(HN_SSIM_THREADS), 0, (hipStream_t)stream, a, win,
+  HN_SSIM_DISPATCH(hn_ssim_forward_kernel, dim3((unsigned)blocks), dim3(HN_WIN_THREADS), 0, (hipStream_t)stream, a, win,
                    dssim_map, partials)
   HN_CHECK_LAUNCH();
   if (sum_out != nullptr) {
-    hipLaunchKernelGGL(hn_ssim_sum_kernel, dim3(1), dim3(HN_SSIM_THREADS), 0, (hipStream_t)stream, partials, (int)blocks,
+    hipLaunchKernelGGL(hn_ssim_sum_kernel, dim3(1), dim3(HN_WIN_THREADS), 0, (hipStream_t)stream, partials, (int)blocks,
                        sum_out);
     HN_CHECK_LAUNCH();
   }
@@ -392,7 +301,7 @@ extern "C" int hn_ssim_backward(const float* pred, const int64_t* pred_strides, 
                                &win, &blocks);
   if (rc != 0) return rc;
   if (d_pred == nullptr || (g_scalar == nullptr) == (g_map == nullptr)) return -3;
-  HN_SSIM_DISPATCH(hn_ssim_backward_kernel, dim3((unsigned)blocks), dim3(HN_SSIM_THREADS), 0, (hipStream_t)stream, a,
+  HN_SSIM_DISPATCH(hn_ssim_backward_kernel, dim3((unsigned)blocks), dim3(HN_WIN_THREADS), 0, (hipStream_t)stream, a,
                    win, g_scalar, g_map, d_pred, d_gt)
   HN_CHECK_LAUNCH();
   return 0;

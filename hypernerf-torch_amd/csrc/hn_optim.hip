@@ -11,6 +11,7 @@
 // t = 6 at 6.0005 instead of 5.9942, and the first rectified step size 0.3 % off.)  The per-element arithmetic is the
 // reference's fp32 tensor arithmetic, operation for operation.
 #include "hn_common.h"
+#include "hn_window.h"      // hn_wave_sum
 
 // The launch grid of every *_step entry point: one block per CU, grid-stride: every thread pays the schedule arithmetic
 // (Adam: two powf, an rsqrtf) once for ~6 vectors instead of once per vector (Adam, 2048 blocks: 26.3 us per launch at
@@ -297,12 +298,6 @@ extern "C" int hn_radam_step(float* params, float* grads, float* exp_avg, float*
 // written with comparisons: a NaN gradient stays NaN as in torch (fminf / fmaxf would drop it); v = +inf changes nothing
 HN_DEV float hn_clip_value(float g, float v) { return g > v ? v : (g < -v ? -v : g); }
 
-HN_DEV float hn_clip_wave_sum(float v) {      // lane 0 of a 64-lane wave ends up with the sum, in a fixed order
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 #define HN_CLIP_PARTIALS 256      // floats of `work` ahead of the ticket word: the largest grid of hn_step_blocks
 
 __global__ __launch_bounds__(256) void hn_grad_norm_kernel(const float* g, long long n, float vp, float gscale,
@@ -337,7 +332,7 @@ __global__ __launch_bounds__(256) void hn_grad_norm_kernel(const float* g, long 
       }
     }
   }
-  s = hn_clip_wave_sum(s);
+  s = hn_wave_sum(s);
   if ((threadIdx.x & 63) == 0) sh[HN_CLIP_PARTIALS + (threadIdx.x >> 6)] = s;
   __syncthreads();
   unsigned* ticket = reinterpret_cast<unsigned*>(work + HN_CLIP_PARTIALS);

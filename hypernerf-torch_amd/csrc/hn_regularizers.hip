@@ -6,6 +6,7 @@
 // head (hn_bg_loss_*), Barron's general loss at alpha = -2 (Geman-McClure) on the squared residual.  Both are a few
 // bytes per point and HBM / latency bound; the warp field between them is the MLP machine's business.
 #include "hn_common.h"
+#include "hn_window.h"      // hn_wave_sum
 
 // ------------------------------------------------------------------------------------------------
 // sampler: out_ids[n] = ids[min(int(u[n,1] * K), K-1)], out_points[n] = points[min(int(u[n,0] * M), M-1)] + std * nrm[n]
@@ -70,12 +71,6 @@ HN_DEV HnBgRow hn_bg_row(const float* __restrict__ w, const float* __restrict__ 
 }
 HN_DEV float hn_bg_gscale(float g, float inv_s2, int n) { return g * 16.0f * inv_s2 / (float)n; }
 
-HN_DEV float hn_bg_wave_sum(float v) {      // lane 0 of a 64-lane wave ends up with the sum, in a fixed order
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(1024) void hn_bg_loss_fwd_kernel(const float* __restrict__ warped,
                                                               const float* __restrict__ points, int n, float inv_s2,
                                                               float* __restrict__ loss, float* __restrict__ d_warped) {
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(1024) void hn_bg_loss_fwd_kernel(const float* __res
       o[0] = r.d[0]; o[1] = r.d[1]; o[2] = r.d[2];
     }
   }
-  s = hn_bg_wave_sum(s);
+  s = hn_wave_sum(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {

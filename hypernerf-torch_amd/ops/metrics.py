@@ -1,4 +1,5 @@
-"""SSIM and multi-scale SSIM of images on the GPU (csrc/hn_metrics.hip, csrc/hn_msssim.hip)."""
+"""SSIM and multi-scale SSIM of images on the GPU (csrc/hn_metrics.hip, csrc/hn_msssim.hip; their shared tile, passes and
+sums: csrc/hn_window.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,6 +11,25 @@ from .. import _lib as L
 
 __all__ = ["SSIM_MAX_WINDOW", "ssim_window", "ssim_dssim", "MSSSIM_LEVELS", "MSSSIM_MAX_SIZE", "MSSSIM_WEIGHTS",
            "msssim_window", "msssim_pyramid", "msssim_workspace_bytes", "msssim_levels"]
+
+
+def _check_pair(name, pred, gt, reflect_radius=None):
+    """What both metrics ask of their images: two float32 (N, C, H, W) tensors of one shape, not empty, and (SSIM) sides
+    that reflect padding by `reflect_radius` allows."""
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
+        raise ValueError(f"{name}: pred and gt must be tensors")
+    if pred.dim() != 4 or pred.shape != gt.shape:
+        raise ValueError(f"{name}: pred and gt must both be (N, C, H, W) of one shape, got {tuple(pred.shape)} and "
+                         f"{tuple(gt.shape)}")
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
+        raise ValueError(f"{name}: pred and gt must be float32")
+    h, w = pred.shape[2], pred.shape[3]
+    if reflect_radius is not None and (h <= reflect_radius or w <= reflect_radius):
+        raise ValueError(f"{name}: H and W must be larger than window_size // 2 = {reflect_radius} (reflect padding), "
+                         f"got {h} x {w}")
+    if pred.numel() == 0:
+        raise ValueError(f"{name}: empty images")
+
 
 # --------------------------------------------------------------------------------------------
 # SSIM (metrics.py:15-20: kornia's ssim loss)
@@ -42,19 +62,7 @@ def _ssim_check(pred, gt, window_size, reduction):
         raise ValueError(f"ssim: window_size {window_size} is above the kernels' limit of {SSIM_MAX_WINDOW}")
     if reduction not in ("mean", "sum", "none"):
         raise ValueError(f"ssim: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
-    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
-        raise ValueError("ssim: pred and gt must be tensors")
-    if pred.dim() != 4 or pred.shape != gt.shape:
-        raise ValueError(f"ssim: pred and gt must both be (N, C, H, W) of one shape, got {tuple(pred.shape)} and "
-                         f"{tuple(gt.shape)}")
-    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError("ssim: pred and gt must be float32")
-    h, w = pred.shape[2], pred.shape[3]
-    if h <= window_size // 2 or w <= window_size // 2:
-        raise ValueError(f"ssim: H and W must be larger than window_size // 2 = {window_size // 2} (reflect padding), "
-                         f"got {h} x {w}")
-    if pred.numel() == 0:
-        raise ValueError("ssim: empty images")
+    _check_pair("ssim", pred, gt, reflect_radius=window_size // 2)
 
 
 class _SsimFn(torch.autograd.Function):
@@ -178,15 +186,7 @@ def msssim_levels(pred: torch.Tensor, gt: torch.Tensor, max_val: float = 1.0) ->
     the result carries no gradient.  The host plan (taps, sizes, workspace size) is cached per shape; the workspace
     itself comes from torch's allocator at every call, as ssim_dssim's does, so a call captured in a HIP graph takes it
     from the graph's pool and the host arrays are consumed at the launch."""
-    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
-        raise ValueError("ms_ssim: pred and gt must be tensors")
-    if pred.dim() != 4 or pred.shape != gt.shape:
-        raise ValueError(f"ms_ssim: pred and gt must both be (N, C, H, W) of one shape, got {tuple(pred.shape)} and "
-                         f"{tuple(gt.shape)}")
-    if pred.dtype != torch.float32 or gt.dtype != torch.float32:
-        raise ValueError("ms_ssim: pred and gt must be float32")
-    if pred.numel() == 0:
-        raise ValueError("ms_ssim: empty images")
+    _check_pair("ms_ssim", pred, gt)
     L.require_gpu(pred, gt)
     x, y = pred.detach(), gt.detach()
     n, c, h, w = x.shape

@@ -25,6 +25,9 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(1, 3, 2, 2), (1, 3, 4, 5), (1, 3, 17, 33), (2, 3, 63, 64), (1, 3, 65, 129), (1, 3, 378, 504)]
 WINDOWS = [3, 5, 7, 11]
 CASES = [(s, w) for s in SHAPES for w in WINDOWS if min(s[2], s[3]) > w // 2]
+# the other radii the library is built for (15 is the dispatch's default branch), on one partial tile that reflects at
+# both borders
+CASES += [((1, 3, 17, 33), w) for w in (9, 13, 15)]
 MAP_TOL, MEAN_TOL, SUM_REL_TOL, GRAD_REL_L2 = 3e-5, 3e-7, 1e-5, 3e-5
 
 
