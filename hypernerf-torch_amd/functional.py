@@ -22,6 +22,7 @@ from .machine import MlpRunner, PendingWgrad, Program, ResolvedWgrad, launch_res
 from .ops.checks import INT32_MAX           # noqa: F401
 from .ops.data import *                     # noqa: F401,F403
 from .ops.gif import *                      # noqa: F401,F403
+from .ops.lpips import *                    # noqa: F401,F403
 from .ops.mesh import *                     # noqa: F401,F403
 from .ops.mesh_render import *              # noqa: F401,F403
 from .ops.metrics import *                  # noqa: F401,F403

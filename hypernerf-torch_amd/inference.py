@@ -519,7 +519,7 @@ def validation_stack(gt: torch.Tensor, pred: torch.Tensor, depth: torch.Tensor, 
 def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False, save_dir=None, group=None,
                     image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm",
                     use_valid_mask: bool = False, ms_ssim: bool = False, save_gif=None, gif_fps: float = 30,
-                    gif_palette: str = "global", save_depth_gif: bool = False) -> Dict:
+                    gif_palette: str = "global", save_depth_gif: bool = False, lpips=None) -> Dict:
     """The per-image loop of the reference's eval.py:145-178 on the GPU: for every sample {'rays': (H*W, 8|9),
     'rgbs': (H*W, 3) optional, 'hw': (H, W) optional} render the fine level in chunks, form the (H, W, 3) image,
     its 8-bit version (eval.py:165 `(img*255).astype(uint8)`) and, when ground truth is present, the PSNR
@@ -540,7 +540,9 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     through metrics.psnr's own argument; off by default, as the reference's eval.py does not mask.
     `ms_ssim` adds the multi-scale SSIM (losses.ms_ssim, the metric of the published Nerfies / HyperNeRF tables) of every
     image with ground truth, on the same views as the SSIM: the result then also has 'ms_ssims': [float] and
-    'mean_ms_ssim': float | None.  Off by default: the result and the work done are unchanged."""
+    'mean_ms_ssim': float | None.  Off by default: the result and the work done are unchanged.
+    `lpips` = an LpipsWeights (losses.load_lpips) on the model's device adds LPIPS (losses.lpips) the same way, on the same
+    views: 'lpips': [float] and 'mean_lpips': float | None.  None by default: the result and the work done are unchanged."""
     if image_format not in ("png", "ppm"):
         raise ValueError("image_format: 'png' or 'ppm'")
     if depth_format not in ("pfm", "bytes"):
@@ -554,7 +556,8 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     from .losses import psnr as _psnr
     from .losses import ssim as _ssim
     from .losses import ms_ssim as _ms_ssim
-    imgs, depths, psnrs, ssims, ms_ssims = [], [], [], [], []
+    from .losses import lpips as _lpips
+    imgs, depths, psnrs, ssims, ms_ssims, lpipss = [], [], [], [], [], []
     gif_frames, depth_frames = [], []
     if save_depth_gif:
         lut = jet_lut()
@@ -579,6 +582,8 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
             ssims.append(float(_ssim(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None])))
             if ms_ssim:
                 ms_ssims.append(float(_ms_ssim(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None])))
+            if lpips is not None:
+                lpipss.append(float(_lpips(img.permute(2, 0, 1)[None], gt.permute(2, 0, 1)[None], lpips)))
         if save_dir is not None:
             import os
             os.makedirs(save_dir, exist_ok=True)
@@ -606,4 +611,7 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     if ms_ssim:
         out['ms_ssims'] = ms_ssims
         out['mean_ms_ssim'] = (sum(ms_ssims) / len(ms_ssims)) if ms_ssims else None
+    if lpips is not None:
+        out['lpips'] = lpipss
+        out['mean_lpips'] = (sum(lpipss) / len(lpipss)) if lpipss else None
     return out

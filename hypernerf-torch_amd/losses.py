@@ -3,7 +3,8 @@
 `MSELoss` is one HIP launch forward (both levels, both means, their sum) and one backward (`hn_mse_loss_*`,
 functional.mse_loss); the metrics `mse` and `psnr` (logging only, no gradient path in the reference) are torch
 one-liners; `ssim` runs kornia's windowed SSIM in HIP (`hn_ssim_*`, ops.metrics.ssim_dssim), differentiable as kornia's;
-`ms_ssim` is the five-level multi-scale SSIM the Nerfies / HyperNeRF tables report (`hn_msssim_*`), a metric only.
+`ms_ssim` is the five-level multi-scale SSIM the Nerfies / HyperNeRF tables report (`hn_msssim_*`), a metric only;
+`lpips` is the third number of those tables, LPIPS v0.1 over a frozen AlexNet or VGG16 (`hn_lpips_*`), a metric only.
 `BackgroundLoss` is HyperNeRF's background regularization, a training term that takes the model instead of rendered
 rays: static points of the capture through the warp field, pulled back to where they were (`hn_bg_*`).
 GPU tensors only, like every op of the package."""
@@ -13,6 +14,7 @@ import torch
 from torch import nn
 
 from . import functional as F
+from .ops import lpips as _lpips_ops
 from .ops import metrics
 
 
@@ -128,4 +130,27 @@ def ms_ssim(image_pred, image_gt, reduction='mean'):
         out = levels[:, last, 0].pow(metrics.MSSSIM_WEIGHTS[last])
         for l in range(last):
             out = out * levels[:, l, 1].pow(metrics.MSSSIM_WEIGHTS[l])
+    return out.mean() if reduction == 'mean' else out
+
+
+def load_lpips(net, backbone_path, lin_path=None, device='cuda'):
+    """The LPIPS weights of `net` ('alex' or 'vgg') from the user's files, on `device` (ops.lpips.load_lpips_weights):
+    a torchvision backbone checkpoint and the lpips package's lin weights, or one saved `lpips.LPIPS(...).state_dict()`.
+    Nothing is downloaded.  The result is what `lpips` and `evaluate_images(..., lpips=...)` take."""
+    return _lpips_ops.load_lpips_weights(net, backbone_path, lin_path).to(device)
+
+
+def lpips(image_pred, image_gt, weights, reduction='mean'):
+    """LPIPS v0.1 (Zhang et al. 2018; the lpips package with normalize=True, spatial=False, eval mode) of images in
+    [0, 1]: the sum of the five layer terms of ops.lpips.lpips_layers.  image_pred and image_gt (N, 3, H, W) fp32 on the
+    GPU, any strides, sides of at least ops.lpips.lpips_min_side(weights.net); weights: load_lpips' result on the images'
+    device.  'none' returns the (N,) values, 'mean' their average.  A metric only: there is no backward and the result
+    never requires grad."""
+    if reduction not in ('mean', 'none'):
+        raise ValueError(f"lpips: reduction must be 'mean' or 'none', got {reduction!r}")
+    layers = _lpips_ops.lpips_layers(image_pred, image_gt, weights)
+    with torch.no_grad():
+        out = layers[:, 0]
+        for l in range(1, _lpips_ops.LPIPS_LAYERS):      # a fixed order: the same bits run to run
+            out = out + layers[:, l]
     return out.mean() if reduction == 'mean' else out

@@ -1,6 +1,7 @@
 """The host halves of the kernels outside the training step, one module per kernel source file:
 
     metrics      csrc/hn_metrics.hip, csrc/hn_msssim.hip    SSIM (differentiable) and multi-scale SSIM
+    lpips        csrc/hn_lpips.hip                           LPIPS: the backbones' layers on the fp32 MFMA, the weight loader
     mesh         csrc/hn_geometry.hip, csrc/hn_fusion.hip    lattice points, isosurface, components, compaction; depth
                                                              fusion into a TSDF volume, its observed faces
                  csrc/hn_mesh_distance.hip                   surface samples, the distance grid, nearest points of a mesh
@@ -13,6 +14,6 @@
 They import the binding (_lib), torch, numpy and each other, never functional, machine or arena: functional imports
 them and re-exports their public names.
 """
-from . import checks, data, gif, mesh, mesh_render, metrics, simplify
+from . import checks, data, gif, lpips, mesh, mesh_render, metrics, simplify
 
-__all__ = ["checks", "data", "gif", "mesh", "mesh_render", "metrics", "simplify"]
+__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "simplify"]

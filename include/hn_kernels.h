@@ -883,6 +883,39 @@ int hn_md_query(const float* points_dev, long long n, const int64_t* perm_dev, c
                 const float* cell_host, int rx, int ry, int rz, float max_distance, float* distance_dev, int32_t* face_dev,
                 float* closest_dev, hnStream_t stream);
 
+/* LPIPS v0.1 (csrc/hn_lpips.hip; DESIGN.md 3.14 holds the definition, tests/lpips_restated.py restates it in float64): the
+ * layers of the frozen AlexNet / VGG16 backbones and the distance head, exact fp32, one entry point per layer kind; the
+ * layer tables and the weights are the host's (ops/lpips/).  All tensors contiguous DEVICE fp32 unless said otherwise.
+ *   hn_lpips_prepare    out (2n, 3, h, w): images [0, n) from pred, [n, 2n) from gt (each (n, 3, h, w) with arbitrary
+ *                element strides, `*_strides`: HOST arrays of 4), every value ((2 v - 1) - shift_c) / scale_c with shift =
+ *                (-0.030, -0.088, -0.188), scale = (0.458, 0.448, 0.450).  net: 0 AlexNet (sides >= 31), 1 VGG16 (>= 16).
+ *   hn_lpips_conv       y (imgs, cout, oh, ow) = [relu](conv(x (imgs, cin, h, w)) + bias), square kernel 1 .. 15, zero
+ *                padding pad < kernel, o = (side + 2 pad - kernel) / stride + 1 (floor).  An implicit GEMM on
+ *                v_mfma_f32_32x32x2_f32: every output is one fmaf chain from 0 over k = (ci * kernel + ky) * kernel + kx
+ *                ascending, then + bias: the same bits for every tile shape, batch size and run.  wt: the weights
+ *                transposed and zero-padded, [Kpad][Mpad] with Kpad = K rounded up to 64, Mpad = cout rounded up to 128;
+ *                ktab: Kpad int32, ci << 8 | ky << 4 | kx of row k, -1 for a padding row.  tile: 0 picks the tile shape
+ *                (the largest of 128 x 128, 64 x 64, 32 x 64 (channels x pixels) whose grid has 256 workgroups), 1 / 2 / 3
+ *                force one.
+ *   hn_lpips_maxpool    y (planes, oh, ow) = max over kernel x kernel windows at stride `stride`, no padding, floor mode.
+ *   hn_lpips_distance   feat (2n, c, h, w), the two images of pair i at i and n + i; lin (c) weights;
+ *                out[i * 5 + layer] = mean over pixels of sum_c lin[c] * (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2,
+ *                |.| the root of the sum of squares over channels.  One workgroup and one partial sum per 64
+ *                pixels of a pair into `workspace` (hn_lpips_workspace_bytes: host arithmetic), a second launch adds a
+ *                pair's partial sums in a fixed order: no float atomics, bit-reproducible.  out: (n, 5), other columns
+ *                untouched.
+ * Status, before any launch: -2 for every refused argument (a NULL pointer, a size <= 0, a side below the net's minimum,
+ * a kernel above 15, more than 4096 channels, a tensor of more than 2^31 - 1 elements, n > 65535 pairs). */
+int hn_lpips_prepare(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int n,
+                     int h, int w, int net, float* out_dev, hnStream_t stream);
+int hn_lpips_conv(const float* x_dev, const float* wt_dev, const float* bias_dev, const int32_t* ktab_dev, float* y_dev,
+                  int imgs, int cin, int h, int w, int cout, int kernel, int stride, int pad, int relu, int tile,
+                  hnStream_t stream);
+int hn_lpips_maxpool(const float* x_dev, float* y_dev, int planes, int h, int w, int kernel, int stride, hnStream_t stream);
+int hn_lpips_workspace_bytes(int n, int h, int w, int64_t* bytes);
+int hn_lpips_distance(const float* feat_dev, const float* lin_dev, int n, int c, int h, int w, int layer, float* out_dev,
+                      void* workspace, hnStream_t stream);
+
 /* Background regularization (HyperNeRF's training loop; csrc/hn_regularizers.hip): static background points of the
  * capture go through the warp field under random warp embeddings and a robust loss pulls warp(p) back to p.
  *
