@@ -53,6 +53,14 @@ recall / F-score at thresholds; `distance_colors` turns per-vertex distances int
     mesh_distance(mesh, small, n_samples=1_000_000, thresholds=[0.01])    # what the simplification cost
     d = point_mesh_distance(small['vertices'], mesh)['distance']
     write_ply("error.ply", small['vertices'], small['faces'], colors=distance_colors(d, vmax=0.02))
+
+Meshes in different frames: the distance means something only once both meshes share a frame.  `register_mesh` finds the
+rigid or similarity transform that moves one onto the other by trimmed ICP (csrc/hn_registration.hip, DESIGN.md 3.15: the
+nearest points come from the same grid, the sums of each iteration from one fused, bit-reproducible reduction, the solve
+is float64 NumPy), `transform_mesh` applies it, and `aligned_mesh_distance` does both and then measures.
+
+    fit = register_mesh(scan, mesh, with_scale=True, trim=0.9, init='centroid')     # fit['matrix'] (4, 4), fit['rms']
+    aligned_mesh_distance(scan, mesh, register=dict(with_scale=True), thresholds=[0.01])
 """
 from __future__ import annotations
 
@@ -784,6 +792,184 @@ def mesh_distance(a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], n_samp
     if return_distances:
         out['distances_ab'], out['distances_ba'] = dists
     return out
+
+
+# ---- registration (csrc/hn_registration.hip) -----------------------------------------------------------------
+def _is_grid(x) -> bool:
+    return isinstance(x, dict) and 'cell_begin' in x
+
+
+def _int_arg(value, what: str, name: str, least: int) -> int:
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) < least:
+        raise ValueError(f"{what}: {name} must be an int >= {least}, got {value!r}")
+    return int(value)
+
+
+def _grid_corners(grid) -> torch.Tensor:
+    """(3 F, 3) fp32: the corners of a distance grid's packed triangles."""
+    return grid['tri'][:, :9].reshape(-1, 3)
+
+
+@torch.no_grad()
+def register_mesh(source, target, n_samples: int = 100_000, seed: int = 0, method: str = 'plane', with_scale: bool = False,
+                  trim: float = 1.0, max_distance: Optional[float] = None, init=None, max_iterations: int = 50,
+                  tol: float = 1e-5, grid_resolution=None) -> Dict:
+    """The similarity transform x -> s R x + t that moves `source` onto `target` by trimmed ICP.  source: a
+    mesh dict, sampled once (sample_surface(source, n_samples, seed)), or an (N, 3) fp32 point tensor; target: a mesh dict or
+    build_distance_grid's result (built once, queried in every iteration).  An iteration transforms the ORIGINAL samples
+    by the current transform (hn_reg_transform; the float64 transform is rounded to fp32 once per iteration, nothing
+    drifts), finds their nearest points on the target (ops.mesh.grid_query with max_distance), keeps the share `trim` (0 <
+    trim <= 1) of them with the smallest distances (ops.registration.trim_threshold), sums what the solve needs on the
+    device (hn_reg_moments: fused, float64, the same bits on every run), reads the 38 sums (the iteration's one host read)
+    and solves in float64 NumPy: method 'point' the closed form of Umeyama / Horn, 'plane' one Gauss-Newton step of the
+    point-to-plane error by minimum-norm least squares; with_scale also fits s.  The step (s', R', t') composes as
+    s <- s' s, R <- R' R, t <- s' R' t + t'.  It stops when the UPDATE is small — the angle of R' <= tol rad, |t'| <= tol *
+    (the diagonal of the target's box) and |s' - 1| <= tol — or after max_iterations.  init: None (identity), a (4, 4)
+    similarity matrix, or 'centroid' (the samples' centroid onto that of n_samples surface samples of the target, seed + 1;
+    with with_scale also the ratio of their rms radii).  ICP converges to the nearest local minimum: it needs an init within
+    reach, a symmetric shape has several answers, and 'point' creeps along smooth surfaces where 'plane' slides.
+    {'matrix': (4, 4) float64, 'scale', 'rotation' (3, 3), 'translation' (3,), 'rms': sqrt(sum d^2 / n) of the last inlier
+    set, 'inliers', 'iterations', 'converged', 'history': [{'rms', 'inliers'}] per iteration}.  ValueError: an empty mesh or
+    point set, arguments out of range, an init that is no similarity (det <= 0, a non-uniform scale), fewer than 3 inliers
+    (6 for 'plane', 7 with scale) in an iteration."""
+    what = "register_mesh"
+    R = ops.registration
+    if isinstance(source, torch.Tensor):
+        samples, src_mesh = ops.checks.check_points(source, what, "source"), None
+        if samples.shape[0] == 0:
+            raise ValueError(f"{what}: the source holds no points")
+    else:
+        samples, src_mesh = None, _mesh_arrays(source, what)
+        if src_mesh[1].shape[0] == 0 or src_mesh[0].shape[0] == 0:
+            raise ValueError(f"{what}: the source mesh has no faces")
+    if _is_grid(target):
+        try:
+            target_faces = int(target['num_faces'])
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"{what}: target must be a mesh dict or what build_distance_grid returned") from None
+        if target_faces == 0:
+            raise ValueError(f"{what}: the target mesh has no faces")
+    else:
+        tv, tf = _mesh_arrays(target, what)
+        if tf.shape[0] == 0 or tv.shape[0] == 0:
+            raise ValueError(f"{what}: the target mesh has no faces")
+    n_samples = _int_arg(n_samples, what, "n_samples", 1)
+    if n_samples > ops.checks.INT32_MAX:
+        raise ValueError(f"{what}: n_samples must be at most 2**31 - 1, got {n_samples}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"{what}: seed must be an int, got {seed!r}")
+    if method not in R.REG_MODES:
+        raise ValueError(f"{what}: method must be 'point' or 'plane', got {method!r}")
+    with_scale = bool(with_scale)
+    try:
+        trim_f, tol_f = float(trim), float(tol)
+    except (TypeError, ValueError):
+        trim_f = tol_f = float("nan")
+    if not 0.0 < trim_f <= 1.0:
+        raise ValueError(f"{what}: trim must be a number in (0, 1], got {trim!r}")
+    if not (tol_f > 0.0 and np.isfinite(tol_f)):
+        raise ValueError(f"{what}: tol must be a positive finite number, got {tol!r}")
+    ops.mesh.check_max_distance(max_distance, what)
+    max_iterations = _int_arg(max_iterations, what, "max_iterations", 1)
+    if grid_resolution is not None:
+        ops.mesh.check_grid_resolution(grid_resolution, what)
+    if init is None:
+        current = (1.0, np.eye(3), np.zeros(3))
+    elif isinstance(init, str):
+        if init != 'centroid':
+            raise ValueError(f"{what}: init must be None, 'centroid' or a (4, 4) similarity matrix, got {init!r}")
+        current = None
+    else:
+        current = R.check_similarity(init, what)
+
+    if samples is None:
+        samples = sample_surface(source, n_samples, int(seed))['points']
+    L.require_gpu(samples)
+    grid = target if _is_grid(target) else build_distance_grid(target, grid_resolution)
+    corners = _grid_corners(grid).double()
+    ok = torch.isfinite(corners).all(dim=1, keepdim=True)
+    box = torch.stack([torch.where(ok, corners, torch.full_like(corners, float("inf"))).amin(0),
+                       torch.where(ok, corners, torch.full_like(corners, float("-inf"))).amax(0)])
+    if current is None:
+        # 'centroid': the moments of both samples about the origin in float64, one host read with the box
+        tgt = sample_surface({'vertices': _grid_corners(grid).contiguous(),
+                              'faces': torch.arange(3 * grid['num_faces'], dtype=torch.int32, device=samples.device).reshape(-1, 3)},
+                             n_samples, int(seed) + 1)['points'].double()
+        src = samples.double()
+        src = src[torch.isfinite(src).all(dim=1)]
+        if src.shape[0] == 0:
+            raise ValueError(f"{what}: the source holds no finite point")
+        stats = torch.stack([box[0], box[1], src.mean(0), tgt.mean(0), (src * src).sum(1).mean().expand(3),
+                             (tgt * tgt).sum(1).mean().expand(3)]).cpu().numpy()
+        c_src, c_tgt = stats[2], stats[3]
+        r_src, r_tgt = (float(np.sqrt(max(m2 - float(c @ c), 0.0))) for m2, c in ((stats[4][0], c_src), (stats[5][0], c_tgt)))
+        s0 = r_tgt / r_src if with_scale and r_src > 0.0 and r_tgt > 0.0 else 1.0
+        current = (s0, np.eye(3), c_tgt - s0 * c_src)
+    else:
+        stats = box.cpu().numpy()
+    diagonal = float(np.linalg.norm(stats[1] - stats[0]))
+
+    need = R.REG_MIN_INLIERS[(method, with_scale)]
+    history, converged, iterations = [], False, 0
+    for iterations in range(1, max_iterations + 1):
+        moved = R.transform_points(samples, *current)
+        query = ops.mesh.grid_query(moved, grid, max_distance)
+        tau = R.trim_threshold(query['distance'], trim_f)
+        sums = R.registration_moments(moved, query, grid['tri'], tau, method).cpu().numpy()      # the iteration's host read
+        inliers = int(sums[0])
+        if inliers < need:
+            raise ValueError(f"{what}: iteration {iterations} has {inliers} inliers, fewer than the {need} that method "
+                             f"{method!r}{' with scale' if with_scale else ''} solves from (max_distance {max_distance!r}, "
+                             f"trim {trim!r})")
+        rms = float(np.sqrt(sums[1] / inliers))
+        history.append({'rms': rms, 'inliers': inliers})
+        step = (R.solve_point if method == 'point' else R.solve_plane)(sums, with_scale)
+        if not (np.isfinite(step[0]) and step[0] > 0.0 and np.isfinite(step[1]).all() and np.isfinite(step[2]).all()):
+            raise ValueError(f"{what}: iteration {iterations} has no finite solution (its {inliers} inliers are degenerate)")
+        current = R.compose_similarity(step, current)
+        if (R.rotation_angle(step[1]) <= tol_f and float(np.linalg.norm(step[2])) <= tol_f * diagonal
+                and abs(step[0] - 1.0) <= tol_f):
+            converged = True
+            break
+    s, rot, t = current
+    return {'matrix': R.similarity_matrix(s, rot, t), 'scale': float(s), 'rotation': np.array(rot), 'translation': np.array(t),
+            'rms': history[-1]['rms'], 'inliers': history[-1]['inliers'], 'iterations': iterations, 'converged': converged,
+            'history': history}
+
+
+@torch.no_grad()
+def transform_mesh(mesh: Dict[str, torch.Tensor], matrix) -> Dict[str, torch.Tensor]:
+    """`mesh` moved by the (4, 4) similarity `matrix` (register_mesh's 'matrix'): the vertices through hn_reg_transform, the
+    'normals', where the mesh has some, through its direction form (rotated, unit length; a zero normal stays zero); the
+    faces, colours and every other key are carried over as they are.  ValueError: a matrix that is no similarity (det <= 0
+    would turn the faces inside out)."""
+    what = "transform_mesh"
+    vertices, _ = _mesh_arrays(mesh, what)
+    s, rot, t = ops.registration.check_similarity(matrix, what)
+    normals = mesh.get('normals')
+    if normals is not None:
+        normals = ops.checks.check_points(normals, what, "normals", rows=vertices.shape[0])
+    out = dict(mesh)
+    out['vertices'] = ops.registration.transform_points(vertices, s, rot, t)
+    if normals is not None:
+        out['normals'] = ops.registration.transform_points(normals, 1.0, rot, np.zeros(3), direction=True)
+    return out
+
+
+@torch.no_grad()
+def aligned_mesh_distance(a: Dict[str, torch.Tensor], b: Dict[str, torch.Tensor], register: Optional[Dict] = None,
+                          **mesh_distance_kwargs) -> Dict:
+    """mesh_distance after registration: register_mesh(a, b, **register), transform_mesh(a, its matrix), mesh_distance(the
+    moved a, b, **mesh_distance_kwargs).  The report of mesh_distance plus 'alignment': register_mesh's result."""
+    what = "aligned_mesh_distance"
+    _mesh_arrays(a, what)
+    _mesh_arrays(b, what)
+    if register is not None and not isinstance(register, dict):
+        raise ValueError(f"{what}: register must be a dict of register_mesh's keyword arguments or None, got {register!r}")
+    alignment = register_mesh(a, b, **(register or {}))
+    report = mesh_distance(transform_mesh(a, alignment['matrix']), b, **mesh_distance_kwargs)
+    report['alignment'] = alignment
+    return report
 
 
 @torch.no_grad()

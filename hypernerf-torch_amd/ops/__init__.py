@@ -5,6 +5,8 @@
     mesh         csrc/hn_geometry.hip, csrc/hn_fusion.hip    lattice points, isosurface, components, compaction; depth
                                                              fusion into a TSDF volume, its observed faces
                  csrc/hn_mesh_distance.hip                   surface samples, the distance grid, nearest points of a mesh
+    registration csrc/hn_registration.hip                    similarity transform of points, the sums an ICP iteration
+                                                             solves from, both solves
     simplify     csrc/hn_simplify.hip                        vertex clustering
     mesh_render  csrc/hn_mesh_render.hip                     projection, binning, ray casting, shading
     data         csrc/hn_data.hip                            ray generation, batch gathers, blend, Pillow-exact resize
@@ -14,6 +16,6 @@
 They import the binding (_lib), torch, numpy and each other, never functional, machine or arena: functional imports
 them and re-exports their public names.
 """
-from . import checks, data, gif, lpips, mesh, mesh_render, metrics, simplify
+from . import checks, data, gif, lpips, mesh, mesh_render, metrics, registration, simplify
 
-__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "simplify"]
+__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "registration", "simplify"]

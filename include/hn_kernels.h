@@ -883,6 +883,34 @@ int hn_md_query(const float* points_dev, long long n, const int64_t* perm_dev, c
                 const float* cell_host, int rx, int ry, int rz, float max_distance, float* distance_dev, int32_t* face_dev,
                 float* closest_dev, hnStream_t stream);
 
+/* Mesh registration (csrc/hn_registration.hip; DESIGN.md 3.15 holds the definition, tests/registration_restated.py restates
+ * it in NumPy, bit for bit): the two kernels of an ICP iteration around hn_md_query.
+ *   hn_reg_transform    out (n, 3) fp32 = s * (R p) + t for points (n, 3) fp32; params_host: 13 HOST floats, R row-major (9),
+ *                s, t (3), all finite.  Every fp32 operation is rounded on its own: row_i = (R_i0*x + R_i1*y) + R_i2*z,
+ *                out_i = row_i * s + t_i.  direction = 1: no s, no t, out = row / sqrtf(dot(row, row)), row itself unless
+ *                the length is > 0 (a zero vector stays zero).  A point that is not finite gives NaN, NaN, NaN.
+ *   hn_reg_moments      the sums one iteration solves from, over the inliers of points (n, 3) fp32 with hn_md_query's closest
+ *                (n, 3), distance (n) and face (n): point k is an inlier when distance[k] is finite and <= tau[0] (one
+ *                DEVICE fp32), 0 <= face[k] < n_faces and, with mode 1, the packed triangle tri[face[k]] (tri (F, 12) fp32
+ *                of hn_md_pack) has a normal of positive finite length; nothing else is read into a sum.  Doubles from
+ *                the fp32 inputs, every double operation rounded on its own, dot(u, v) = (ux*vx + uy*vy) + uz*vz.
+ *                mode 0 (point to point), 19 values: count, sum d^2, sum p (3), sum q (3), sum q_i p_j (9, index 3 i + j),
+ *                sum dot(p, p), sum dot(q, q).  mode 1 (point to plane), 38 values: count, sum d^2, sum r^2, the upper
+ *                triangle of J^T J by rows (28), J^T r (7), with n = m / sqrt(dot(m, m)), m = (B - A) x (C - A),
+ *                r = dot(p - q, n), J = [p x n, n, dot(p, n)].  sums (38) doubles, the unused tail 0; partials
+ *                (n_blocks, 38) doubles of workspace.  n_blocks workgroups (1 .. 1024) of 256 threads: a thread adds its
+ *                points k = g, g + 256 n_blocks, ... in order, a wave folds its lanes by halves, a workgroup adds its
+ *                waves as (w0 + w1) + (w2 + w3), a second launch adds the partials in block order.  No atomics: the
+ *                result is a function of the inputs, n and n_blocks, the same bits on every run.
+ * Status, before any launch: -2 for a size out of range (n or n_faces <= 0 or above 2^31 - 1, n_blocks outside 1 .. 1024, a
+ * mode or direction that is neither 0 nor 1, params_host NULL or not finite), -3 for a NULL device pointer that must not be
+ * (tri may be NULL with mode 0). */
+int hn_reg_transform(const float* points_dev, long long n, const float* params_host, int direction, float* out_dev,
+                     hnStream_t stream);
+int hn_reg_moments(const float* points_dev, const float* closest_dev, const float* distance_dev, const int32_t* face_dev,
+                   long long n, const float* tri_dev, long long n_faces, const float* tau_dev, int mode, int n_blocks,
+                   double* partials_dev, double* sums_dev, hnStream_t stream);
+
 /* LPIPS v0.1 (csrc/hn_lpips.hip; DESIGN.md 3.14 holds the definition, tests/lpips_restated.py restates it in float64): the
  * layers of the frozen AlexNet / VGG16 backbones and the distance head, exact fp32, one entry point per layer kind; the
  * layer tables and the weights are the host's (ops/lpips/).  All tensors contiguous DEVICE fp32 unless said otherwise.
