@@ -28,6 +28,7 @@ from .ops.mesh_render import *              # noqa: F401,F403
 from .ops.metrics import *                  # noqa: F401,F403
 from .ops.registration import *             # noqa: F401,F403
 from .ops.simplify import *                 # noqa: F401,F403
+from .ops.texture import *                  # noqa: F401,F403
 
 _PRECISION = os.environ.get("HN_PRECISION", "bf16")
 

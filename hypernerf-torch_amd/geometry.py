@@ -61,6 +61,18 @@ is float64 NumPy), `transform_mesh` applies it, and `aligned_mesh_distance` does
 
     fit = register_mesh(scan, mesh, with_scale=True, trim=0.9, init='centroid')     # fit['matrix'] (4, 4), fit['rms']
     aligned_mesh_distance(scan, mesh, register=dict(with_scale=True), thresholds=[0.01])
+
+Taking a mesh out with its appearance: after simplify_mesh a colour per vertex keeps little of what the field knows.
+`texture_atlas` gives every face a chart in one image (csrc/hn_texture.hip, DESIGN.md 3.16: two faces to a power-of-two
+cell, cells packed in Z-order, no host loop over faces), `rasterize_atlas` turns its texels into points and normals,
+`bake_field_texture` asks the field for their colours, `render_textured_mesh` puts the texture back on the rendered
+mesh and `write_obj` writes mesh, UVs and the image for a viewer.
+
+    small = simplify_mesh(mesh, cell=0.02)
+    atlas = texture_atlas(small, atlas_texel_for_size(small, 4096), max_size=4096)
+    texture = bake_field_texture(model, small, atlas, frame_id=12)        # (H_t, W_t, 3) uint8
+    img = render_textured_mesh(small, atlas, texture, rays, cam, (W, H))
+    write_obj("frame12.obj", small, atlas, texture)                        # + frame12.mtl, frame12.png
 """
 from __future__ import annotations
 
@@ -1074,3 +1086,271 @@ def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
     normals = table[:, 3:6].copy() if names[3:6] == ["nx", "ny", "nz"] else None
     return {"vertices": table[:, :3].copy(), "normals": normals, "faces": rec["idx"].astype(np.int32).reshape(nf, 3),
             "colors": vrec["c"].reshape(nv, 3).copy() if has_colors else None}
+
+
+# ---- taking a mesh out with its appearance: a texture atlas baked from the field (csrc/hn_texture.hip) ---
+def _check_atlas_mesh(mesh, what: str):
+    """(vertices, faces, normals) of a mesh dict on one GPU, or ValueError."""
+    vertices, faces, normals, _ = _check_render_mesh(mesh, what)
+    if not vertices.is_cuda or not faces.is_cuda or (normals is not None and not normals.is_cuda):
+        raise ValueError(f"{what}: the mesh must live on the GPU (there is no CPU fallback)")
+    if faces.device != vertices.device or (normals is not None and normals.device != vertices.device):
+        raise ValueError(f"{what}: the mesh's tensors must live on one device")
+    return vertices, faces, normals
+
+
+@torch.no_grad()
+def texture_atlas(mesh: Dict[str, torch.Tensor], texel: float, min_cell: int = 16, max_cell: int = 256,
+                  max_size: int = 8192) -> Dict:
+    """A texture atlas of the mesh with one chart per face, texels of length `texel`: {'uv': (F, 3, 2) fp32,
+    the corners of every face in absolute texel coordinates (texel (i, j) has its centre at (i + 0.5, j + 0.5)), 'size':
+    (W_t, H_t), 'cell_start': (n_cells, 2) int32, 'cell_side': (n_cells,) int32, 'cell_face': (n_cells, 2) int32 (-1: an
+    empty half), 'texel', and 'min_cell' / 'class_cells', the cells per side that rasterize_atlas finds a texel's cell
+    with} on the mesh's device.
+    A face gets the smallest power-of-two cell side s in [min_cell, max_cell] whose L = s - 7 texels cover its longest edge
+    (max_cell when none does: such a face is sampled more coarsely than `texel`); two faces share a square cell as the
+    two right triangles of legs L along its diagonal, a 1.5-texel gutter around each, so that a bilinear fetch inside a
+    chart never reads another face's texels.  Cells are packed by descending side in Z-order, without holes; W_t =
+    min_cell * 2^m, H_t = W_t or W_t / 2.  Deterministic: a sort of unique keys, no atomics.  One host read.
+    ValueError: cell sides that are no powers of two in 16 .. 1024; texel not positive and finite; max_size above 16384; an
+    atlas wider than max_size (the message names the size needed); a face with a vertex id outside [0, V)."""
+    what = "texture_atlas"
+    if not isinstance(mesh, dict):
+        raise ValueError(f"{what}: mesh must be a dict with 'vertices' and 'faces'")
+    min_cell, max_cell = ops.texture.check_cells_arg(min_cell, max_cell, what)
+    texel = ops.texture.check_texel(texel, what)
+    max_size = ops.texture.check_max_size(max_size, what)
+    vertices, faces, _ = _check_atlas_mesh(mesh, what)
+    dev, n_faces = vertices.device, faces.shape[0]
+    if n_faces == 0:
+        hist = [0] * 11
+        empty = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)      # noqa: E731
+        cell_start, cell_side, cell_face = empty(0, 2), empty(0), empty(0, 2)
+        uv = torch.zeros((0, 3, 2), dtype=torch.float32, device=dev)
+    else:
+        _, keys, hist = ops.texture.face_classes(vertices, faces, texel, min_cell, max_cell, what)
+    size = ops.texture.check_atlas_fits(hist, min_cell, max_size, what)
+    if n_faces:
+        cell_start, cell_side, cell_face, uv = ops.texture.atlas_layout(keys, hist, min_cell)
+    return {'uv': uv, 'size': size, 'cell_start': cell_start, 'cell_side': cell_side, 'cell_face': cell_face,
+            'texel': texel, 'min_cell': min_cell, 'class_cells': tuple(ops.texture.class_cells(hist)[1])}
+
+
+@torch.no_grad()
+def atlas_texel_for_size(mesh: Dict[str, torch.Tensor], size: int, min_cell: int = 16, max_cell: int = 256) -> float:
+    """The finest texel length of the ladder texel_k = 2^(k/2) * (longest bounding-box side / size), k = 0, 1, 2, ..., whose
+    texture_atlas fits size x size.  One face classification and one host read of 12 ints per step, at most 64 steps.
+    ValueError: a mesh without faces or without extent; a mesh that does not fit even with every face in a min_cell chart."""
+    what = "atlas_texel_for_size"
+    if not isinstance(mesh, dict):
+        raise ValueError(f"{what}: mesh must be a dict with 'vertices' and 'faces'")
+    min_cell, max_cell = ops.texture.check_cells_arg(min_cell, max_cell, what)
+    size = ops.texture.check_max_size(size, what, "size")
+    vertices, faces, _ = _check_atlas_mesh(mesh, what)
+    if faces.shape[0] == 0 or vertices.shape[0] == 0:
+        raise ValueError(f"{what}: the mesh has no faces")
+    lo, hi = (np.asarray(t, dtype=np.float64) for t in ops.simplify.vertex_extent(vertices))
+    longest = float((hi - lo).max()) if np.isfinite(lo).all() and np.isfinite(hi).all() else 0.0
+    if not longest > 0.0:
+        raise ValueError(f"{what}: the vertices have no finite extent")
+    need = None
+    for k in range(64):
+        texel = ops.texture.check_texel(2.0 ** (0.5 * k) * longest / size, what)
+        hist = ops.texture.face_classes(vertices, faces, texel, min_cell, max_cell, what)[2]
+        need = ops.texture.atlas_size(hist, min_cell)
+        if max(need) <= size:
+            return texel
+        if hist[min_cell.bit_length() - 1] == faces.shape[0]:
+            break
+    raise ValueError(f"{what}: the mesh needs {need[0]} x {need[1]} texels even with every face in a {min_cell}-texel cell; "
+                     f"size is {size}")
+
+
+@torch.no_grad()
+def rasterize_atlas(mesh: Dict[str, torch.Tensor], atlas: Dict) -> Dict[str, torch.Tensor]:
+    """The atlas texels in 3-D: {'owner': (H_t, W_t) int32, the face whose chart owns the texel or -1, 'position': (H_t, W_t,
+    3) fp32, the point of the face's plane under the texel centre — extrapolated outside the triangle, so that bilinear
+    sampling reproduces an affine function exactly up to the face's edges —, 'normal': (H_t, W_t, 3) fp32, the unit
+    interpolated vertex normal there (the face normal without 'normals' or where the interpolation vanishes)}; zeros at
+    unowned texels (hn_tex_rasterize)."""
+    what = "rasterize_atlas"
+    vertices, faces, normals = _check_atlas_mesh(mesh, what)
+    ops.texture.check_atlas(atlas, faces.shape[0], what)
+    return ops.texture.atlas_rasterize(vertices, faces, normals, atlas)
+
+
+@torch.no_grad()
+def bake_texture(mesh: Dict[str, torch.Tensor], atlas: Dict, color_fn, dtype=torch.uint8, fill=0) -> torch.Tensor:
+    """The (H_t, W_t, 3) texture of the atlas whose owned texels hold color_fn(points (n, 3), normals (n, 3)) -> (n, 3) fp32
+    in [0, 1], called ONCE on the owned texels of rasterize_atlas in row-major order; unowned texels hold `fill`.
+    dtype float32: the colours as they are; uint8: (rgb * 255) truncated, the convention of vertex_colors."""
+    what = "bake_texture"
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{what}: dtype must be torch.uint8 or torch.float32, got {dtype}")
+    try:
+        given, fill = float(fill), (float(fill) if dtype == torch.float32 else int(fill))
+        ok = bool(np.isfinite(given)) if dtype == torch.float32 else (0 <= fill <= 255 and fill == given)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: fill must be one {'finite number' if dtype == torch.float32 else 'integer in 0 .. 255'}")
+    if not callable(color_fn):
+        raise ValueError(f"{what}: color_fn must be callable")
+    rast = rasterize_atlas(mesh, atlas)
+    (w, h), dev = atlas['size'], rast['owner'].device
+    index = torch.nonzero(rast['owner'].view(-1) >= 0).view(-1)
+    n = index.shape[0]
+    texture = torch.full((h, w, 3), fill, dtype=dtype, device=dev)
+    colors = color_fn(rast['position'].view(-1, 3)[index], rast['normal'].view(-1, 3)[index])
+    if not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (n, 3) or colors.dtype != torch.float32 \
+            or colors.device != dev:
+        raise ValueError(f"{what}: color_fn must return a ({n}, 3) float32 tensor on {dev}")
+    texture.view(-1, 3)[index] = colors if dtype == torch.float32 else (colors * 255).to(torch.uint8)
+    return texture
+
+
+@torch.no_grad()
+def bake_field_texture(model, mesh: Dict[str, torch.Tensor], atlas: Dict, frame_id: int,
+                       view: Union[str, Sequence[float], torch.Tensor] = 'normal', level: str = 'fine', chunk: int = 1 << 20,
+                       render_opts=None, dtype=torch.uint8) -> torch.Tensor:
+    """bake_texture with the field's colour at frame `frame_id`: vertex_colors(model, points, normals, frame_id, view=...) at
+    every owned texel's point, seen along -normal or from the camera position `view`.  The mesh lives on the model's
+    device.  The values do not depend on `chunk`; model._level_state is left as found."""
+    if int(chunk) < 1:
+        raise ValueError(f"bake_field_texture: chunk must be positive, got {chunk}")
+
+    def color_fn(points, normals):
+        return vertex_colors(model, points, normals, frame_id, view=view, level=level, chunk=chunk, render_opts=render_opts,
+                             dtype=torch.float32)
+    return bake_texture(mesh, atlas, color_fn, dtype=dtype)
+
+
+@torch.no_grad()
+def render_textured_mesh(mesh: Dict[str, torch.Tensor], atlas: Dict, texture: torch.Tensor, rays: torch.Tensor, camera,
+                         image_wh, shading: str = 'headlight', ambient: float = 0.3, background=(1.0, 1.0, 1.0),
+                         filter: str = 'bilinear', binning: bool = True) -> Dict[str, torch.Tensor]:
+    """render_mesh with the colour from a texture: the same keys and shapes, the same face / depth / bary / normal images
+    (ops.mesh_render.mesh_trace), and rgb / rgb8 from `texture` (H_t, W_t, 3) uint8 or fp32 fetched at the hit point's atlas
+    coordinates (hn_tex_shade), filter 'bilinear' or 'nearest'; the mesh's 'colors' are not looked at.  No mip levels: a
+    minified texture aliases.  One chart per face: magnified bilinear filtering does not blend across face edges."""
+    what = "render_textured_mesh"
+    vertices, faces, normals, _ = _check_render_mesh(mesh, what)
+    w, h = ops.mesh_render.check_image_wh(image_wh, what)
+    camera = ops.checks.check_camera(camera, what)
+    rays = ops.checks.check_rays(rays, h * w, what)
+    ops.mesh_render.check_shading(shading, ambient, background, (0.0, 0.0, 0.0), what)
+    ops.texture.check_atlas(atlas, faces.shape[0], what)
+    texture = ops.texture.check_texture(texture, atlas, what)
+    if filter not in ops.texture.TEX_FILTERS:
+        raise ValueError(f"{what}: filter must be one of {tuple(ops.texture.TEX_FILTERS)}, got {filter!r}")
+    if not vertices.is_cuda or not faces.is_cuda or not rays.is_cuda or not texture.is_cuda:
+        raise ValueError(f"{what}: the mesh, the texture and the rays must live on the GPU (there is no CPU fallback)")
+    out = ops.mesh_render.mesh_trace(vertices, faces, rays, camera, (w, h), binning=bool(binning))
+    out.update(ops.texture.texture_shade(vertices, faces, normals, atlas, texture, rays, out['face'], out['bary'], shading,
+                                         ambient, background, filter))
+    return {k: t.view((h, w) + tuple(t.shape[1:])) for k, t in out.items()}
+
+
+def write_obj(path, mesh: Dict, atlas: Dict, texture) -> None:
+    """A textured Wavefront OBJ: `name.obj` (path), `name.mtl` and `name.png` beside it.  The .obj holds `mtllib`, `v` per
+    vertex, `vn` per vertex when the mesh has 'normals', three `vt` per face — u = x / W_t, v = 1 - y / H_t of atlas['uv'],
+    exact in the decimal digits written — `usemtl` and `f a/ta/na b/tb/nb c/tc/nc` (`a/ta` without normals), 1-based; the
+    .mtl one material with `map_Kd name.png`; the .png the texture (H_t, W_t, 3) uint8 through inference.write_png, row 0
+    on top.  Tensors or arrays, host or device.  ValueError: a path that does not end in .obj, a texture that is not
+    uint8 or not of the atlas's size, a uv table that is not (F, 3, 2)."""
+    import os
+    from . import inference
+    what = "write_obj"
+    path = os.fspath(path)
+    if not path.lower().endswith(".obj"):
+        raise ValueError(f"{what}: path must end in .obj, got {path!r}")
+    if not isinstance(mesh, dict) or not isinstance(atlas, dict) or 'uv' not in atlas or 'size' not in atlas:
+        raise ValueError(f"{what}: mesh must be a mesh dict and atlas the dict texture_atlas returns")
+    tex = texture.detach().cpu().numpy() if isinstance(texture, torch.Tensor) else np.asarray(texture)
+    if tex.dtype != np.uint8:
+        raise ValueError(f"{what}: texture must be uint8 (bake with dtype=torch.uint8), got {tex.dtype}")
+    w, h = (int(x) for x in atlas['size'])
+    if tex.shape != (h, w, 3):
+        raise ValueError(f"{what}: texture is {tuple(tex.shape)}, the atlas is ({h}, {w}, 3)")
+    v = _host(mesh['vertices'], np.float32).reshape(-1, 3)
+    f = _host(mesh['faces'], np.int32).reshape(-1, 3)
+    uv = _host(atlas['uv'], np.float32)
+    if uv.shape != (f.shape[0], 3, 2):
+        raise ValueError(f"{what}: the atlas lays out {uv.shape[0]} faces, the mesh has {f.shape[0]}")
+    nrm = mesh.get('normals')
+    if nrm is not None:
+        nrm = _host(nrm, np.float32).reshape(-1, 3)
+        if nrm.shape != v.shape:
+            raise ValueError(f"{what}: {nrm.shape[0]} normals for {v.shape[0]} vertices")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"{what}: faces hold a vertex id outside [0, {v.shape[0]})")
+    base = path[:-4]
+    name = os.path.basename(base)
+    # float32 survives nine significant digits; u and v are dyadic in float64 when the sides are powers of two
+    lines = [f"mtllib {name}.mtl"]
+    lines += ["v %.9g %.9g %.9g" % tuple(r) for r in v.tolist()]
+    if nrm is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(r) for r in nrm.tolist()]
+    u64 = uv.reshape(-1, 2).astype(np.float64)
+    lines += ["vt %.17g %.17g" % (x / w, 1.0 - y / h) for x, y in u64.tolist()]
+    lines.append(f"usemtl {name}")
+    corner = "%d/%d/%d" if nrm is not None else "%d/%d"
+    for k, (a, b, c) in enumerate(f.tolist()):
+        ids = ((a + 1, 3 * k + 1, a + 1), (b + 1, 3 * k + 2, b + 1), (c + 1, 3 * k + 3, c + 1))
+        lines.append("f " + " ".join(corner % (t if nrm is not None else t[:2]) for t in ids))
+    with open(path, "w", encoding="ascii") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(base + ".mtl", "w", encoding="ascii") as fh:
+        fh.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    inference.write_png(base + ".png", tex)
+
+
+def read_obj(path) -> Dict:
+    """What write_obj wrote: {'vertices': (V, 3) float32, 'normals': (V, 3) float32 | None, 'faces': (F, 3) int32, 'vt':
+    (F, 3, 2) float64 as written, 'uv': (F, 3, 2) float32, vt mapped back to texel coordinates (u W_t, (1 - v) H_t),
+    'texture': (H_t, W_t, 3) uint8, 'size': (W_t, H_t), 'mtl': the .mtl's file name, 'map_Kd': the image's file name}.  Standard
+    library and NumPy only."""
+    import os
+    from . import inference
+    what = "read_obj"
+    path = os.fspath(path)
+    v, vn, vt, faces, mtl, used = [], [], [], [], None, None
+    with open(path, "r", encoding="ascii") as fh:
+        for line in fh:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "v":
+                v.append([float(x) for x in w[1:4]])
+            elif w[0] == "vn":
+                vn.append([float(x) for x in w[1:4]])
+            elif w[0] == "vt":
+                vt.append([float(x) for x in w[1:3]])
+            elif w[0] == "f":
+                faces.append([[int(x) for x in c.split("/")] for c in w[1:]])
+            elif w[0] == "mtllib":
+                mtl = w[1]
+            elif w[0] == "usemtl":
+                used = w[1]
+    n_f = len(faces)
+    corners = np.asarray(faces, dtype=np.int64).reshape(n_f, 3, -1) if n_f else np.zeros((0, 3, 3 if vn else 2), dtype=np.int64)
+    if mtl is None or used is None or len(vt) != 3 * n_f or corners.shape[2] != (3 if vn else 2) \
+            or not (corners[:, :, 1].reshape(-1) == np.arange(1, 3 * n_f + 1)).all() \
+            or (vn and (len(vn) != len(v) or not (corners[:, :, 2] == corners[:, :, 0]).all())):
+        raise ValueError(f"{what}: {path} has a layout write_obj does not write")
+    image = None
+    with open(os.path.join(os.path.dirname(path), mtl), "r", encoding="ascii") as fh:
+        for line in fh:
+            w = line.split()
+            if w[:1] == ["map_Kd"]:
+                image = w[1]
+    if image is None:
+        raise ValueError(f"{what}: {mtl} names no map_Kd image")
+    texture = inference.read_png(os.path.join(os.path.dirname(path), image))
+    h_t, w_t = texture.shape[:2]
+    vt = np.asarray(vt, dtype=np.float64).reshape(n_f, 3, 2)
+    uv = np.stack([vt[..., 0] * w_t, (1.0 - vt[..., 1]) * h_t], axis=-1).astype(np.float32)
+    return {"vertices": np.asarray(v, dtype=np.float32).reshape(-1, 3),
+            "normals": np.asarray(vn, dtype=np.float32).reshape(-1, 3) if vn else None,
+            "faces": (corners[:, :, 0] - 1).astype(np.int32), "vt": vt, "uv": uv, "texture": texture, "size": (w_t, h_t),
+            "mtl": mtl, "map_Kd": image}

@@ -8,6 +8,8 @@
     registration csrc/hn_registration.hip                    similarity transform of points, the sums an ICP iteration
                                                              solves from, both solves
     simplify     csrc/hn_simplify.hip                        vertex clustering
+    texture      csrc/hn_texture.hip                         texture atlas: face classes, cell layout, texel rasteriser,
+                                                             textured shading
     mesh_render  csrc/hn_mesh_render.hip                     projection, binning, ray casting, shading
     data         csrc/hn_data.hip                            ray generation, batch gathers, blend, Pillow-exact resize
     gif          csrc/hn_gif.hip                             colour histogram, palette map, LZW, depth colour map
@@ -16,6 +18,6 @@
 They import the binding (_lib), torch, numpy and each other, never functional, machine or arena: functional imports
 them and re-exports their public names.
 """
-from . import checks, data, gif, lpips, mesh, mesh_render, metrics, registration, simplify
+from . import checks, data, gif, lpips, mesh, mesh_render, metrics, registration, simplify, texture
 
-__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "registration", "simplify"]
+__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "registration", "simplify", "texture"]

@@ -911,6 +911,55 @@ int hn_reg_moments(const float* points_dev, const float* closest_dev, const floa
                    long long n, const float* tri_dev, long long n_faces, const float* tau_dev, int mode, int n_blocks,
                    double* partials_dev, double* sums_dev, hnStream_t stream);
 
+/* Texture atlas (csrc/hn_texture.hip; DESIGN.md 3.16 holds the definition, tests/texture_restated.py restates it in NumPy
+ * float32): one chart per face, two faces to a square cell of power-of-two side s (16 .. 1024), cells packed in Z-order.
+ * Vertices (V, 3) fp32, faces (F, 3) int32; every fp32 operation rounded on its own.  L = s - 7.
+ *   hn_tex_classify   per face: class[f] (int32) = log2(s) of the smallest s in [min_cell, max_cell] with m <= (L*texel)^2, m the
+ *                largest squared edge length ((dx*dx + dy*dy) + dz*dz); max_cell when none does.  keys[f] (int64) =
+ *                (10 - class) << 32 | f: ascending keys are descending sides, ascending face ids.  A face with an id outside
+ *                [0, V) gets min_cell and stores 1 into err[0] (int32, zeroed by the caller).
+ *   hn_tex_layout     from the sorted keys: class_rank_host = 8 HOST int64, the first sorted rank of side 1024 >> q for q = 0 ..
+ *                6, then F.  Side s with ranks r0 .. r1 has ceil((r1 - r0) / 2) cells, cell j holding rank r0 + 2j (lower
+ *                half) and r0 + 2j + 1 (upper half, -1 past r1); cells are numbered side by side in that order, n_cells in
+ *                all, and the Morton index of a cell is the sum of (side / min_cell)^2 over the cells before it: x from
+ *                its even bits, y from its odd bits, times min_cell = cell_start (n_cells, 2) int32.  cell_side (n_cells)
+ *                int32, cell_face (n_cells, 2) int32.  uv (F, 3, 2) fp32, absolute texel coordinates with texel (i, j)
+ *                centred at (i + 0.5, j + 0.5): the lower half's corners at start + (1.5, 1.5), + (1.5 + L, 1.5), + (1.5,
+ *                1.5 + L), the upper half's at the point mirror (x, y) -> (s - x, s - y) of those.
+ *   hn_tex_rasterize  one work-item per texel of the (H, W) atlas (sides multiples of min_cell, at most 16384);
+ *                class_cells_host = 8 HOST int64, the first cell of side 1024 >> q, then n_cells.  owner (H, W) int32 = the
+ *                face of the half the texel lies in: the lower half owns i + j <= s - 2 (cell-relative), the upper half
+ *                i + j >= s, nobody i + j = s - 1; -1 there, outside every cell, in an empty half and for a face or
+ *                vertex id out of range.  position (H, W, 3) fp32 = (b0*v0 + b1*v1) + b2*v2 with b1 = (x - 1.5) / L,
+ *                b2 = (y - 1.5) / L, b0 = (1 - b1) - b2 at the texel centre (x, y), mirrored first in the upper half; not
+ *                clamped to the triangle.  normal (H, W, 3) fp32 = the vertex normals mixed alike and divided by their
+ *                length sqrt(dot(N, N)) (normals_dev NULL, or a length not > 0: the face normal cross(v1 - v0, v2 - v0)
+ *                alike; zero when that has no length either).  Unowned texels get zeros.
+ *   hn_tex_shade      hn_mesh_shade with the colour from a texture (tex_h, tex_w, 3), texture_kind 1: uint8 / 255, 2: fp32:
+ *                (u, v) = (w0*uv[f][0] + w1*uv[f][1]) + w2*uv[f][2] per coordinate, clamped to the bounding box of the three;
+ *                filter 1 (bilinear): a = u - 0.5, i0 = floor(a), fx = a - i0, rows alike, top = c00 + fx*(c10 - c00), bot =
+ *                c01 + fx*(c11 - c01), colour = top + fy*(bot - top); filter 0: the texel (floor(u), floor(v)).  Indices are
+ *                clamped into the texture.  Normal, headlight factor, clamp to [0, 1], rgb8 and background as hn_mesh_shade.
+ * Status, before any launch: -2 for a size out of range (a count <= 0 where one is needed or above 2^31 - 1, a cell side
+ * that is no power of two in 16 .. 1024, min_cell > max_cell, texel not positive and finite, a class table that is not
+ * ascending from 0 to the count or describes more than 16384 x 16384 texels, an atlas side outside 1 .. 16384 or no
+ * multiple of min_cell, ray_ld < 6, a kind or filter that does not exist, a colour outside [0, 1]), -3 for a NULL pointer
+ * that must not be. */
+int hn_tex_classify(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces, float texel,
+                    int min_cell, int max_cell, int32_t* class_dev, int64_t* keys_dev, int32_t* err_dev, hnStream_t stream);
+int hn_tex_layout(const int64_t* sorted_keys_dev, long long n_faces, const int64_t* class_rank_host, int min_cell,
+                  long long n_cells, int32_t* cell_start_dev, int32_t* cell_side_dev, int32_t* cell_face_dev, float* uv_dev,
+                  hnStream_t stream);
+int hn_tex_rasterize(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces,
+                     const float* normals_dev, const int32_t* cell_face_dev, long long n_cells,
+                     const int64_t* class_cells_host, int min_cell, int H, int W, int32_t* owner_dev, float* position_dev,
+                     float* normal_dev, hnStream_t stream);
+int hn_tex_shade(const float* vertices_dev, long long n_vertices, const int32_t* faces_dev, long long n_faces,
+                 const float* normals_dev, const float* uv_dev, const void* texture_dev, int texture_kind, int tex_h,
+                 int tex_w, int filter, const float* rays_dev, int ray_ld, long long n_pixels, const int32_t* face_dev,
+                 const float* bary_dev, int headlight, float ambient, const float* background_host, float* normal_out_dev,
+                 float* rgb_out_dev, uint8_t* rgb8_out_dev, hnStream_t stream);
+
 /* LPIPS v0.1 (csrc/hn_lpips.hip; DESIGN.md 3.14 holds the definition, tests/lpips_restated.py restates it in float64): the
  * layers of the frozen AlexNet / VGG16 backbones and the distance head, exact fp32, one entry point per layer kind; the
  * layer tables and the weights are the host's (ops/lpips/).  All tensors contiguous DEVICE fp32 unless said otherwise.
