@@ -4,9 +4,9 @@ PyTorch is used for device memory, streams and the autograd graph only; all arit
 hot path happens in the HIP kernels.  Every function here raises if handed a CPU tensor.
 
 This module holds the training step: precision mode, MLP programs, weight-gradient scheduling, the GLO embedding,
-sampling, draws, the step prologue, compositing, the loss heads, SE(3) and the stand-alone encoders.  Metrics, the data
-path, meshes and the GIF quantiser live in ops/, one module per kernel source file; their public names (each module's
-__all__) stay reachable here.
+sampling, draws, the step prologue, compositing, the loss heads, the regularizers, SE(3) and the stand-alone encoders.
+Metrics, the data path, meshes and the GIF quantiser live in ops/, one module per kernel source file; their public
+names (each module's __all__) stay reachable here.
 """
 from __future__ import annotations
 
@@ -909,19 +909,38 @@ _UNIT_ROOTS = set()     # data_ptr() of the cached root gradients that hold exac
 _ROOT_GRADS: Dict[tuple, torch.Tensor] = {}
 
 
-def backward(loss: torch.Tensor, weight: float = 1.0):
-    """`(weight * loss).backward()` without the two launches autograd adds around it: the root gradient is a cached
-    device scalar holding `weight` (loss.backward() alone fills a fresh ones_like every call, and `loss * w` is one
-    more elementwise kernel) — what training.TrainStep and bench.py call once per step / chunk."""
+_ROOT_VALUES: Dict[int, float] = {}     # data_ptr() of every cached fp32 root gradient -> the value it holds
+
+
+def _root_grad(loss: torch.Tensor, weight: float) -> torch.Tensor:
     key = (str(loss.device), float(weight), loss.dtype)
     g = _ROOT_GRADS.get(key)
     if g is None:
         if torch.cuda.is_current_stream_capturing():
             raise L.HnError("functional.backward: first use of a new weight inside a stream capture (run a warm-up step)")
         g = _ROOT_GRADS[key] = torch.full((), float(weight), dtype=loss.dtype, device=loss.device)
-        if float(weight) == 1.0 and loss.dtype == torch.float32:
-            _UNIT_ROOTS.add(g.data_ptr())
-    loss.backward(gradient=g)
+        if loss.dtype == torch.float32:
+            _ROOT_VALUES[g.data_ptr()] = float(weight)
+            if float(weight) == 1.0:
+                _UNIT_ROOTS.add(g.data_ptr())
+    return g
+
+
+def backward(loss: torch.Tensor, weight: float = 1.0):
+    """`(weight * loss).backward()` without the two launches autograd adds around it: the root gradient is a cached
+    device scalar holding `weight` (loss.backward() alone fills a fresh ones_like every call, and `loss * w` is one
+    more elementwise kernel) — what training.TrainStep and bench.py call once per step / chunk."""
+    loss.backward(gradient=_root_grad(loss, weight))
+
+
+def backward_all(roots: Sequence[Tuple[torch.Tensor, float]]):
+    """`sum(weight * loss for loss, weight in roots).backward()` as ONE traversal of the autograd graph, every root with
+    the cached device scalar `backward` gives it: losses that share nodes (the photometric loss and a term on the same
+    level's compositing weights) run those nodes' backward — the compositing kernel, the MLP machines — once, with
+    the gradients of all roots, not once per root."""
+    if not roots:
+        raise ValueError("backward_all: no roots")
+    torch.autograd.backward([loss for loss, _ in roots], [_root_grad(loss, w) for loss, w in roots])
 
 
 def mse_loss(coarse: torch.Tensor, fine: Optional[torch.Tensor], target: torch.Tensor) -> torch.Tensor:
@@ -1009,6 +1028,94 @@ def bg_loss(warped: torch.Tensor, points: torch.Tensor, scale: float) -> torch.T
     if not scale > 0:
         raise ValueError(f"bg_loss: scale must be positive, got {scale}")
     return _BgLossFn.apply(warped, points, float(scale))
+
+
+# --------------------------------------------------------------------------------------------
+# distortion loss (csrc/hn_regularizers.hip)
+# --------------------------------------------------------------------------------------------
+SPACINGS = ('linear', 'disparity')      # index = `spacing` of hn_distortion_*
+_DIST_TICKETS: Dict[str, torch.Tensor] = {}
+
+
+def _dist_ticket(device) -> torch.Tensor:
+    """The zeroed uint32 the mean's last-block reduction counts on; every launch leaves it zero.  One per device: the
+    launches that share it are ordered by the stream they run on."""
+    key = str(device)
+    t = _DIST_TICKETS.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.HnError("distortion_loss: first use inside a stream capture (run a warm-up step first)")
+        t = _DIST_TICKETS[key] = torch.zeros(4, dtype=torch.int32, device=device)
+    return t
+
+
+class _DistortionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weights, z, near, far, spacing, mean, root):
+        L.require_gpu(weights, z)
+        L.load()
+        w = weights.detach().contiguous()
+        zc = z.detach().contiguous()
+        b, s = w.shape
+        per_ray = torch.empty(b, dtype=torch.float32, device=w.device)
+        loss = torch.empty((), dtype=torch.float32, device=w.device) if mean else None
+        ticket = _dist_ticket(w.device) if mean else None
+        ctx.unit = None
+        if mean and ctx.needs_input_grad[0]:
+            # as _MseFn: the gradient for the root gradient the caller announced (`root`, by default exactly 1) comes out
+            # of the forward launch; any other incoming gradient takes the backward kernel
+            dw = torch.empty_like(w)
+            L.launch("hn_distortion_forward_grad", L.ptr(w), L.ptr(zc), b, s, near, far, spacing, root, L.ptr(per_ray),
+                     L.ptr(loss), L.ptr(ticket), L.ptr(dw), L.stream_handle())
+            ctx.unit = dw
+        else:
+            L.launch("hn_distortion_forward", L.ptr(w), L.ptr(zc), b, s, near, far, spacing, L.ptr(per_ray), L.ptr(loss),
+                     L.ptr(ticket), L.stream_handle())
+        ctx.saved = (w, zc, b, s, near, far, spacing, mean, root)
+        return loss if mean else per_ray
+
+    @staticmethod
+    def backward(ctx, g):
+        L.load()
+        w, zc, b, s, near, far, spacing, mean, root = ctx.saved
+        # a cached device scalar of functional.backward / backward_all that holds exactly `root`
+        if ctx.unit is not None and _ROOT_VALUES.get(g.data_ptr()) == root:
+            return ctx.unit, None, None, None, None, None, None
+        g = g.contiguous().float()
+        dw = torch.empty_like(w)
+        L.launch("hn_distortion_backward", L.ptr(w), L.ptr(zc), b, s, near, far, spacing, L.ptr(g), 0 if mean else 1,
+                 L.ptr(dw), L.stream_handle())
+        return dw, None, None, None, None, None, None
+
+
+def distortion_loss(weights: torch.Tensor, z: torch.Tensor, near: float, far: float, spacing: str = 'linear',
+                    reduction: str = 'mean', root: float = 1.0) -> torch.Tensor:
+    """Mip-NeRF 360's distortion loss (Barron et al. 2022, eq. 15) of one level: weights, z (B, S) fp32 in the level's
+    sorted order (what `results[level]['weights']` and `model.last_sampling` hold), S <= MAX_SAMPLES.  With the
+    normalised distance s = (z - near) / (far - near) ('linear') or (1/z - 1/near) / (1/far - 1/near) ('disparity',
+    near > 0), sample i < S-1 owning [s_i, s_{i+1}] (width d_i, midpoint m_i) and the last sample a point mass at its
+    own depth,  L_ray = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i.  'mean' returns the scalar mean over rays,
+    'none' the (B,) values.  Differentiable in `weights` only.  One launch forward (hn_distortion_forward_grad), which
+    for 'mean' also writes the gradient for a root gradient of `root`: a backward pass whose root is the cached scalar
+    `root` of `backward` / `backward_all` launches nothing more; any other incoming gradient takes hn_distortion_backward."""
+    if weights.dim() != 2 or weights.shape != z.shape or weights.shape[0] == 0 or weights.shape[1] == 0 \
+            or weights.dtype != torch.float32 or z.dtype != torch.float32:
+        raise ValueError(f"distortion_loss: weights and z must both be (B, S) fp32, got {tuple(weights.shape)} "
+                         f"{weights.dtype} and {tuple(z.shape)} {z.dtype}")
+    if weights.shape[1] > MAX_SAMPLES:
+        raise ValueError(f"distortion_loss: at most {MAX_SAMPLES} samples per ray, got {weights.shape[1]}")
+    if spacing not in SPACINGS:
+        raise ValueError(f"distortion_loss: spacing must be one of {SPACINGS}, got {spacing!r}")
+    if reduction not in ('mean', 'none'):
+        raise ValueError(f"distortion_loss: reduction must be 'mean' or 'none', got {reduction!r}")
+    near, far, root = float(near), float(far), float(root)
+    if not (near == near and far == far) or near == far or abs(near) == float('inf') or abs(far) == float('inf'):
+        raise ValueError(f"distortion_loss: near and far must be finite and differ, got {near} and {far}")
+    if spacing == 'disparity' and not near > 0:
+        raise ValueError(f"distortion_loss: disparity spacing needs near > 0, got {near}")
+    if root != root:
+        raise ValueError("distortion_loss: root is NaN")
+    return _DistortionFn.apply(weights, z, near, far, SPACINGS.index(spacing), reduction == 'mean', root)
 
 
 # --------------------------------------------------------------------------------------------

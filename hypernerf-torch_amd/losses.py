@@ -7,8 +7,10 @@ one-liners; `ssim` runs kornia's windowed SSIM in HIP (`hn_ssim_*`, ops.metrics.
 `lpips` is the third number of those tables, LPIPS v0.1 over a frozen AlexNet or VGG16 (`hn_lpips_*`), a metric only.
 `BackgroundLoss` is HyperNeRF's background regularization, a training term that takes the model instead of rendered
 rays: static points of the capture through the warp field, pulled back to where they were (`hn_bg_*`).
+`DistortionLoss` is Mip-NeRF 360's distortion loss, a training term on the compositing weights of the rendered levels
+that discourages floaters (`hn_distortion_*`).
 GPU tensors only, like every op of the package."""
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 from torch import nn
@@ -94,6 +96,67 @@ class BackgroundLoss:
         if warped.shape[-1] != 3:         # a field that appends further coordinates: the loss is on the spatial ones
             warped = warped[..., :3]
         return F.bg_loss(warped, p, self.scale)
+
+
+class DistortionLoss:
+    """Mip-NeRF 360's distortion loss (Barron et al. 2022, eq. 15): per ray, with s the depth normalised to [0, 1]
+    between near and far, sample i owning the interval up to the next sample (midpoint m_i, width d_i) and the last
+    sample a point mass at its own depth,
+
+        L_ray = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i          loss = mean over rays, summed over `levels`
+
+    a penalty on compositing weights that are spread out or split along the ray: what floaters are made of.  The
+    weights are the level's `results[level]['weights']`, the depths `model.last_sampling` ('z_coarse', 'z_fine': the
+    same sorted order); one launch per level (functional.distortion_loss).  `spacing=None` follows the model
+    ('disparity' with use_linear_disparity, else 'linear'); `near` / `far` default to the model's.  weight = 0.01 is the
+    paper's lambda.  `TrainStep(..., distortion_loss=DistortionLoss())` adds `weight` times the term to every step."""
+
+    LEVELS = ('coarse', 'fine')
+
+    def __init__(self, weight: float = 0.01, levels: Sequence[str] = ('fine',), spacing: Optional[str] = None,
+                 near: Optional[float] = None, far: Optional[float] = None):
+        levels = (levels,) if isinstance(levels, str) else tuple(levels)
+        if not levels:
+            raise ValueError("DistortionLoss: no levels")
+        bad = [lv for lv in levels if lv not in self.LEVELS]
+        if bad or len(set(levels)) != len(levels):
+            raise ValueError(f"DistortionLoss: levels must be distinct names out of {self.LEVELS}, got {levels}")
+        if spacing is not None and spacing not in F.SPACINGS:
+            raise ValueError(f"DistortionLoss: spacing must be None or one of {F.SPACINGS}, got {spacing!r}")
+        if not float(weight) >= 0:
+            raise ValueError(f"DistortionLoss: weight must not be negative, got {weight}")
+        self.weight, self.levels, self.spacing = float(weight), levels, spacing
+        self.near = None if near is None else float(near)
+        self.far = None if far is None else float(far)
+
+    def per_level(self, model, results, root: float = 1.0) -> List[torch.Tensor]:
+        """The unweighted loss of every level in `levels`, in that order.  `root`: the root gradient the caller will
+        back-propagate each of them with (functional.backward_all): the forward launch then writes that gradient."""
+        sampling = getattr(model, 'last_sampling', None)
+        if sampling is None:
+            raise ValueError("DistortionLoss: the model has kept no depths (model.last_sampling: a forward with fine "
+                             "samples comes first)")
+        spacing = self.spacing or ('disparity' if getattr(model, 'use_linear_disparity', False) else 'linear')
+        near = model.near if self.near is None else self.near
+        far = model.far if self.far is None else self.far
+        out = []
+        for level in self.levels:
+            if level not in results:
+                raise ValueError(f"DistortionLoss: the model rendered no '{level}' level")
+            weights, z = results[level]['weights'], sampling['z_' + level]
+            if z.shape != weights.shape:
+                raise ValueError(f"DistortionLoss: '{level}' weights {tuple(weights.shape)} and depths {tuple(z.shape)} "
+                                 f"are not of one forward pass")
+            out.append(F.distortion_loss(weights, z, near, far, spacing, root=root))
+        return out
+
+    def __call__(self, model, results) -> torch.Tensor:
+        """The unweighted sum over `levels` of the model's latest forward pass (`results` = what it returned)."""
+        terms = self.per_level(model, results)
+        total = terms[0]
+        for t in terms[1:]:
+            total = total + t
+        return total
 
 
 def mse(image_pred, image_gt, valid_mask=None, reduction='mean'):

@@ -13,6 +13,9 @@ optionally in two buckets, the first in flight while the weight gradients of the
 `step(rays, rgbs)` returns the log the reference's training_step records: {'train/loss', 'train/psnr', 'lr'}
 (device scalars, no host sync).  `background_loss=losses.BackgroundLoss(...)` adds HyperNeRF's background regularization
 to every step (and 'train/background_loss' to the log); without it the step is launch for launch the one above.
+`distortion_loss=losses.DistortionLoss(...)` adds Mip-NeRF 360's distortion loss on the rendered levels' compositing
+weights (and 'train/distortion_loss'): one launch per level behind the compositing launches, back-propagated together
+with the MSE in ONE traversal (functional.backward_all); without it the step is launch for launch the one above.
 `clip_grad_norm=` / `clip_grad_value=` clip the gradient buffer in two HIP launches right before every optimizer launch
 (optim.GradClip: by value, then by global norm; Lightning's gradient_clip_val / gradient_clip_algorithm) and
 `clip_grad_norm` adds 'train/grad_norm' (the norm before clipping) to the log; without them nothing is allocated or launched.
@@ -43,7 +46,7 @@ class TrainStep:
                  decay_step: Optional[Sequence[int]] = None, decay_gamma: float = 0.1, overlap_grad_sync: bool = False,
                  hparams=None, force_dp: bool = False, capture_collective: bool = True, optimizer: str = "adam",
                  momentum: float = 0.9, batcher=None, background_loss=None, clip_grad_norm: Optional[float] = None,
-                 clip_grad_value: Optional[float] = None):
+                 clip_grad_value: Optional[float] = None, distortion_loss=None):
         # the optimizer of the reference's get_optimizer (utils/__init__.py:23-41): hparams.optimizer (and
         # hparams.momentum for 'sgd') when hparams carries one, the keywords otherwise; lr / eps / weight_decay always
         # from the keywords.  Checked before any device work.
@@ -104,6 +107,8 @@ class TrainStep:
         # losses.BackgroundLoss or None: a term of its own ahead of the ray chunks (_forward_backward_body)
         self.background_loss = background_loss
         self._bg_rng: Optional[Dict[str, torch.Tensor]] = None   # its injected draws, split off `rng` (_split_rng)
+        # losses.DistortionLoss or None: a term on every ray chunk's compositing weights (_forward_backward_body)
+        self.distortion_loss = distortion_loss
         self._graph: Optional[GraphedStep] = None
         self._rays = self._rgbs = None
         self._rng: Optional[Dict[str, torch.Tensor]] = None    # fixed buffers of injected random draws (tests)
@@ -123,7 +128,8 @@ class TrainStep:
 
     def _forward_backward_body(self):
         b = self._rays.shape[0]
-        loss_sum, psnr_in = None, []
+        loss_sum, dist_sum, psnr_in = None, None, []
+        dl = self.distortion_loss
         bg = None
         if self.background_loss is not None:
             # a term of its own, handled exactly like a non-last ray chunk: back-propagated at once (its activations are
@@ -141,8 +147,16 @@ class TrainStep:
             kw = {} if self._rng is None else {'rng': {k: v[i:i + self.chunk] for k, v in self._rng.items()}}
             results = self.model(model_utils.prepare_ray_dict(rays), dict(_EXTRA), **kw)
             w = rays.shape[0] / b
+            # the term's forward launches (one per level, right behind the compositing launches) write the gradient for
+            # the root they are about to get
+            terms = dl.per_level(self.model, results, root=dl.weight * w) if dl is not None else []
             loss = self.loss_fn(results, rgbs)
-            F.backward(loss, w)          # into arena.grad (zeroed by the previous Adam launch); cached root gradient = w
+            if dl is None:
+                F.backward(loss, w)      # into arena.grad (zeroed by the previous Adam launch); cached root gradient = w
+            else:
+                # ONE traversal: the compositing kernels and the MLP machines run backward once, with the gradients of
+                # both losses
+                F.backward_all([(loss, w)] + [(t, dl.weight * w) for t in terms])
             if i + self.chunk < b:
                 F.flush_held_wgrads()        # only the LAST chunk's held jobs overlap with the all-reduce (a held
                                              # job keeps its chunk's activation stash alive)
@@ -150,11 +164,19 @@ class TrainStep:
             with torch.no_grad():
                 loss_sum = loss.detach() * w if loss_sum is None else loss_sum + loss.detach() * w
                 psnr_in.append(results[typ]['rgb'].detach())
+                if dl is not None:
+                    d = terms[0].detach()
+                    for t in terms[1:]:
+                        d = d + t.detach()
+                    d = d if w == 1.0 else d * w
+                    dist_sum = d if dist_sum is None else dist_sum + d
         with torch.no_grad():
             pred = psnr_in[0] if len(psnr_in) == 1 else torch.cat(psnr_in, 0)
             self._log = {'train/loss': loss_sum, 'train/psnr': psnr(pred, self._rgbs)}
             if bg is not None:
                 self._log['train/background_loss'] = bg          # unweighted
+            if dist_sum is not None:
+                self._log['train/distortion_loss'] = dist_sum    # unweighted
 
     def _optimizer_step(self):
         if self.clip is not None:

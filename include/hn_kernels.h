@@ -1021,6 +1021,35 @@ int hn_bg_loss_forward_grad(const float* warped, const float* points, int n, flo
 int hn_bg_loss_backward(const float* warped, const float* points, int n, float scale, const float* g_loss,
                         float* d_warped, hnStream_t stream);
 
+/* Distortion loss of Mip-NeRF 360 (Barron et al. 2022, eq. 15; csrc/hn_regularizers.hip) on ONE level's compositing
+ * weights.  weights, z (n_rays, n_samples) contiguous fp32, both in the level's sorted order (z ascending along a ray),
+ * n_samples <= 512.  Normalised distance
+ *   s_i = (z_i - near) / (far - near)                  spacing 0 (linear)
+ *   s_i = (1/z_i - 1/near) / (1/far - 1/near)          spacing 1 (disparity; near > 0)
+ * Sample i < S-1 owns [s_i, s_{i+1}]: width d_i = s_{i+1} - s_i, midpoint m_i = (s_i + s_{i+1}) / 2; the last sample (the
+ * compositing kernel's "infinite" interval) is a point mass: d = 0, m = s_{S-1}.
+ *   L_ray = sum_ij w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i        loss = mean over rays of L_ray
+ *   dL_ray/dw_i = 2 sum_j w_j |m_i - m_j| + (2/3) w_i d_i             (depths carry no gradient)
+ * O(S) per ray (prefix and suffix sums; one wave per ray).  n_samples = 1 gives loss 0 and gradient 0.
+ *
+ * per_ray (n_rays) receives L_ray and is required: it is also what the mean is taken from.  loss_out: ONE device float,
+ * the mean, added in a fixed order by the block that finishes last (no float atomics: bit-reproducible); NULL in
+ * hn_distortion_forward = per-ray values only.  ticket: ONE device uint32 that is 0 before the first launch; the launch
+ * leaves it 0 (needed whenever loss_out is given; launches that share a ticket must be stream-ordered).
+ * hn_distortion_forward_grad also writes d_weights = grad_scale / n_rays * dL_ray/dw — bit for bit what
+ * hn_distortion_backward writes for g_loss[0] == grad_scale.  hn_distortion_backward: g_loss is ONE device float (the
+ * mean's incoming gradient) or, with per_ray_g != 0, n_rays floats (the incoming gradient of per_ray; no 1 / n_rays).
+ *
+ * Status: -2 for every refused argument (a NULL pointer, n_rays <= 0, n_samples <= 0 or > 512, far == near, a spacing
+ * that is neither of the two, near <= 0 under disparity spacing, a NaN grad_scale), checked on the host before any launch. */
+int hn_distortion_forward(const float* weights, const float* z, int n_rays, int n_samples, float near, float far,
+                          int spacing, float* per_ray, float* loss_out, uint32_t* ticket, hnStream_t stream);
+int hn_distortion_forward_grad(const float* weights, const float* z, int n_rays, int n_samples, float near, float far,
+                               int spacing, float grad_scale, float* per_ray, float* loss_out, uint32_t* ticket,
+                               float* d_weights, hnStream_t stream);
+int hn_distortion_backward(const float* weights, const float* z, int n_rays, int n_samples, float near, float far,
+                           int spacing, const float* g_loss, int per_ray_g, float* d_weights, hnStream_t stream);
+
 /* torch.optim.Adam (the reference's default optimizer, utils/__init__.py get_optimizer) over ONE flat fp32 buffer
  * (ParamArena): p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps), m,v updated first, L2 weight decay added to the
  * gradient.  `hyper_dev`: 8 floats ON THE DEVICE, [lr, beta1, beta2, eps, weight_decay, grad_scale, 0, 0] — read by the
