@@ -644,228 +644,27 @@ HN_DEV void hn_layer_pipelined(bf16x8* cur, bf16x8* nxt, const float* bias, WStr
 // need 237 (AUXG 2) / 253 (AUXG 3) registers and no scratch (12 / 72 B/lane with them).
 // TRAIN: masks and stashes are written (HnMlpArgs.training); the inference build carries none of that code.
 // S8: HN_MODE_BF16_S8 — the stash is written as e4m3, 1 KiB per tile (hn_stash); nothing else changes.
+// ACTS: the program may hold LeakyReLU / ELU / Softplus layers.  Without it every layer is ReLU or linear by construction
+// (HnMlpArgs.wide_ops bit 2) and none of hn_act_tile's code is in the build (hn_mlp_fwd_relu_kernel below).
+//
+// The statements of the kernel are in hn_mlp_fwd_body.h, included textually into the two entries below, and NOT in a
+// __device__ function template the entries call: hipcc only addresses the 2.5 KB of arguments straight from the kernel
+// argument segment while `a` is the kernel's own parameter.  With the body in a function (argument by reference, by value
+// or as a pointer to the segment: all three cross-compiled) every existing build comes out different, the fp32 and EXTRA
+// builds with all of HnMlpArgs copied to scratch (2584-2760 B/lane).
+// hn_mlp_fwd_kernel takes every program (ACTS on).  hn_mlp_fwd_relu_kernel is the lean render-level bf16 build for
+// programs whose layers are all ReLU or linear (hn_mlp_forward picks it by HnMlpArgs.wide_ops bit 2); its fixed flags are
+// defaulted template parameters so that the body's `if constexpr` stay dependent.  (No lean AUXG = 3 inference build:
+// like its generic sibling it would need scratch.)
 template <bool BF16, int AUXG, bool EXTRA, bool TRAIN, bool S8 = false>
 __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_fwd_kernel(const HnMlpArgs a) {
-  using M = ModeT<BF16>;
-  constexpr int SX = S8 ? 1 : 0;
-  static_assert(!(S8 && (EXTRA || !TRAIN || !BF16)), "the 8-bit stash exists for the render-level bf16 training builds only");
-  if constexpr (S8) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");     // FP16_OVFL: 8-bit conversions clamp
-  using Frag = typename M::Frag;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  constexpr int PTS = M::WAVES * 32;
-  const int ntiles = (a.n_points + PTS - 1) / PTS;
-  hn_timeline_begin(a.timeline);
-#ifdef HN_PROF
-  long long* prof_buf = reinterpret_cast<long long*>(a.prof);
-  const bool prof_on = prof_buf != nullptr && blockIdx.x == 0 && wave == 0;
-  int prof_n = 0;
-#endif
-
-  WStream<M::WAVES> ws;
-  ws.g = reinterpret_cast<const char*>(a.wstream);
-  ws.lds = smem;
-  ws.nchunks = a.n_chunks;
-  ws.wave = wave;
-  ws.lane = lane;
-
-  Frag cur[8 * M::STEPS32];
-  Frag nxt[8 * M::STEPS32];
-
-  // biases and the feature table live in LDS for the whole kernel: no global loads inside the MFMA loops
-  float* bias_lds = reinterpret_cast<float*>(smem + 2 * HN_CHUNK_UNITS * 1024);
-  HnFeat* feat_lds = reinterpret_cast<HnFeat*>(bias_lds + ((a.n_bias + 3) & ~3));
-  HnDFeat* dfeat_lds = reinterpret_cast<HnDFeat*>(feat_lds + ((a.n_feat + 1) & ~1));      // bf16 kernels only
-  // per wave: value plane (n_comps x 32 floats) and, bf16 only, the (hi, lo) planes of x / 2pi for the first n_trig
-  const int n_trig = BF16 ? a.n_trig_comps : 0;
-  const bool with_lo = a.trig_lo_planes != 0;
-  const int n_planes = BF16 ? a.n_comps + n_trig + (with_lo ? n_trig : 1) : a.n_comps;
-  float* srcv = reinterpret_cast<float*>(BF16 ? reinterpret_cast<char*>(dfeat_lds + a.n_feat)
-                                              : reinterpret_cast<char*>(dfeat_lds)) + wave * (n_planes * 32);
-  float* rev = BF16 ? srcv + a.n_comps * 32 : nullptr;
-  for (int i = threadIdx.x; i < a.n_bias; i += blockDim.x) bias_lds[i] = a.bias[i];
-  for (int i = threadIdx.x; i < a.n_feat; i += blockDim.x) {
-    const HnFeat e = a.feat[i];
-    feat_lds[i] = e;
-    if constexpr (BF16) dfeat_lds[i] = hn_derive_feat_fwd(e, a.n_comps, n_trig, with_lo);
-  }
-  __syncthreads();
-
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int blk = tile * M::WAVES + wave;  // 32-point block of this wave
-    const int p0 = blk * 32 + r;
-    const bool valid = p0 < a.n_points;
-    const int p = valid ? p0 : a.n_points - 1;
-    const int ray = p / a.samples_per_ray;
-    const bool wave_valid = blk * 32 < a.n_points;  // wave-uniform: the block holds at least one point
-    hn_stage_sources(srcv, a, p, ray, lane, rev, n_trig, with_lo);
-    ws.start();
-
-    HnOpWords w_next = hn_load_op(a.ops, 0, a.n_ops);
-    for (int op = 0; op < a.n_ops; ++op) {
-      const HnOpWords w = w_next;
-      w_next = hn_load_op(a.ops, op + 1, a.n_ops);
-      const int code = w[0];
-      if (code == HN_OP_LAYER) {
-        HN_STAMP(100 + op);
-        const int K32 = w[1] & 255, nG = (w[1] >> 8) & 255, NT = (w[1] >> 16) & 255;
-        const int act = (w[1] >> 24) & 15, flags = (w[1] >> 28) & 15;
-        const float* bias = bias_lds + w[2];
-        const bool do_mask = TRAIN && w[4] >= 0 && wave_valid && act != HN_ACT_SOFTPLUS;   // (softplus: w4 = p1)
-        const bool do_stash = TRAIN && w[5] >= 0 && wave_valid;
-        char* out_base = do_stash ? hn_slot_base<BF16, SX>(a, w[5], NT, blk) : nullptr;
-        char* aux_base = (TRAIN && wave_valid) ? hn_slot_base<BF16, SX>(a, w[6], 2 * nG, blk) : nullptr;
-        uint32_t* mask_base = do_mask ? hn_mask_base(a, w[4], (NT + 1) >> 1, blk, lane) : nullptr;
-        const bool has_out = w_next[0] == HN_OP_OUT;    // head layer: its <=4 outputs leave from the accumulator
-        const HnOpWords out_w = w_next;
-        Frag aux[AUXG * 2 * M::STEPS32];
-#pragma unroll
-        for (int g = 0; g < AUXG; ++g) {
-          if (g < nG) {
-            if (EXTRA && (flags & HN_LAYER_DIRECT))
-              hn_make_group<true>(aux + g * 2 * M::STEPS32, feat_lds + w[3] + 64 * g, dfeat_lds + w[3] + 64 * g, srcv,
-                                  lane, a, p, ray);
-            else
-              hn_make_group<false>(aux + g * 2 * M::STEPS32, feat_lds + w[3] + 64 * g, dfeat_lds + w[3] + 64 * g, srcv,
-                                   lane, a, p, ray);
-            if (aux_base != nullptr) {
-              hn_stash<BF16, SX>(aux + g * 2 * M::STEPS32, aux_base, 2 * g, lane);
-              hn_stash<BF16, SX>(aux + (g * 2 + 1) * M::STEPS32, aux_base, 2 * g + 1, lane);
-            }
-          }
-        }
-        unsigned bits = 0;
-        HN_STAMP(1);
-        if constexpr (BF16) {
-          // plain 128 -> 128 ReLU layers (template rgb branch, warp field) take the pipelined body (adding the 64-wide
-          // shape as well tips the register allocator into spilling inside the generic path: measured 7 % slower)
-          const bool plain = nG == 0 && act == HN_ACT_RELU && !(flags & HN_LAYER_NO_COMMIT) && !has_out &&
-                             wave_valid && do_stash == do_mask;
-          if (plain && K32 == 4 && NT == 4) {
-            if (do_stash) hn_layer_pipelined<4, 4, true, SX>(cur, nxt, bias, ws, out_base, mask_base, lane);
-            else hn_layer_pipelined<4, 4, false, SX>(cur, nxt, bias, ws, out_base, mask_base, lane);
-            continue;
-          }
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if (t < NT) {
-            f32x16 acc;
-            hn_init_acc(acc, bias, t, h);
-            hn_gemm_k<BF16>(acc, cur, K32, ws);
-#pragma unroll
-            for (int g = 0; g < AUXG; ++g)
-              if (g < nG) hn_gemm_blocks<BF16, 2>(acc, aux + g * 2 * M::STEPS32, ws);
-            HN_STAMP(2);
-            if (act == HN_ACT_RELU) {
-#pragma unroll
-              for (int i = 0; i < 16; ++i) {
-                bits = hn_push_mask<BF16>(bits, acc[i]);
-                acc[i] = __int_as_float(max(__float_as_int(acc[i]), 0));  // relu on the bit pattern: one v_max_i32
-              }
-            } else if (act != HN_ACT_NONE) {
-              hn_act_tile<BF16>(acc, act, __int_as_float(w[7]), __int_as_float(w[4]), bits);
-            }
-            if (has_out && t == 0 && h == 0 && valid) {
-              // the OUT op that follows a head layer: <= 4 fp32 columns straight from the accumulator
-              const HnDst d = a.dst[out_w[1]];
-              const int n = out_w[3];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                if (i < n) {
-                  float y = acc[i];
-                  if (out_w[4] == 1) y = 1.0f / (1.0f + expf(-y));
-                  if (out_w[5] >= 0) {
-                    const HnSrc sr = a.src[out_w[5]];
-                    y = __fadd_rn(sr.ptr[(size_t)(sr.per_ray ? ray : p) * sr.ld + out_w[6] + i], y);
-                  }
-                  d.ptr[(size_t)p * d.ld + out_w[2] + i] = y;
-                }
-              }
-            }
-            if (has_out && t == 0 && h == 0 && out_w[7] > 0) {
-              // publish the head's results as staged components of this block (every lane: padded points too)
-              const int n = out_w[3];
-#pragma unroll
-              for (int i = 0; i < 4; ++i) {
-                if (i < n) {
-                  float y = acc[i];
-                  if (out_w[4] == 1) y = 1.0f / (1.0f + expf(-y));
-                  if (out_w[5] >= 0) {
-                    const HnSrc sr = a.src[out_w[5]];
-                    y = __fadd_rn(sr.ptr[(size_t)(sr.per_ray ? ray : p) * sr.ld + out_w[6] + i], y);
-                  }
-                  const int ci = out_w[7] - 1 + i;
-                  srcv[ci * 32 + r] = y;
-                  if (BF16 && ci < n_trig) {
-                    float hi, lo;
-                    hn_rev_split(y, hi, lo);
-                    rev[ci * 32 + r] = hi;
-                    if (with_lo) rev[(n_trig + ci) * 32 + r] = lo;
-                  }
-                }
-              }
-            }
-            hn_acc_to_frags(acc, nxt + t * M::STEPS32);
-#ifdef HN_PROF
-            if (prof_on) {   // make the stamp wait for the tile's results
-              float x__ = acc[15];
-              asm volatile("v_mov_b32 %0, %0" : "+v"(x__)::"memory");
-            }
-#endif
-            HN_STAMP(3);
-            if ((t & 1) || t == NT - 1) {
-              // a plain (cached) store: the backward machine stalls on these words at the top of every layer, and
-              // unlike the once-streamed stash they are small enough (70 MB per step) to survive in L2 / MALL
-              if (do_mask) mask_base[(t >> 1) * 64 + lane] = (t & 1) ? bits : bits << 16;
-              bits = 0;
-            }
-            if (do_stash) {
-              if constexpr (SX != 0) hn_stash8_acc<SX>(acc, out_base, t, lane);
-              else hn_stash<BF16, SX>(nxt + t * M::STEPS32, out_base, t, lane);
-            }
-            HN_STAMP(4);
-          }
-        }
-        if (!(flags & HN_LAYER_NO_COMMIT)) {
-#pragma unroll
-          for (int t = 0; t < 8; ++t)
-            if (t < NT)
-#pragma unroll
-              for (int s = 0; s < M::STEPS32; ++s) cur[t * M::STEPS32 + s] = nxt[t * M::STEPS32 + s];
-        }
-      } else if (code == HN_OP_OUT) {
-        // handled inside the LAYER op it follows (the raw accumulator is only alive there)
-      } else if (EXTRA && code == HN_OP_OUT_WIDE) {
-        const int n = w[3], NT = w[4];
-        if (valid) {
-          const HnDst d = a.dst[w[1]];
-#pragma unroll
-          for (int t = 0; t < 8; ++t)
-            if (t < NT) {
-              if constexpr (BF16) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s)
-#pragma unroll
-                  for (int j = 0; j < 8; ++j) {
-                    const int row = 32 * t + 16 * s + hn_pi16(h, j);
-                    if (row < n) d.ptr[(size_t)p * d.ld + w[2] + row] = (float)cur[2 * t + s][j];
-                  }
-              } else {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                  const int row = 32 * t + hn_rho(q, h);
-                  if (row < n) d.ptr[(size_t)p * d.ld + w[2] + row] = cur[16 * t + q];
-                }
-              }
-            }
-        }
-      }
-    }
-  }
-  hn_timeline_end(a.timeline);
+  constexpr bool ACTS = true;
+#include "hn_mlp_fwd_body.h"
+}
+template <int AUXG, bool TRAIN, bool BF16 = true, bool EXTRA = false, bool S8 = false, bool ACTS = false>
+__global__ __launch_bounds__(ModeT<true>::WAVES * 64, 2) void hn_mlp_fwd_relu_kernel(const HnMlpArgs a) {
+  static_assert(BF16 && !EXTRA && !S8 && !ACTS, "the lean build is bf16, render-level, ReLU-only");
+#include "hn_mlp_fwd_body.h"
 }
 
 // Backward machine: if the NEXT op is a layer with a ReLU mask, start loading its mask words (raw, not complemented)
@@ -882,6 +681,72 @@ HN_DEV bool hn_prefetch_masks(const HnMlpArgs& a, const HnOpWords& wn, int blk, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Software-pipelined backward layer for the plain 128 -> 128 layers (warp field, template rgb branch), lean build only:
+// hn_layer_pipelined's scheme on dZ.  The 8 products of tile t and the mask-and, conversion and stash of tile t-1 share
+// ONE basic block, slot by slot (two accumulators alternate).  Same take() sequence as the generic tile loop, so the
+// barrier counts of waves on either path match; the next layer's mask words are fetched behind the first tile.
+// HN_BWD_PIPE=0 builds the lean backward without it (the body is measured on its own through this switch).
+// ------------------------------------------------------------------------------------------------
+#ifndef HN_BWD_PIPE
+#define HN_BWD_PIPE 1
+#endif
+// one share of the previous tile's epilogue: k = 0..7 elements 2k, 2k+1 (relu' from the mask word, pack to bf16),
+// k = 8 the two 16-byte stash stores of the finished fragments
+HN_DEV void hn_bwd_epilogue_share(int k, int tp, const f32x16& a, bf16x8* frag, unsigned nbits, char* dz_base, int lane) {
+  if (k < 8) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int i = 2 * k + e;
+      frag[i >> 3][i & 7] = (__bf16)__int_as_float(__float_as_int(a[i]) & hn_keep_mask(nbits, tp & 1, i));
+    }
+  } else if (k == 8) {
+    hn_stash<true, 0>(frag, dz_base, tp, lane);
+  }
+}
+template <int K32, int NT>
+HN_DEV void hn_bwd_layer_pipelined(bf16x8* cur, bf16x8* nxt, WStream<ModeT<true>::WAVES>& ws, const unsigned* mbits,
+                                   char* dz_base, int lane, const HnMlpArgs& a, const HnOpWords& w_next, int blk,
+                                   unsigned* mnext, bool& mnext_ready) {
+  constexpr int N = 2 * K32;            // MFMAs (= issue slots) per tile
+  constexpr int D = 2;                  // fragment reads in flight
+  constexpr int SHARES = 9;
+  constexpr int PER_SLOT = (SHARES + N - 1) / N;
+  f32x16 acc[2];
+#pragma unroll
+  for (int t = 0; t <= NT; ++t) {
+    const char* wl = nullptr;
+    if (t < NT) wl = ws.take(N) + lane * 16;        // may pass the chunk barrier (a branch): kept out of the block
+    if (t == 1) mnext_ready = hn_prefetch_masks(a, w_next, blk, lane, true, mnext);
+    const int tp = t - 1;
+    bf16x8 q[D];
+    if (t < NT) {
+      hn_init_acc(acc[t & 1], nullptr, t, 0);
+#pragma unroll
+      for (int u = 0; u < D; ++u) q[u] = *reinterpret_cast<const bf16x8*>(wl + u * 1024);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      // ---- slot u: one product of tile t, one fragment read ahead, shares of tile t-1's epilogue ----
+      if (t < NT) {
+        acc[t & 1] = hn_mfma_bf16(q[u % D], cur[u], acc[t & 1]);
+        if (u + D < N) q[u % D] = *reinterpret_cast<const bf16x8*>(wl + (u + D) * 1024);
+      }
+      if (t > 0) {
+#pragma unroll
+        for (int e = 0; e < PER_SLOT; ++e) {
+          const int k = u * PER_SLOT + e;
+          if (k < SHARES) hn_bwd_epilogue_share(k, tp, acc[tp & 1], nxt + tp * 2, mbits[tp >> 1], dz_base, lane);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NT * 2; ++i) cur[i] = nxt[i];
+}
+
+// ------------------------------------------------------------------------------------------------
 // backward-data machine
 // ------------------------------------------------------------------------------------------------
 // WIDE: the program holds HN_BOP_LOAD_WIDE ops (stand-alone modules with > 4 output columns; never a render-level
@@ -889,299 +754,18 @@ HN_DEV bool hn_prefetch_masks(const HnMlpArgs& a, const HnOpWords& wn, int blk, 
 // per tile pushes the allocator over 256 registers in the prologue).
 // S8: HN_MODE_BF16_S8 — the machine carries 2^dz_scale_log2 * dZ (exact) and stashes it as e5m2, 1 KiB per tile; source
 // and embedding gradients are scaled back on their way out.
+// ACTS: as in the forward.  Without it a layer's derivative is the ReLU mask (or nothing): no hn_dact_y, no read-back of
+// the layer output, no three-way branch per tile (hn_mlp_bwd_relu_kernel below).
+// The statements are in hn_mlp_bwd_body.h, included into both entries (see the forward machine for why not a function).
 template <bool BF16, bool WIDE, bool S8 = false>
 __global__ __launch_bounds__(ModeT<BF16>::WAVES * 64, BF16 ? 2 : 1) void hn_mlp_bwd_kernel(const HnMlpArgs a) {
-  using M = ModeT<BF16>;
-  constexpr int SZ = S8 ? 2 : 0;
-  static_assert(!(S8 && WIDE) && !(S8 && !BF16), "the 8-bit stash exists for the render-level bf16 builds only");
-  if constexpr (S8) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1");     // FP16_OVFL: 8-bit conversions clamp
-  const float dz_scale = S8 ? ldexpf(1.0f, a.dz_scale_log2) : 1.0f;
-  const float dz_unscale = S8 ? ldexpf(1.0f, -a.dz_scale_log2) : 1.0f;
-  using Frag = typename M::Frag;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  constexpr int PTS = M::WAVES * 32;
-  const int ntiles = (a.n_points + PTS - 1) / PTS;
-  HnFeat* feat_lds = reinterpret_cast<HnFeat*>(smem + 2 * HN_CHUNK_UNITS * 1024);
-  HnDFeat* dfeat_lds = reinterpret_cast<HnDFeat*>(feat_lds + ((a.n_feat + 1) & ~1));      // bf16 kernel only
-  float* srcv = reinterpret_cast<float*>(BF16 ? reinterpret_cast<char*>(dfeat_lds + a.n_feat)
-                                              : reinterpret_cast<char*>(dfeat_lds)) + wave * (a.n_comps * 32);
-  hn_timeline_begin(a.timeline);
-#ifdef HN_PROF
-  long long* prof_buf = reinterpret_cast<long long*>(a.prof);
-  const bool prof_on = prof_buf != nullptr && blockIdx.x == 0 && wave == 0;
-  int prof_n = 0;
-#endif
-  for (int i = threadIdx.x; i < a.n_feat; i += blockDim.x) {
-    const HnFeat e = a.feat[i];
-    feat_lds[i] = e;
-    if constexpr (BF16) dfeat_lds[i] = hn_derive_feat(e);
-  }
-  __syncthreads();
-
-  WStream<M::WAVES> ws;
-  ws.g = reinterpret_cast<const char*>(a.wstream);
-  ws.lds = smem;
-  ws.nchunks = a.n_chunks;
-  ws.wave = wave;
-  ws.lane = lane;
-
-  Frag cur[8 * M::STEPS32];
-  Frag nxt[8 * M::STEPS32];
-  Frag cur2[M::STEPS32];
-
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int blk = tile * M::WAVES + wave;
-    const int p0 = blk * 32 + r;
-    const bool valid = p0 < a.n_points;
-    const int p = valid ? p0 : a.n_points - 1;
-    const int ray = p / a.samples_per_ray;
-    const bool wave_valid = blk * 32 < a.n_points;
-    f32x16 dacc;  // source gradients of the block: row rho(i,h) = dsrc column, col r = point
-    hn_init_acc(dacc, nullptr, 0, h);
-    hn_stage_sources(srcv, a, p, ray, lane);
-    ws.start();
-
-    HnOpWords w_next = hn_load_op(a.ops, 0, a.n_ops);
-    unsigned mnext[4] = {0u, 0u, 0u, 0u};
-    bool mnext_ready = false;
-    for (int op = 0; op < a.n_ops; ++op) {
-      const HnOpWords w = w_next;
-      w_next = hn_load_op(a.ops, op + 1, a.n_ops);
-      const int code = w[0];
-      HN_STAMP(100 * code + op);
-      if (code != HN_BOP_LAYER && code != HN_BOP_AUX) mnext_ready = false;   // LOAD ops do not prefetch
-      if (code == HN_BOP_LOAD) {
-        // dZ (<= 4 columns) of an output layer -> one 32-feature tile
-        const int n = w[3] & 255;
-        const bool to2 = (w[3] >> 8) & 1;
-        float d[4] = {0.f, 0.f, 0.f, 0.f};
-        if ((w[3] >> 9) & 1) {
-          // the gradient later ops left in the source-gradient accumulators for the components this head published:
-          // slots 8q + i sit in registers 4q + i of the h == 0 lanes (row rho(4q + i, 0) = 8q + i)
-          const int q = (w[3] >> 10) & 3;
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            d[i] = q == 0 ? dacc[i] : (q == 1 ? dacc[4 + i] : (q == 2 ? dacc[8 + i] : dacc[12 + i]));
-        }
-        if (h == 0 && valid) {
-          const HnSrc s = a.src[w[1] < 0 ? 0 : w[1]];
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if (i < n) {
-              float g = (w[1] >= 0 && s.ptr != nullptr) ? s.ptr[(size_t)p * s.ld + w[2] + i] : 0.0f;
-              if constexpr (S8) g *= dz_scale;
-              if ((w[3] >> 9) & 1) g += d[i];
-              if (w[4] == 1) {
-                const HnSrc ys = a.src[w[5]];
-                const float y = ys.ptr[(size_t)p * ys.ld + w[6] + i];
-                g = g * y * (1.0f - y);
-              }
-              d[i] = g;
-            } else {
-              d[i] = 0.0f;
-            }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) d[i] = 0.0f;
-        }
-        Frag tmp[M::STEPS32];
-        hn_zero_frags(tmp, M::STEPS32);
-        if constexpr (BF16) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) tmp[0][i] = (__bf16)d[i];  // h==0, j<4 <-> features 0..3
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) tmp[i] = d[i];             // step q, h==0 <-> feature q
-        }
-        if (a.training && w[7] >= 0 && wave_valid) hn_stash<BF16, SZ>(tmp, hn_slot_base<BF16, SZ>(a, w[7], 1, blk), 0, lane);
-#pragma unroll
-        for (int s = 0; s < M::STEPS32; ++s) {
-          if (to2) cur2[s] = tmp[s];
-          else cur[s] = tmp[s];
-        }
-      } else if (WIDE && code == HN_BOP_LOAD_WIDE) {
-        const int n = w[3] & 0xffff, NT = w[4], dact = (w[3] >> 16) & 15;
-        const HnSrc s = a.src[w[1]];
-        unsigned nbits = 0xffffffffu;  // complement of the mask word: set = keep
-        char* dz_base = (a.training && wave_valid) ? hn_slot_base<BF16>(a, w[7], NT, blk) : nullptr;
-        const bool has_mask = w[5] >= 0 && dact != HN_ACT_SOFTPLUS;              // (softplus: w5 = p1)
-        const bool from_y = (dact == HN_ACT_ELU || dact == HN_ACT_SOFTPLUS) && wave_valid;
-        const char* y_base = from_y ? hn_slot_base<BF16>(a, w[7], NT, blk) : nullptr;  // y, stashed by the forward
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if (t < NT) {
-            if (has_mask && !(t & 1)) {  // output activation was relu / leaky relu: dZ = dY * f'(mask)
-              nbits = wave_valid ? ~hn_mask_base(a, w[5], (NT + 1) >> 1, blk, lane)[(t >> 1) * 64 + lane] : 0u;
-            }
-            f32x16 v;
-            if (dact == 0) {
-#pragma unroll
-              for (int i = 0; i < 16; ++i) {
-                const int row = 32 * t + hn_rho(i, h);
-                const bool keep = hn_keep_mask(nbits, t & 1, i) != 0;
-                v[i] = (valid && keep && row < n) ? s.ptr[(size_t)p * s.ld + w[2] + row] : 0.0f;
-              }
-            } else {
-              const float p0 = __int_as_float(w[6]), p1 = __int_as_float(w[5]);
-              f32x16 y = {0};
-              if (y_base != nullptr) y = hn_unstash<BF16>(y_base, t, lane);
-#pragma unroll
-              for (int i = 0; i < 16; ++i) {
-                const int row = 32 * t + hn_rho(i, h);
-                const float g = (valid && row < n) ? s.ptr[(size_t)p * s.ld + w[2] + row] : 0.0f;
-                float d = 1.0f;
-                if (dact == HN_ACT_LEAKY_RELU) d = hn_keep_mask(nbits, t & 1, i) != 0 ? 1.0f : p0;
-                else d = hn_dact_y<BF16>(dact, y[i], p0, p1);
-                v[i] = g * d;
-              }
-            }
-            hn_acc_to_frags(v, cur + t * M::STEPS32);
-            if (dz_base != nullptr) hn_stash<BF16>(cur + t * M::STEPS32, dz_base, t, lane);
-          }
-        }
-      } else if (code == HN_BOP_LAYER) {
-        const int K32 = w[1] & 255, K32b = (w[1] >> 8) & 255, NT = (w[1] >> 16) & 255;
-        const bool has_mask = w[4] >= 0;
-        const bool do_stash = a.training && w[5] >= 0 && wave_valid;
-        char* dz_base = do_stash ? hn_slot_base<BF16, SZ>(a, w[5], NT, blk) : nullptr;
-        const int dact = w[2];      // 0: relu' from the mask (or nothing); else HN_ACT_LEAKY_RELU / ELU / SOFTPLUS
-        const char* y_base = (!S8 && (dact == HN_ACT_ELU || dact == HN_ACT_SOFTPLUS) && wave_valid)
-                                 ? hn_slot_base<BF16>(a, w[6], NT, blk) : nullptr;
-        unsigned nbits = 0xffffffffu;
-        unsigned mbits[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};  // complemented words: set = keep
-        if (has_mask) {
-          if (mnext_ready) {   // fetched while the previous op ran (hn_prefetch_masks): no memory wait here
-#pragma unroll
-            for (int dd = 0; dd < 4; ++dd) mbits[dd] = ~mnext[dd];
-          } else {             // all relu masks of the layer up front: one VMEM wait per layer, none per tile
-            const uint32_t* mb = hn_mask_base(a, w[4], (NT + 1) >> 1, blk, lane);
-#pragma unroll
-            for (int dd = 0; dd < 4; ++dd)
-              if (2 * dd < NT)
-                mbits[dd] = wave_valid ? ~mb[dd * 64 + lane] : 0u;
-          }
-        }
-        mnext_ready = false;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if (t < NT) {
-            f32x16 acc;
-            hn_init_acc(acc, nullptr, t, h);
-            hn_gemm_k<BF16>(acc, cur, K32, ws);
-            if (K32b) hn_gemm_blocks<BF16, 1>(acc, cur2, ws);
-            // the next layer's mask words, issued behind this tile's chunk barrier so that they have the rest of
-            // the layer to arrive (the backward machine used to stall ~3 us on them at the top of every layer)
-            if (t == 0) mnext_ready = hn_prefetch_masks(a, w_next, blk, lane, wave_valid, mnext);
-            HN_STAMP(2);
-            if (!(t & 1)) nbits = mbits[t >> 1];
-            // dZ of padded points is zero from the LOAD ops on and stays zero: no `valid` select here
-            if (dact == 0) {
-#pragma unroll
-              for (int i = 0; i < 16; ++i)
-                acc[i] = __int_as_float(__float_as_int(acc[i]) & hn_keep_mask(nbits, t & 1, i));
-            } else if (dact == HN_ACT_LEAKY_RELU) {
-              const float p0 = __int_as_float(w[3]);
-#pragma unroll
-              for (int i = 0; i < 16; ++i)
-                if (hn_keep_mask(nbits, t & 1, i) == 0) acc[i] *= p0;
-            } else if (y_base != nullptr) {
-              const f32x16 y = hn_unstash<BF16>(y_base, t, lane);
-              const float p0 = __int_as_float(w[3]), p1 = __int_as_float(w[7]);
-#pragma unroll
-              for (int i = 0; i < 16; ++i) acc[i] *= hn_dact_y<BF16>(dact, y[i], p0, p1);
-            }
-            hn_acc_to_frags(acc, nxt + t * M::STEPS32);
-            if (do_stash) {
-              if constexpr (SZ != 0) hn_stash8_acc<SZ>(acc, dz_base, t, lane);
-              else hn_stash<BF16, SZ>(nxt + t * M::STEPS32, dz_base, t, lane);
-            }
-            HN_STAMP(4);
-          }
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-          if (t < NT)
-#pragma unroll
-            for (int s = 0; s < M::STEPS32; ++s) cur[t * M::STEPS32 + s] = nxt[t * M::STEPS32 + s];
-      } else if (code == HN_BOP_AUX) {
-        // gradient of generated features: per 32-feature tile tmp = W_aux^T . dZ, then the chain rule
-        const int K32 = w[1] & 255, K32b = (w[1] >> 8) & 255, nG = (w[1] >> 16) & 255;
-        // w2: bit tt = tile tt holds a feature that differentiates into a source (the others are neither in the weight
-        // stream nor computed: encoders of plain inputs in front of a GLO row, padding); bit 8 + tt = one of them is
-        // trigonometric (a tile of identity features only — GLO rows — takes W^T dZ as it is: d feature / dx = 1)
-        const int tiles = w[2];
-        bool first = true;
-        mnext_ready = false;
-        for (int tt = 0; tt < 2 * nG; ++tt) {
-          if (!((tiles >> tt) & 1)) continue;
-          f32x16 acc;
-          hn_init_acc(acc, nullptr, 0, h);
-          hn_gemm_k<BF16>(acc, cur, K32, ws);
-          if (K32b) hn_gemm_blocks<BF16, 1>(acc, cur2, ws);
-          if (first) mnext_ready = hn_prefetch_masks(a, w_next, blk, lane, wave_valid, mnext);
-          first = false;
-          // chain rule per feature, then the reduction over the features of each source component as one more
-          // matrix product: dacc[slot][point] += S[slot][feature] . G[feature][point]  (S: 0/1 selection block that
-          // the host put in the weight stream right behind this tile's weights).  No LDS accumulators: an LDS
-          // atomic after an LDS-DMA makes the compiler drain vmcnt, i.e. the weight prefetch.
-          const HnFeat* ft = feat_lds + w[3] + 32 * tt;
-          if ((tiles >> (8 + tt)) & 1) {
-            if constexpr (BF16) {
-              // accumulator register i is feature rho(i, h): four runs of 4 consecutive table entries
-              const HnDFeat* dft = dfeat_lds + w[3] + 32 * tt + 4 * h;
-              const char* srcv_r = reinterpret_cast<const char*>(srcv) + 4 * r;
-#pragma unroll
-              for (int q4 = 0; q4 < 4; ++q4) {
-                float g[4];
-                hn_feature_grads4(dft + 8 * q4, srcv_r, g);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[4 * q4 + e] *= g[e];
-              }
-            } else {
-#pragma unroll
-              for (int i = 0; i < 16; ++i) acc[i] *= hn_feature_grad<BF16>(ft[hn_rho(i, h)], srcv, r);
-            }
-          }
-          Frag gfr[M::STEPS32];
-          hn_acc_to_frags(acc, gfr);
-          hn_gemm_blocks<BF16, 1>(dacc, gfr, ws);
-          HN_STAMP(5);
-        }
-      }
-    }
-    // source gradients of this block -> global
-    if (a.n_dsrc > 0 && a.dsrc != nullptr && p0 < a.n_points) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int slot = hn_rho(i, h);
-        if (slot < a.n_dsrc) a.dsrc[(size_t)p0 * a.n_dsrc + slot] = S8 ? dacc[i] * dz_unscale : dacc[i];
-      }
-    }
-    // GLOEmbed backward (modules.py:155-167 under autograd): the block's 32 points belong to one ray, so the
-    // gradient of the gathered row is the sum over the lanes of each half, added once per block and component
-    if (a.embed_reg_mask != 0 && wave_valid) {
-      const long long erow = a.embed_idx[(blk * 32) / a.samples_per_ray];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        if (a.embed_reg_mask & (1 << i)) {
-          float v = valid ? (S8 ? dacc[i] * dz_unscale : dacc[i]) : 0.0f;
-#pragma unroll
-          for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m, 64);
-          const int col = a.embed_col[hn_rho(i, h)];
-          if (r == 0 && col >= 0) {
-            // (the opt-in 8-bit-stash build keeps the atomics: the host never hands it a partial buffer, and the extra
-            // pointer pushed that build's allocation into scratch)
-            if (!S8 && a.embed_partial != nullptr) a.embed_partial[(size_t)blk * a.embed_dim + col] = v;
-            else if (erow >= 0 && erow < a.embed_rows) atomicAdd(a.embed_grad + (size_t)erow * a.embed_dim + col, v);
-          }
-        }
-      }
-    }
-  }
-  hn_timeline_end(a.timeline);
+  constexpr bool ACTS = true;
+#include "hn_mlp_bwd_body.h"
+}
+template <bool BF16 = true, bool WIDE = false, bool S8 = false, bool ACTS = false>
+__global__ __launch_bounds__(ModeT<true>::WAVES * 64, 2) void hn_mlp_bwd_relu_kernel(const HnMlpArgs a) {
+  static_assert(BF16 && !WIDE && !S8 && !ACTS, "the lean build is bf16, render-level, ReLU-only");
+#include "hn_mlp_bwd_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1843,6 +1427,8 @@ static void hn_allow_big_lds() {
   HN_BIG((hn_mlp_fwd_kernel<false, 3, true, true>)); HN_BIG((hn_mlp_fwd_kernel<false, 3, true, false>));
   HN_BIG((hn_mlp_fwd_kernel<true, 2, false, true, true>)); HN_BIG((hn_mlp_fwd_kernel<true, 3, false, true, true>));
   HN_BIG((hn_mlp_bwd_kernel<true, false, true>)); HN_BIG((hn_wgrad_kernel<true, true>));
+  HN_BIG((hn_mlp_fwd_relu_kernel<2, true>)); HN_BIG((hn_mlp_fwd_relu_kernel<2, false>));
+  HN_BIG((hn_mlp_fwd_relu_kernel<3, true>)); HN_BIG((hn_mlp_bwd_relu_kernel<>));
 #undef HN_BIG
   (void)hipFuncSetAttribute((const void*)hn_mlp_bwd_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
   (void)hipFuncSetAttribute((const void*)hn_mlp_bwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
@@ -1891,7 +1477,7 @@ static int hn_check_args(const HnMlpArgs* a) {
   if (a->ops == nullptr || a->wstream == nullptr) return -3;
   if (a->mode != HN_MODE_BF16 && a->mode != HN_MODE_F32 && a->mode != HN_MODE_BF16_S8) return -4;
   // the 8-bit stash exists in the render-level training builds only (no stand-alone-module paths)
-  if (a->mode == HN_MODE_BF16_S8 && a->training && a->wide_ops != 0) return -4;
+  if (a->mode == HN_MODE_BF16_S8 && a->training && (a->wide_ops & 3) != 0) return -4;
   if (a->mode == HN_MODE_BF16_S8 && (a->dz_scale_log2 < -60 || a->dz_scale_log2 > 60)) return -5;
   if (a->n_dsrc < 0 || a->n_dsrc > HN_DSRC_COMPS) return -5;
   if (a->n_bias < 0 || a->n_feat < 0 || a->n_comps < 0 || a->n_comps > HN_MAX_COMPS) return -5;
@@ -1899,6 +1485,10 @@ static int hn_check_args(const HnMlpArgs* a) {
   if (a->n_comps > 0 && a->comps == nullptr) return -3;
   return 0;
 }
+
+// HnMlpArgs.wide_ops bit 2 (every layer ReLU or linear) with bits 0 and 1 clear, plain bf16: the launch takes the lean
+// ReLU-only build.  A caller that does not know the bit leaves it clear and gets the generic kernels.
+static bool hn_relu_only(const HnMlpArgs* a) { return a->mode == HN_MODE_BF16 && (a->wide_ops & 7) == 4; }
 
 // Host-only: the extent of `stash` and `masks` an op program touches for n_points points (the kernels do no
 // bounds checks of their own; a host that did not compile the program itself sizes its buffers with this).
@@ -1968,8 +1558,16 @@ extern "C" int hn_mlp_forward(const HnMlpArgs* a, hnStream_t stream) {
   if (a->mode == HN_MODE_BF16_S8 && a->training) {
     if (a->max_groups <= 2) hipLaunchKernelGGL((hn_mlp_fwd_kernel<true, 2, false, true, true>), grid_b, blk_b, lds, st, *a);
     else hipLaunchKernelGGL((hn_mlp_fwd_kernel<true, 3, false, true, true>), grid_b, blk_b, lds, st, *a);
+  } else if (bf && hn_relu_only(a)) {
+    // every layer ReLU or linear, no stand-alone-module paths: the lean builds
+    const bool train = a->training != 0;
+#define HN_FWD_RELU(G, T) hipLaunchKernelGGL((hn_mlp_fwd_relu_kernel<G, T>), grid_b, blk_b, lds, st, *a)
+    if (a->max_groups <= 2) { if (train) HN_FWD_RELU(2, true); else HN_FWD_RELU(2, false); }
+    else if (train) HN_FWD_RELU(3, true);
+    else HN_FWD(3, false, false);      // no lean build of this one (it would need scratch, like the generic)
+#undef HN_FWD_RELU
   } else if (bf) {
-    const bool extra = a->wide_ops != 0, train = a->training != 0;
+    const bool extra = (a->wide_ops & 3) != 0, train = a->training != 0;
     if (a->max_groups <= 2) {
       if (extra) { if (train) HN_FWD(2, true, true); else HN_FWD(2, true, false); }
       else { if (train) HN_FWD(2, false, true); else HN_FWD(2, false, false); }
@@ -1998,6 +1596,9 @@ extern "C" int hn_mlp_backward(const HnMlpArgs* a, hnStream_t stream) {
     const size_t lds = 2 * HN_CHUNK_UNITS * 1024 + flds + (size_t)a->n_feat * 16 + (size_t)WB * a->n_comps * 32 * 4;
     if (a->mode == HN_MODE_BF16_S8 && a->training)
       hipLaunchKernelGGL((hn_mlp_bwd_kernel<true, false, true>), dim3(hn_grid_for(a->n_points, WB * 32)), dim3(WB * 64), lds,
+                         (hipStream_t)stream, *a);
+    else if (hn_relu_only(a))
+      hipLaunchKernelGGL((hn_mlp_bwd_relu_kernel<>), dim3(hn_grid_for(a->n_points, WB * 32)), dim3(WB * 64), lds,
                          (hipStream_t)stream, *a);
     else if (a->wide_ops & 1)
       hipLaunchKernelGGL((hn_mlp_bwd_kernel<true, true>), dim3(hn_grid_for(a->n_points, WB * 32)), dim3(WB * 64), lds,

@@ -55,6 +55,10 @@ def mode_consts(mode: int):
 # 57344) keeps gradients between 2^-30 and 0.87 (mean-reduced losses put them around 1e-7 .. 1e-3); the weight-gradient
 # kernel divides the sums by it again.  A power of two: exact everywhere but in the 8-bit rounding itself.
 DZ_SCALE_LOG2 = int(os.environ.get("HN_DZ_SCALE_LOG2", 16))
+# HN_FORCE_GENERIC=1: never announce a ReLU-only program (HnMlpArgs.wide_ops bit 2), so every launch takes the generic
+# machine kernels.  The lean builds compute the same bits; this is the A/B handle and what the bit-identity test toggles.
+FORCE_GENERIC = os.environ.get("HN_FORCE_GENERIC", "0") not in ("", "0")
+WIDE_OPS_RELU_ONLY = 4      # HnMlpArgs.wide_ops bit 2 (include/hn_kernels.h)
 
 
 # --------------------------------------------------------------------------------------------
@@ -439,6 +443,13 @@ class Program:
         if ly.act in ("none", "relu"):
             return 0, 0, 0
         return ACT_CODES[ly.act], f32_bits(ly.act_params[0]), f32_bits(ly.act_params[1])
+
+    def relu_only_bit(self) -> int:
+        """HnMlpArgs.wide_ops bit 2: every layer is ReLU or linear, so the launches may take the lean ReLU-only builds of
+        the machine kernels (0 under HN_FORCE_GENERIC)."""
+        if FORCE_GENERIC:
+            return 0
+        return WIDE_OPS_RELU_ONLY if all(ly.act in ("none", "relu") for ly in self.layers) else 0
 
     @property
     def y_acts(self) -> bool:
@@ -1392,7 +1403,7 @@ class MlpRunner:
         a.comps, a.n_comps = d.comps.data_ptr(), len(self.prog.comp_map)
         wide = any(ly.out is not None and ly.out.wide for ly in self.prog.layers)
         direct = any(f.kind != L.HN_FEAT_ZERO and (f.src, f.comp) not in self.prog.comp_map for f in self.prog.feat_table)
-        a.wide_ops = (1 if wide else 0) | (2 if direct else 0)
+        a.wide_ops = (1 if wide else 0) | (2 if direct else 0) | self.prog.relu_only_bit()
         a.dz_scale_log2 = DZ_SCALE_LOG2 if mode == L.HN_MODE_BF16_S8 else 0
         a.n_trig_comps = min(len(self.prog.comp_map), max(1, self.prog.n_trig_comps))
         # hi + lo planes of x / 2pi for the encoded components when the forward's LDS budget allows (158 KiB: ring +

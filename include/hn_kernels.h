@@ -201,7 +201,11 @@ typedef struct {
   int32_t wide_ops;       /* bit 0: the op program holds HN_OP_OUT_WIDE / HN_BOP_LOAD_WIDE ops; bit 1: its feature table
                              holds HN_FEAT_ID_DIRECT entries (layers flagged HN_LAYER_DIRECT).  Forward launches take
                              the kernel build that carries those paths if either bit is set, backward launches if bit 0
-                             is; 0 selects the builds without them (what every render-level program runs: no scratch) */
+                             is; 0 selects the builds without them (what every render-level program runs: no scratch).
+                             bit 2: every layer of the program is ReLU or linear (no LeakyReLU / ELU / Softplus op words).
+                             With bit 2 set, bits 0 and 1 clear and mode HN_MODE_BF16 the launches take the lean ReLU-only
+                             builds (hn_mlp_fwd_relu_kernel / hn_mlp_bwd_relu_kernel: same results bit for bit, less code);
+                             a caller that leaves the bit clear gets the generic builds, which run every program */
   int32_t dz_scale_log2;  /* HN_MODE_BF16_S8, backward: the machine carries 2^dz_scale_log2 * dZ (exact: a power of two)
                              so that the e5m2 stash keeps small gradients; source / embedding gradients leave unscaled */
   int32_t trig_lo_planes; /* 1: the lo planes are staged (exactly reduced sine arguments); 0: hi only + one shared zero
