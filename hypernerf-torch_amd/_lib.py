@@ -22,7 +22,7 @@ PRODUCT_LIB_PATH = os.path.join(CSRC, "libhn_hip.so")
 LIB_PATH = os.environ.get("HN_LIB_PATH") or PRODUCT_LIB_PATH
 SOURCES = ["hn_mlp.hip", "hn_render.hip", "hn_data.hip", "hn_calib.hip", "hn_optim.hip", "hn_metrics.hip", "hn_msssim.hip",
            "hn_geometry.hip", "hn_regularizers.hip", "hn_gif.hip", "hn_simplify.hip", "hn_mesh_render.hip", "hn_fusion.hip",
-           "hn_mesh_distance.hip", "hn_lpips.hip", "hn_registration.hip", "hn_texture.hip"]
+           "hn_mesh_distance.hip", "hn_lpips.hip", "hn_registration.hip", "hn_texture.hip", "hn_occupancy.hip"]
 CSRC_HEADERS = ["hn_common.h", "hn_pack.h", "hn_camera.h", "hn_window.h", "hn_wave.h", "hn_mlp_fwd_body.h", "hn_mlp_bwd_body.h"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "hn_kernels.h")
 BUILD_MACROS = ("HN_REDUCE_SPLIT", "HN_BF16_WAVES", "HN_PROF", "HN_CHUNK_UNITS", "HN_WGRAD_AUX", "HN_WGRAD_STAGES", "HN_WGRAD_MAXSLOT", "HN_BWD_PIPE")     # build-time tuning knobs (A/B experiments)

@@ -26,6 +26,7 @@ from .ops.lpips import *                    # noqa: F401,F403
 from .ops.mesh import *                     # noqa: F401,F403
 from .ops.mesh_render import *              # noqa: F401,F403
 from .ops.metrics import *                  # noqa: F401,F403
+from .ops.occupancy import *                # noqa: F401,F403
 from .ops.registration import *             # noqa: F401,F403
 from .ops.simplify import *                 # noqa: F401,F403
 from .ops.texture import *                  # noqa: F401,F403

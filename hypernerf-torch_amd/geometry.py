@@ -73,6 +73,16 @@ mesh and `write_obj` writes mesh, UVs and the image for a viewer.
     texture = bake_field_texture(model, small, atlas, frame_id=12)        # (H_t, W_t, 3) uint8
     img = render_textured_mesh(small, atlas, texture, rays, cam, (W, H))
     write_obj("frame12.obj", small, atlas, texture)                        # + frame12.mtl, frame12.png
+
+Rendering faster: most samples of a ray lie in air.  `occupancy_grid` turns the density lattice of a frame into one bit per
+lattice cell (csrc/hn_occupancy.hip), `clip_rays` cuts every ray to the part of [near, far] between the
+first and the last occupied cell it crosses and re-parametrises it so that an unchanged model samples exactly that part,
+`unclip` maps depths back, and inference.render_image / evaluate_images, depth_images_from_field and extract_mesh_fused
+take `occupancy=` and do all three; `OccupancyCache` builds the grid of each frame on first use.
+
+    occ = occupancy_grid(model, bounds, 128, frame_id=12, sigma_min=0.5, dilate=1)
+    occupancy_fraction(occ)                                               # the occupied share of the cells
+    img = inference.render_image(model, rays, occupancy=occ)             # rays of frame 12
 """
 from __future__ import annotations
 
@@ -83,6 +93,8 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .ops.occupancy import (OccupancyCache, clip_rays, occupancy_fraction, occupancy_from_density, occupancy_grid,      # noqa: F401
+                            occupancy_union, unclip)
 
 ROW = 64      # lattice points per row of a query: one row = one "ray" of the programs (one id, one view direction)
 
@@ -408,13 +420,18 @@ def fuse_depth(depths: torch.Tensor, cameras, bounds, resolution, trunc: Optiona
 @torch.no_grad()
 def depth_images_from_field(model, cameras, image_wh, frame_id: int, near: float, far: float, acc_min: float = 0.5,
                             acc_free: float = 0.05, normalize: bool = True, level: str = 'fine',
-                            chunk: int = 16384, *, ndc: bool = False) -> torch.Tensor:
+                            chunk: int = 16384, *, ndc: bool = False, occupancy=None) -> torch.Tensor:
     """(N, H, W) fp32 depth images of the field at frame `frame_id` through `cameras` (N, 24), in fuse_depth's convention.
     Per camera: camera_rays(near, far), a ninth column holding frame_id (as the rays of a dataset carry it), then
     inference.render_image(keys=('depth', 'acc')).  Where acc >= acc_min the pixel is a surface at depth / acc
     (`normalize`: the expected distance of the mass the ray did meet) or at depth; where acc <= acc_free the ray hit
     nothing: +inf; in between nothing is known: 0.  The two thresholds are the caller's to set: they decide what counts
-    as seen, and no value suits every scene.  ndc=True (a model trained on NDC rays) is refused."""
+    as seen, and no value suits every scene.  ndc=True (a model trained on NDC rays) is refused.
+    occupancy: an occupancy dict (occupancy_grid) or an OccupancyCache, asked for `frame_id`; the rays are then clipped to
+    the occupied cells before they are rendered (inference.render_image's `occupancy`).  With both ends
+    clipped the sample a model with use_sample_at_infinity treats as 'at infinity' sits at the exit of the last occupied
+    cell, not at `far`; a lattice can miss structure thinner than a cell (sigma_min and dilate are the guard); a model
+    with use_linear_disparity spaces its samples over the clipped interval.  None: the launches are unchanged."""
     from . import inference
     what = "depth_images_from_field"
     _refuse_ndc(ndc, what)
@@ -424,11 +441,14 @@ def depth_images_from_field(model, cameras, image_wh, frame_id: int, near: float
     if not 0.0 <= acc_free < acc_min <= 1.0:
         raise ValueError(f"{what}: the thresholds need 0 <= acc_free < acc_min <= 1, got acc_free {acc_free}, acc_min {acc_min}")
     device = next(model.parameters()).device
+    occ_kw = {}
+    if occupancy is not None:
+        occ_kw['occupancy'] = occupancy.get(int(frame_id)) if isinstance(occupancy, OccupancyCache) else occupancy
     out = torch.empty((cameras.shape[0], h, w), dtype=torch.float32, device=device)
     for n, cam in enumerate(cameras.to(device)):
         rays = camera_rays(cam, w, h, near, far)
         rays = torch.cat([rays, torch.full((rays.shape[0], 1), float(int(frame_id)), device=device)], dim=1)
-        field = inference.render_image(model, rays, chunk=chunk, level=level, keys=('depth', 'acc'))
+        field = inference.render_image(model, rays, chunk=chunk, level=level, keys=('depth', 'acc'), **occ_kw)
         depth, acc = field['depth'].reshape(h, w).float(), field['acc'].reshape(h, w).float()
         surface = depth / acc if normalize else depth
         out[n] = torch.where(acc >= acc_min, surface,
@@ -470,13 +490,14 @@ def tsdf_isosurface(volume: Dict[str, torch.Tensor], bounds, observed_only: bool
 
 def extract_mesh_fused(model, bounds, resolution, frame_id: int, cameras, image_wh, near: float, far: float,
                        trunc: Optional[float] = None, min_faces: Optional[int] = None, keep_largest: Optional[int] = None,
-                       simplify=None, colors=None, *, ndc: bool = False, **kw) -> Dict[str, torch.Tensor]:
+                       simplify=None, colors=None, *, ndc: bool = False, occupancy=None, **kw) -> Dict[str, torch.Tensor]:
     """The surface of frame `frame_id` where the field renders it, with no iso level to guess:
     tsdf_isosurface(fuse_depth(depth_images_from_field(model, cameras, image_wh, frame_id, near, far), cameras, bounds,
     resolution, trunc), bounds), then extract_mesh's tail: filter_mesh(min_faces, keep_largest), simplify_mesh by
     `simplify` lattice spacings, 'colors' = vertex_colors(view=colors).  Of **kw, acc_min / acc_free / normalize go to
     depth_images_from_field, level / chunk to it and to vertex_colors, render_opts to vertex_colors.  ndc=True is
-    refused."""
+    refused.  occupancy (a dict or an OccupancyCache) goes to depth_images_from_field: the depth maps are rendered with
+    empty space skipped."""
     _refuse_ndc(ndc, "extract_mesh_fused")
     factor = None if simplify is None else _simplify_factor(simplify)
     field_kw = {k: kw[k] for k in ('acc_min', 'acc_free', 'normalize', 'level', 'chunk') if k in kw}
@@ -484,6 +505,8 @@ def extract_mesh_fused(model, bounds, resolution, frame_id: int, cameras, image_
     unknown = set(kw) - set(field_kw) - set(color_kw)
     if unknown:
         raise TypeError(f"extract_mesh_fused: unexpected keyword arguments {sorted(unknown)}")
+    if occupancy is not None:
+        field_kw['occupancy'] = occupancy
     depths = depth_images_from_field(model, cameras, image_wh, frame_id, near, far, **field_kw)
     mesh = tsdf_isosurface(fuse_depth(depths, cameras, bounds, resolution, trunc), bounds)
     return _finish_mesh(mesh, model, bounds, resolution, frame_id, factor, colors, min_faces, keep_largest, color_kw)

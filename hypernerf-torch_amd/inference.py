@@ -37,10 +37,42 @@ def batched_inference(model, rays_dict, N_samples=None, N_importance=None, use_d
 
 @torch.no_grad()
 def render_image(model, rays: torch.Tensor, chunk: int = 16384, level: str = 'fine',
-                 keys: Sequence[str] = ('rgb', 'depth', 'acc'), group=None) -> Dict[str, torch.Tensor]:
+                 keys: Sequence[str] = ('rgb', 'depth', 'acc'), group=None, occupancy=None, near=None, far=None,
+                 clip_far: bool = True, miss: str = 'render', miss_rgb=None) -> Dict[str, torch.Tensor]:
     """rays (N, 8|9) of one image -> {key: (N, ...)} for the requested per-ray outputs of `level`.
     With torch.distributed initialised every rank renders a contiguous 1/world slice and the pixels are gathered
-    with one all-gather per key (slices are padded to equal length)."""
+    with one all-gather per key (slices are padded to equal length).
+
+    `occupancy` (a dict of occupancy_grid / occupancy_from_density; None: everything below is off and the launches are
+    today's) skips empty space: this rank's slice is clipped once (ops.occupancy.clip_rays) to the part
+    of [near, far] between the first and the last occupied cell of each ray, the re-parametrised rows are rendered with
+    the ORIGINAL directions as 'viewdirs' — the model spends its whole sample budget inside the clipped interval — and
+    the results are mapped back to true distances (ops.occupancy.unclip: depth through the sum of the level's weights).
+    `keys` may then hold 'rgb', 'depth', 'acc' and 'med_depth' only.  near / far: the interval the model samples,
+    model.near / model.far by default; given explicitly they are also handed to the model's forward.
+    clip_far: the interval ends at the exit of the last occupied cell, and the sample HyperNeRF treats as 'at infinity'
+    (use_sample_at_infinity) then sits there, not at `far`; clip_far=False clips the front only and keeps it at `far`.
+    miss='render' renders the rays that meet no occupied cell unclipped, exactly as without an occupancy; miss='skip'
+    sends only the hit rays to the model and fills the others with rgb = miss_rgb (three floats or a float, default 0),
+    depth, med_depth and acc 0: the caller asserts that there is nothing outside the grid.
+    A lattice can miss structure thinner than a cell: sigma_min and dilate of the occupancy are the guard against that.
+    A model with use_linear_disparity places its samples linearly in disparity of the re-parametrised z, i.e. over the
+    clipped interval mapped onto [near, far], not in the disparity of the true distance."""
+    if occupancy is not None or miss != 'render':
+        from .ops import occupancy as occ_ops
+        if miss not in ('render', 'skip'):
+            raise ValueError(f"render_image: miss must be 'render' or 'skip', got {miss!r}")
+        if occupancy is None:
+            raise ValueError("render_image: miss='skip' needs an occupancy")
+        unknown = [k for k in keys if k not in occ_ops.OCC_KEYS]
+        if unknown:
+            raise ValueError(f"render_image: with an occupancy the keys are {occ_ops.OCC_KEYS}, got {unknown}")
+        fill = torch.as_tensor(0.0 if miss_rgb is None else miss_rgb, dtype=torch.float32).reshape(-1)
+        if fill.numel() not in (1, 3):
+            raise ValueError(f"render_image: miss_rgb must be a number or three numbers, got {miss_rgb!r}")
+        model_kw = {k: float(v) for k, v in (('near', near), ('far', far)) if v is not None}
+        t_near = model.near if near is None else near
+        t_far = model.far if far is None else far
     n = rays.shape[0]
     world = torch.distributed.get_world_size(group) if hdist.dist.is_available() and hdist.dist.is_initialized() else 1
     rank = torch.distributed.get_rank(group) if world > 1 else 0
@@ -48,11 +80,36 @@ def render_image(model, rays: torch.Tensor, chunk: int = 16384, level: str = 'fi
     per = -(-n // world)                                  # padded slice length, equal on all ranks
     mine = rays[lo:hi]
     outs = {k: [] for k in keys}
-    for start in range(0, mine.shape[0], chunk):
-        rd = model_utils.prepare_ray_dict(mine[start:start + chunk])
-        res = model(rd, dict(_EXTRA))[level]
-        for k in keys:
-            outs[k].append(res[k])
+    if occupancy is None:
+        for start in range(0, mine.shape[0], chunk):
+            rd = model_utils.prepare_ray_dict(mine[start:start + chunk])
+            res = model(rd, dict(_EXTRA))[level]
+            for k in keys:
+                outs[k].append(res[k])
+    else:
+        clip = occ_ops.clip_rays(mine, occupancy, t_near, t_far, clip_far=clip_far)
+        rows, dirs, affine = clip['rays'], mine[:, 3:6], clip['affine']
+        if miss == 'skip':
+            kept = torch.nonzero(clip['hit']).reshape(-1)
+            rows, dirs, affine = rows[kept], dirs[kept], affine[kept]
+        need = [k for k in keys] + (['weights'] if 'depth' in keys else [])
+        for start in range(0, rows.shape[0], chunk):
+            rd = model_utils.prepare_ray_dict(rows[start:start + chunk])
+            rd['viewdirs'] = dirs[start:start + chunk]
+            res = model(rd, dict(_EXTRA), **model_kw)[level]
+            res = occ_ops.unclip({k: res[k] for k in need}, affine[start:start + chunk])
+            for k in keys:
+                outs[k].append(res[k])
+        if miss == 'skip':
+            for k in keys:
+                shape = (mine.shape[0], 3) if k == 'rgb' else (mine.shape[0],)
+                full = torch.zeros(shape, dtype=torch.float32, device=rays.device)
+                if k == 'rgb':
+                    full[:] = fill.to(rays.device)
+                if outs[k]:
+                    got = torch.cat(outs[k], dim=0)
+                    full[kept] = got.reshape((kept.shape[0],) + shape[1:]).to(full.dtype)
+                outs[k] = [full] if mine.shape[0] else []
     result = {}
     for k in keys:
         if outs[k]:
@@ -515,11 +572,29 @@ def validation_stack(gt: torch.Tensor, pred: torch.Tensor, depth: torch.Tensor, 
     return torch.stack(planes + [depth.float().cpu()])
 
 
+def _image_occupancy(occupancy, rays: torch.Tensor, i: int):
+    """The occupancy dict of image i: `occupancy` itself, or an OccupancyCache's grid of the frame in column 8 of the rays."""
+    from .ops.occupancy import OccupancyCache
+    if not isinstance(occupancy, OccupancyCache):
+        return occupancy
+    if rays.dim() != 2 or rays.shape[1] < 9:
+        raise ValueError(f"evaluate_images: an OccupancyCache needs the frame id in column 8 of the rays; image {i} has "
+                         f"rays of shape {tuple(rays.shape)}")
+    if rays.shape[0] == 0:
+        raise ValueError(f"evaluate_images: image {i} has no rays to read a frame id from")
+    first, last = (float(v) for v in torch.stack([rays[:, 8].min(), rays[:, 8].max()]).tolist())      # one host read
+    if first != last or first != int(first):
+        raise ValueError(f"evaluate_images: image {i} holds frame ids {first} .. {last}; an OccupancyCache needs one "
+                         "integer id per image")
+    return occupancy.get(int(first))
+
+
 @torch.no_grad()
 def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False, save_dir=None, group=None,
                     image_format: str = "png", save_depth: bool = False, depth_format: str = "pfm",
                     use_valid_mask: bool = False, ms_ssim: bool = False, save_gif=None, gif_fps: float = 30,
-                    gif_palette: str = "global", save_depth_gif: bool = False, lpips=None) -> Dict:
+                    gif_palette: str = "global", save_depth_gif: bool = False, lpips=None, occupancy=None,
+                    clip_far: bool = True) -> Dict:
     """The per-image loop of the reference's eval.py:145-178 on the GPU: for every sample {'rays': (H*W, 8|9),
     'rgbs': (H*W, 3) optional, 'hw': (H, W) optional} render the fine level in chunks, form the (H, W, 3) image,
     its 8-bit version (eval.py:165 `(img*255).astype(uint8)`) and, when ground truth is present, the PSNR
@@ -542,7 +617,12 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
     image with ground truth, on the same views as the SSIM: the result then also has 'ms_ssims': [float] and
     'mean_ms_ssim': float | None.  Off by default: the result and the work done are unchanged.
     `lpips` = an LpipsWeights (losses.load_lpips) on the model's device adds LPIPS (losses.lpips) the same way, on the same
-    views: 'lpips': [float] and 'mean_lpips': float | None.  None by default: the result and the work done are unchanged."""
+    views: 'lpips': [float] and 'mean_lpips': float | None.  None by default: the result and the work done are unchanged.
+    `occupancy` skips empty space in every image (render_image's `occupancy` and `clip_far`; missed rays are rendered
+    unclipped): an occupancy dict serves all images; an ops.occupancy.OccupancyCache gives each image the grid of its
+    frame, the id in column 8 of its rays, which must be one value per image (8-column rays are refused).  A model
+    trained with use_sample_at_infinity has learnt the colour of its last sample at `far`: clip_far=False keeps it there
+    (DESIGN.md 3.18 has the measurement).  None by default: the result and the work done are unchanged."""
     if image_format not in ("png", "ppm"):
         raise ValueError("image_format: 'png' or 'ppm'")
     if depth_format not in ("pfm", "bytes"):
@@ -563,7 +643,11 @@ def evaluate_images(model, images, chunk: int = 16384, white_back: bool = False,
         lut = jet_lut()
     for i, sample in enumerate(images):
         rays = sample['rays']
-        res = render_image(model, rays, chunk=chunk, keys=('rgb', 'depth'), group=group)
+        if occupancy is None:
+            res = render_image(model, rays, chunk=chunk, keys=('rgb', 'depth'), group=group)
+        else:
+            res = render_image(model, rays, chunk=chunk, keys=('rgb', 'depth'), group=group,
+                               occupancy=_image_occupancy(occupancy, rays, i), clip_far=clip_far)
         n = rays.shape[0]
         h, w = sample.get('hw', (1, n))
         img = res['rgb'].view(h, w, 3)

@@ -11,6 +11,7 @@
     texture      csrc/hn_texture.hip                         texture atlas: face classes, cell layout, texel rasteriser,
                                                              textured shading
     mesh_render  csrc/hn_mesh_render.hip                     projection, binning, ray casting, shading
+    occupancy    csrc/hn_occupancy.hip                       occupancy bits of a density lattice, dilation, ray clipping
     data         csrc/hn_data.hip                            ray generation, batch gathers, blend, Pillow-exact resize
     gif          csrc/hn_gif.hip                             colour histogram, palette map, LZW, depth colour map
     checks       —                                           argument validators more than one of them uses
@@ -18,6 +19,6 @@
 They import the binding (_lib), torch, numpy and each other, never functional, machine or arena: functional imports
 them and re-exports their public names.
 """
-from . import checks, data, gif, lpips, mesh, mesh_render, metrics, registration, simplify, texture
+from . import checks, data, gif, lpips, mesh, mesh_render, metrics, occupancy, registration, simplify, texture
 
-__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "registration", "simplify", "texture"]
+__all__ = ["checks", "data", "gif", "lpips", "mesh", "mesh_render", "metrics", "occupancy", "registration", "simplify", "texture"]

@@ -835,6 +835,39 @@ int hn_tsdf_face_keep(const int32_t* faces_dev, long long n_faces, const float* 
                       const float* weight_dev, int nx, int ny, int nz, const float* bounds_host, int32_t* fkeep_dev,
                       int32_t* vkeep_dev, hnStream_t stream);
 
+/* Empty-space skipping (csrc/hn_occupancy.hip; DESIGN.md 3.18 holds the definition, tests/occupancy_restated.py restates it
+ * in NumPy).  A lattice of (nx, ny, nz) points, as hn_grid_points lays it out, has (cx, cy, cz) = (nx-1, ny-1, nz-1) cells;
+ * their occupancy is (cx, cy, words) uint64 with words = ceil(cz / 64): bit b of word w of row (i, j) is cell
+ * (i, j, 64 w + b), the bits past cz are zero.  At most 2048 cells per axis.
+ *   hn_occ_mark       bits of the density lattice grid (nx, ny, nz) fp32: a cell is occupied iff one of its 8 corners is
+ *                     >= sigma_min or NaN.  One wave writes one word (a 64-bit ballot): no atomics, the same bits every run.
+ *   hn_occ_dilate     out = in dilated once by the 3 x 3 x 3 cube (26 neighbours).  Bits carry across word boundaries,
+ *                     nothing wraps at the faces of the grid, the padding bits stay zero.  Not in place.
+ *   hn_occ_count      *count (int64, on the device) = the number of set bits of n_words words (zeroed by a memset node on
+ *                     the stream, then integer atomics: the sum does not depend on their order).
+ *   hn_occ_clip_rays  rays (n, ray_ld >= 6) fp32 rows [o, d, ...]: the ray's part of [t_near, t_far] from the entry of the
+ *                     first to the exit of the last occupied cell it crosses, by a 3-D DDA over the cells of bounds_host
+ *                     (six HOST floats), one ray per work-item, at most cx + cy + cz + 3 steps.  Every plane distance is
+ *                     ((lo + i * cell) - o) / d from the plane's index, each operation rounded on its own in fp32.  Space
+ *                     outside the box is empty; a ray that is not finite, misses the box or meets no occupied cell is a
+ *                     miss.  clip_far == 0 keeps t1 = t_far; an interval shorter than min_span grows by half the
+ *                     difference at both ends, clamped to [t_near, t_far].  Outputs, each may be NULL: t (n, 2) = (t0, t1);
+ *                     hit (n) uint8; rays_out (n, ray_ld): columns 0-2 o + d * a, 3-5 b * d with
+ *                     b = (t1 - t0) / (t_far - t_near), a = t0 - b * t_near, the other columns copied; affine (n, 2) = (a, b),
+ *                     so that a model sampling z in [t_near, t_far] along the new row is at distance a + b z along the
+ *                     old one.  A miss gives t = (t_near, t_far), hit 0, affine (0, 1) and the input row bit for bit, and so
+ *                     does every row with t0 == t_near and t1 == t_far.
+ * Status, before any launch: -2 for a size out of range (no cell or more than 2048 along an axis, a lattice hn_grid_points
+ * refuses, hi <= lo or a bound that is not finite, a NaN sigma_min, n or n_words outside 1 .. 2^31 - 1, ray_ld outside
+ * 6 .. 64, t_far <= t_near or not finite, min_span negative or not finite, bounds_host NULL, out == in), -3 for a NULL device
+ * pointer that must not be. */
+int hn_occ_mark(const float* grid_dev, int nx, int ny, int nz, float sigma_min, uint64_t* bits_dev, hnStream_t stream);
+int hn_occ_dilate(const uint64_t* in_dev, uint64_t* out_dev, int cx, int cy, int cz, hnStream_t stream);
+int hn_occ_count(const uint64_t* bits_dev, long long n_words, int64_t* count_dev, hnStream_t stream);
+int hn_occ_clip_rays(const float* rays_dev, long long n, int ray_ld, const uint64_t* bits_dev, int cx, int cy, int cz,
+                     const float* bounds_host, float t_near, float t_far, int clip_far, float min_span, float* t_dev,
+                     uint8_t* hit_dev, float* rays_out_dev, float* affine_dev, hnStream_t stream);
+
 /* Mesh-to-mesh distance (csrc/hn_mesh_distance.hip; DESIGN.md 3.13 holds the definition, tests/mesh_distance_restated.py
  * restates it in NumPy float32).  Vertices (V, 3) fp32, faces (F, 3) int32; every fp32 operation that decides a result is
  * rounded on its own, dot(u, v) = (ux*vx + uy*vy) + uz*vz.  lo_host / cell_host: three HOST floats each, the low corner
