@@ -25,6 +25,7 @@ from .geometry import (camera_from_c2w, camera_rays, component_sizes, density_gr
                        tsdf_isosurface, vertex_colors, write_ply)
 from .geometry import (OccupancyCache, clip_rays, occupancy_fraction, occupancy_from_density, occupancy_grid, occupancy_union,
                        unclip)
+from .ops.occupancy import OccupancyStack, clip_batch
 from .geometry import (atlas_texel_for_size, bake_field_texture, bake_texture, rasterize_atlas, read_obj,
                        render_textured_mesh, texture_atlas, write_obj)
 

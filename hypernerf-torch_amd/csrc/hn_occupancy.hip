@@ -13,6 +13,8 @@
 //                     Nothing wraps at the faces of the grid and the padding bits stay zero.
 //   hn_occ_count      the number of set bits (integer atomics: the sum does not depend on their order).
 //   hn_occ_clip_rays  one ray per lane, a 3-D DDA through the cells (below).
+//   hn_occ_clip_batch the same DDA for a training batch: each ray against the grid of its own frame, graph-capturable
+//                     (tests/occupancy_train_restated.py).
 #include "hn_camera.h"
 
 #define HN_OCC_MAX_CELLS 2048      // cells per axis: every (float)index is exact and the walk's bound stays small
@@ -167,20 +169,14 @@ HN_DEV float hn_occ_t(const HnOccGrid& g, int a, int i, float o, float d) {
   return __fdiv_rn(__fsub_rn(hn_occ_plane(g, a, i), o), d);
 }
 
-__global__ __launch_bounds__(256) void hn_occ_clip_rays_kernel(const float* __restrict__ rays, long long n, int ray_ld,
-                                                               const unsigned long long* __restrict__ bits, HnOccGrid g,
-                                                               float near, float far, int clip_far, float min_span,
-                                                               float* __restrict__ t_out, uint8_t* __restrict__ hit_out,
-                                                               float* __restrict__ rays_out,
-                                                               float* __restrict__ affine_out) {
-  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (r >= n) return;
-  const float* __restrict__ row = rays + (size_t)r * ray_ld;
+// Steps 1-4 for one ray against the grid whose words start at `bits`: true when a cell counted, with t0 the entry of the
+// first and t1 the exit of the last counted cell (both untouched otherwise).  first_only ends the walk at the first
+// counted cell: t0 is final there, and t1 is only that cell's exit — for a caller that replaces it (clip_far == 0).
+HN_DEV bool hn_occ_walk(const HnOccGrid& g, const unsigned long long* __restrict__ bits, float o0, float o1, float o2,
+                        float d0, float d1, float d2, float near, float far, bool first_only, float& t0, float& t1) {
   const float inf = __builtin_huge_valf(), fmax_ = 3.402823466e38f;
-  const float o0 = row[0], o1 = row[1], o2 = row[2], d0 = row[3], d1 = row[4], d2 = row[5];
   const float o[3] = {o0, o1, o2}, d[3] = {d0, d1, d2};
-  float t0 = near, t1 = far;
-  int hit = 0;
+  bool hit = false;
   bool ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) ok = ok && fabsf(o[a]) <= fmax_ && fabsf(d[a]) <= fmax_;
@@ -228,9 +224,10 @@ __global__ __launch_bounds__(256) void hn_occ_clip_rays_kernel(const float* __re
       const float tout = fminf(fminf(tn0, tn1), fminf(tn2, tx));
       const unsigned long long word = bits[((size_t)i0 * g.c[1] + i1) * g.words + (i2 >> 6)];
       if (((word >> (i2 & 63)) & 1ull) != 0ull && tout > tc) {
-        if (hit == 0) t0 = tc;
+        if (!hit) t0 = tc;
         t1 = tout;
-        hit = 1;
+        hit = true;
+        if (first_only) break;
       }
       if (!(tout < tx)) break;
       if (tn0 <= tn1 && tn0 <= tn2) {
@@ -246,7 +243,14 @@ __global__ __launch_bounds__(256) void hn_occ_clip_rays_kernel(const float* __re
       tc = fmaxf(tc, tout);
     }
   }
-  if (hit != 0) {
+  return hit;
+}
+
+// Step 5 up to the affine map: (t0, t1) of a hit become final (clip_far, min_span), those of a miss (near, far); true
+// when the row is to be copied ((t0, t1) == (near, far): a = 0, b = 1).
+HN_DEV bool hn_occ_span(bool hit, float near, float far, int clip_far, float min_span, float& t0, float& t1, float& a,
+                        float& b) {
+  if (hit) {
     if (clip_far == 0) t1 = far;
     const float span = __fsub_rn(t1, t0);
     if (span < min_span) {
@@ -259,8 +263,35 @@ __global__ __launch_bounds__(256) void hn_occ_clip_rays_kernel(const float* __re
     t1 = far;
   }
   const bool identity = t0 == near && t1 == far;
-  const float b = identity ? 1.0f : __fdiv_rn(__fsub_rn(t1, t0), __fsub_rn(far, near));
-  const float a = identity ? 0.0f : __fsub_rn(t0, __fmul_rn(b, near));
+  b = identity ? 1.0f : __fdiv_rn(__fsub_rn(t1, t0), __fsub_rn(far, near));
+  a = identity ? 0.0f : __fsub_rn(t0, __fmul_rn(b, near));
+  return identity;
+}
+
+// The output row: o + d * a, b * d (the input's bits when `identity`), columns 6 .. ray_ld - 1 copied.
+HN_DEV void hn_occ_store_row(const float* __restrict__ row, int ray_ld, bool identity, float a, float b,
+                             float* __restrict__ dst) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float oc = row[c], dc = row[3 + c];
+    dst[c] = identity ? oc : __fadd_rn(oc, __fmul_rn(dc, a));
+    dst[3 + c] = identity ? dc : __fmul_rn(b, dc);
+  }
+  for (int c = 6; c < ray_ld; ++c) dst[c] = row[c];
+}
+
+__global__ __launch_bounds__(256) void hn_occ_clip_rays_kernel(const float* __restrict__ rays, long long n, int ray_ld,
+                                                               const unsigned long long* __restrict__ bits, HnOccGrid g,
+                                                               float near, float far, int clip_far, float min_span,
+                                                               float* __restrict__ t_out, uint8_t* __restrict__ hit_out,
+                                                               float* __restrict__ rays_out,
+                                                               float* __restrict__ affine_out) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float* __restrict__ row = rays + (size_t)r * ray_ld;
+  float t0 = near, t1 = far, a, b;
+  const bool hit = hn_occ_walk(g, bits, row[0], row[1], row[2], row[3], row[4], row[5], near, far, false, t0, t1);
+  const bool identity = hn_occ_span(hit, near, far, clip_far, min_span, t0, t1, a, b);
   if (t_out != nullptr) {
     t_out[2 * (size_t)r] = t0;
     t_out[2 * (size_t)r + 1] = t1;
@@ -270,15 +301,7 @@ __global__ __launch_bounds__(256) void hn_occ_clip_rays_kernel(const float* __re
     affine_out[2 * (size_t)r] = a;
     affine_out[2 * (size_t)r + 1] = b;
   }
-  if (rays_out != nullptr) {
-    float* __restrict__ dst = rays_out + (size_t)r * ray_ld;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      dst[c] = identity ? o[c] : __fadd_rn(o[c], __fmul_rn(d[c], a));
-      dst[3 + c] = identity ? d[c] : __fmul_rn(b, d[c]);
-    }
-    for (int c = 6; c < ray_ld; ++c) dst[c] = row[c];
-  }
+  if (rays_out != nullptr) hn_occ_store_row(row, ray_ld, identity, a, b, rays_out + (size_t)r * ray_ld);
 }
 
 extern "C" int hn_occ_clip_rays(const float* rays_dev, long long n, int ray_ld, const uint64_t* bits_dev, int cx, int cy,
@@ -294,6 +317,93 @@ extern "C" int hn_occ_clip_rays(const float* rays_dev, long long n, int ray_ld, 
   hipLaunchKernelGGL(hn_occ_clip_rays_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      rays_dev, n, ray_ld, reinterpret_cast<const unsigned long long*>(bits_dev), g, t_near, t_far,
                      clip_far, min_span, t_dev, hit_dev, rays_out_dev, affine_dev);
+  HN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// hn_occ_clip_batch: the same clip for a batch that mixes frames, one ray per lane, each against the grid of its own
+// frame.  bits holds n_slots grids of one geometry back to back; the ray's id v (column id_col of its row, 0 when
+// id_col < 0) picks slot_of_id[(int)v] when v is finite and 0 <= (int)v < n_ids.  Any other v, and a slot outside
+// [0, n_slots), means "no grid": the row is copied, hit = 0, affine = (0, 1).  With a slot, steps 1-5 above on that grid;
+// clip_far == 0 ends the walk at the first counted cell (t1 becomes far whatever the rest of the walk would find).
+// Every pointer the launch reads is fixed: a replayed graph sees what the host wrote into bits and slot_of_id since.
+// hit_count: zeroed on the stream ahead of the launch, then one integer atomic per wave after a wave reduction (the count
+// does not depend on their order).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hn_occ_clip_batch_kernel(const float* __restrict__ rays, long long n, int ray_ld,
+                                                                int id_col, const unsigned long long* __restrict__ bits,
+                                                                int n_slots, const int32_t* __restrict__ slot_of_id,
+                                                                int n_ids, HnOccGrid g, float near, float far, int clip_far,
+                                                                float min_span, float* __restrict__ rays_out,
+                                                                float* __restrict__ viewdirs_out,
+                                                                float* __restrict__ affine_out,
+                                                                uint8_t* __restrict__ hit_out,
+                                                                unsigned long long* __restrict__ hit_count) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool hit = false;
+  if (r < n) {      // no early return: every lane of the wave takes part in the reduction below
+    const float* __restrict__ row = rays + (size_t)r * ray_ld;
+    const float v = id_col < 0 ? 0.0f : row[id_col];
+    int slot = -1;
+    if (v > -1.0f && v < 2147483648.0f) {      // false for NaN and +-inf; (int)v is then defined, and >= 0
+      const int id = (int)v;
+      if (id < n_ids) slot = slot_of_id[id];
+    }
+    float t0 = near, t1 = far, a, b;
+    if (slot >= 0 && slot < n_slots) {
+      const unsigned long long* __restrict__ grid = bits + (size_t)slot * g.c[0] * g.c[1] * g.words;
+      hit = hn_occ_walk(g, grid, row[0], row[1], row[2], row[3], row[4], row[5], near, far, clip_far == 0, t0, t1);
+    }
+    const bool identity = hn_occ_span(hit, near, far, clip_far, min_span, t0, t1, a, b);
+    if (hit_out != nullptr) hit_out[r] = (uint8_t)hit;
+    if (affine_out != nullptr) {
+      affine_out[2 * (size_t)r] = a;
+      affine_out[2 * (size_t)r + 1] = b;
+    }
+    if (viewdirs_out != nullptr) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) viewdirs_out[3 * (size_t)r + c] = row[3 + c];
+    }
+    if (rays_out != nullptr) hn_occ_store_row(row, ray_ld, identity, a, b, rays_out + (size_t)r * ray_ld);
+  }
+  if (hit_count != nullptr) {
+    int c = hit ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if ((threadIdx.x & 63) == 0 && c != 0) atomicAdd(hit_count, (unsigned long long)c);
+  }
+}
+
+__global__ void hn_occ_zero_kernel(unsigned long long* __restrict__ count) {
+  if (threadIdx.x == 0) *count = 0ull;
+}
+
+extern "C" int hn_occ_clip_batch(const float* rays_dev, long long n, int ray_ld, int id_col, const uint64_t* bits_dev,
+                                 int n_slots, int cx, int cy, int cz, const int32_t* slot_of_id_dev, int n_ids,
+                                 const float* bounds_host, float t_near, float t_far, int clip_far, float min_span,
+                                 float* rays_out_dev, float* viewdirs_out_dev, float* affine_dev, uint8_t* hit_dev,
+                                 int64_t* hit_count_dev, hnStream_t stream) {
+  HnOccGrid g;
+  if (bounds_host == nullptr || !hn_occ_grid(cx, cy, cz, bounds_host, &g)) return -2;
+  if (n < 1 || n > 2147483647ll || ray_ld < 6 || ray_ld > 64) return -2;
+  if (id_col >= ray_ld || (id_col >= 0 && id_col < 6)) return -2;
+  if (n_slots < 1 || n_ids < 1) return -2;
+  if (!(fabsf(t_near) <= 3.402823466e38f) || !(fabsf(t_far) <= 3.402823466e38f) || !(t_far > t_near)) return -2;
+  if (!(min_span >= 0.0f && min_span <= 3.402823466e38f)) return -2;
+  if (rays_dev == nullptr || bits_dev == nullptr || slot_of_id_dev == nullptr) return -3;
+  if (rays_out_dev == rays_dev) return -2;
+  if (hit_count_dev != nullptr) {
+    // a one-lane kernel node, not a memset node: under replays that alternate with eager work the memset node of this
+    // counter was seen to leave 0x01 bytes behind once in a dozen replays on the MI355X
+    hipLaunchKernelGGL(hn_occ_zero_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                       reinterpret_cast<unsigned long long*>(hit_count_dev));
+    HN_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(hn_occ_clip_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     rays_dev, n, ray_ld, id_col, reinterpret_cast<const unsigned long long*>(bits_dev), n_slots,
+                     slot_of_id_dev, n_ids, g, t_near, t_far, clip_far, min_span, rays_out_dev, viewdirs_out_dev, affine_dev,
+                     hit_dev, reinterpret_cast<unsigned long long*>(hit_count_dev));
   HN_CHECK_LAUNCH();
   return 0;
 }

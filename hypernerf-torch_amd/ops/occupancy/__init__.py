@@ -1,6 +1,7 @@
 """Empty-space skipping for the render path (csrc/hn_occupancy.hip): a density lattice as one bit per
 lattice cell, its dilation and population count, rays clipped to the occupied part of [near, far], and the map of a
-clipped ray's results back to true distances.
+clipped ray's results back to true distances.  For the training step: OccupancyStack, grids of several
+frames in one fixed buffer, and clip_batch, one graph-capturable launch that clips every ray against its frame's grid.
 
 An occupancy is a dict {'bits': (cx, cy, words) int64 on the GPU, 'cells': (cx, cy, cz), 'bounds': six floats}: the
 lattice of (cx + 1, cy + 1, cz + 1) points over `bounds` has cx * cy * cz cells, words = ceil(cz / 64), and bit b of word w
@@ -21,7 +22,7 @@ from ..mesh import check_lattice, check_volume
 
 __all__ = ["OCC_MAX_CELLS", "OCC_MAX_RAY_LD", "OCC_KEYS", "check_occupancy", "occupancy_mark", "occupancy_dilate",
            "occupancy_count", "occupancy_from_density", "occupancy_grid", "occupancy_union", "occupancy_fraction", "clip_rays",
-           "unclip", "OccupancyCache"]
+           "unclip", "OccupancyCache", "OccupancyStack", "CLIP_BATCH_KEYS", "clip_batch"]
 
 # mirrors of csrc/hn_occupancy.hip's limits (no macros in the header: its set of constants is that of ABI 340)
 OCC_MAX_CELLS = 2048      # cells per axis
@@ -331,3 +332,177 @@ class OccupancyCache:
 
     def __len__(self):
         return len(self._entries)
+
+
+def _check_ids(ids, what: str):
+    try:
+        ids = list(ids)
+    except TypeError:
+        raise ValueError(f"{what}: ids must be a sequence of frame ids, got {ids!r}") from None
+    if not ids or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0 or int(v) >= INT32_MAX
+                      for v in ids):
+        raise ValueError(f"{what}: ids must be one or more ints in 0 .. 2**31 - 2, got {ids!r}")
+    ids = [int(v) for v in ids]
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"{what}: ids must be distinct, got {ids!r}")
+    return tuple(sorted(ids))
+
+
+class OccupancyStack:
+    """The occupancies of several frames over ONE lattice, in buffers whose storage never changes after construction — what
+    a captured training step reads (clip_batch):
+      bits        (n_slots, cx, cy, words) int64: the grids, each in the layout of an occupancy's 'bits'
+      slot_of_id  (max(ids) + 1,) int32: the slot of a frame id, -1 for an id without a grid
+      cells, bounds, ids (ascending), shared
+    `ids` are the distinct frame ids that get a grid: a slot each, or (shared=True) slot 0 for all of them.  Every grid
+    starts all-occupied (the padding bits past cz zero), which clips no ray whose [near, far] lies in the box.  set() and
+    fill() write in place, so a replayed graph sees them."""
+
+    def __init__(self, cells, bounds, ids, shared: bool = False, device='cuda'):
+        what = "OccupancyStack"
+        self.cells = _check_cells(cells, what)
+        self.bounds = _check_bounds(self.cells, bounds, what)
+        self.ids = _check_ids(ids, what)
+        self.shared = bool(shared)
+        self.n_slots = 1 if self.shared else len(self.ids)
+        cx, cy, cz = self.cells
+        words = (cz + 63) // 64
+        if self.n_slots * cx * cy * words > INT32_MAX:
+            raise ValueError(f"{what}: {self.n_slots} grids of {self.cells} cells exceed 2**31 - 1 words")
+        slots = np.full(self.ids[-1] + 1, -1, dtype=np.int32)
+        for slot, fid in enumerate(self.ids):
+            slots[fid] = 0 if self.shared else slot
+        self.slot_of_id = torch.from_numpy(slots).to(device)
+        self.bits = torch.empty((self.n_slots, cx, cy, words), dtype=torch.int64, device=device)
+        self.fill(True)
+
+    def fill(self, all_occupied: bool) -> None:
+        """Every grid all-occupied (True) or empty (False), in place."""
+        with torch.no_grad():
+            if not all_occupied:
+                self.bits.zero_()
+                return
+            self.bits.fill_(-1)
+            tail = self.cells[2] % 64
+            if tail:
+                self.bits[..., -1] = (1 << tail) - 1
+
+    def slot(self, frame_id: int) -> int:
+        """The slot of a frame id, or ValueError when it has no grid."""
+        if isinstance(frame_id, bool) or not isinstance(frame_id, (int, np.integer)) or int(frame_id) not in self.ids:
+            raise ValueError(f"OccupancyStack: {frame_id!r} is not one of the ids {self.ids}")
+        return 0 if self.shared else self.ids.index(int(frame_id))
+
+    def set(self, key, occ: Dict, slot: bool = False) -> None:
+        """Copy the bits of occupancy `occ` (same cells and bounds) into the grid of frame id `key` — or, with slot=True,
+        into slot `key` — in place."""
+        what = "OccupancyStack.set"
+        if slot:
+            if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < self.n_slots:
+                raise ValueError(f"{what}: slot must be an int in 0 .. {self.n_slots - 1}, got {key!r}")
+            at = int(key)
+        else:
+            at = self.slot(key)
+        bits, cells, bounds = check_occupancy(occ, what)
+        if cells != self.cells or bounds != self.bounds:
+            raise ValueError(f"{what}: the occupancy has cells {cells} over {bounds}, the stack {self.cells} over {self.bounds}")
+        if bits.device != self.bits.device:
+            raise ValueError(f"{what}: the occupancy lives on {bits.device}, the stack on {self.bits.device}")
+        with torch.no_grad():
+            self.bits[at].copy_(bits)
+
+    def occupancy(self, frame_id: int) -> Dict:
+        """The occupancy dict of a frame: 'bits' is a VIEW of its slot (clip_rays, occupancy_fraction and
+        render_image(occupancy=) take it)."""
+        return {'bits': self.bits[self.slot(frame_id)], 'cells': self.cells, 'bounds': self.bounds}
+
+    def state_dict(self) -> Dict:
+        return {'bits': self.bits.clone(), 'slot_of_id': self.slot_of_id.clone(), 'cells': self.cells, 'bounds': self.bounds,
+                'ids': self.ids, 'shared': self.shared}
+
+    def load_state_dict(self, state: Dict) -> None:
+        what = "OccupancyStack.load_state_dict"
+        if (tuple(state['cells']) != self.cells or tuple(float(v) for v in state['bounds']) != self.bounds
+                or tuple(state['ids']) != self.ids or bool(state['shared']) != self.shared):
+            raise ValueError(f"{what}: the state is that of another stack (cells, bounds, ids or shared differ)")
+        if tuple(state['bits'].shape) != tuple(self.bits.shape) or state['bits'].dtype != torch.int64:
+            raise ValueError(f"{what}: bits must be a {tuple(self.bits.shape)} int64 tensor")
+        with torch.no_grad():
+            self.bits.copy_(state['bits'])
+
+
+CLIP_BATCH_KEYS = ('rays', 'viewdirs', 'affine', 'hit', 'hit_count')
+
+
+@torch.no_grad()
+def clip_batch(rays: torch.Tensor, stack: OccupancyStack, near: float, far: float, clip_far: bool = True,
+               min_span: Optional[float] = None, out: Optional[Dict[str, torch.Tensor]] = None,
+               id_col: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """clip_rays for a batch that mixes frames (hn_occ_clip_batch, ONE graph-capturable launch): every row of rays
+    (N, 6 .. 64) fp32 is clipped against the grid `stack` holds for the frame id in its column `id_col` (None: column 8
+    when there is one, as prepare_ray_dict reads it; otherwise, and for a negative id_col, every ray has id 0).
+      'rays'      (N, ld)  as clip_rays' — bit for bit, per frame — the row itself for an id without a grid
+      'viewdirs'  (N, 3)   the INPUT rows' directions: render 'rays' with these as 'viewdirs'
+      'affine'    (N, 2)   (a, b) as clip_rays'; (0, 1) without a grid
+      'hit'       (N,)     uint8
+      'hit_count' ()       int64 on the device: hit.sum()
+    clip_far=False keeps t1 = far and ends each walk at the first occupied cell.  `out`: a dict of these five tensors to
+    write into instead of allocating (a captured step replays on them).  The launch reads stack.bits and
+    stack.slot_of_id where they are: a replay sees every set() / fill() since.  No host synchronisation."""
+    what = "clip_batch"
+    if not isinstance(rays, torch.Tensor) or rays.dim() != 2 or not 6 <= rays.shape[1] <= OCC_MAX_RAY_LD \
+            or rays.dtype != torch.float32:
+        raise ValueError(f"{what}: rays must be a (N, 6 .. {OCC_MAX_RAY_LD}) float32 tensor")
+    n, ld = rays.shape
+    if n > INT32_MAX:
+        raise ValueError(f"{what}: {n} rays exceed 2**31 - 1")
+    if not isinstance(stack, OccupancyStack):
+        raise ValueError(f"{what}: stack must be an OccupancyStack, got {type(stack).__name__}")
+    near, far = _check_interval(near, far, what)
+    cells, bounds = stack.cells, stack.bounds
+    if min_span is None:
+        min_span = min((bounds[2 * c + 1] - bounds[2 * c]) / cells[c] for c in range(3))
+    try:
+        min_span = float(min_span)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: min_span must be a number or None, got {min_span!r}") from None
+    if not (math.isfinite(min_span) and min_span >= 0.0):
+        raise ValueError(f"{what}: min_span must be finite and not negative, got {min_span}")
+    if id_col is None:
+        id_col = 8 if ld > 8 else -1
+    if isinstance(id_col, bool) or not isinstance(id_col, (int, np.integer)) or int(id_col) >= ld or 0 <= int(id_col) < 6:
+        raise ValueError(f"{what}: id_col must be negative or a column in 6 .. {ld - 1}, got {id_col!r}")
+    id_col = max(int(id_col), -1)
+    if not (rays.is_cuda and stack.bits.is_cuda):
+        raise ValueError(f"{what}: rays and the stack must live on the GPU (there is no CPU fallback)")
+    if rays.device != stack.bits.device:
+        raise ValueError(f"{what}: rays and the stack must live on one device")
+    dev = rays.device
+    shapes = {'rays': ((n, ld), torch.float32), 'viewdirs': ((n, 3), torch.float32), 'affine': ((n, 2), torch.float32),
+              'hit': ((n,), torch.uint8), 'hit_count': ((), torch.int64)}
+    if out is None:
+        rays = rays.detach().contiguous()
+        out = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (shape, dtype) in shapes.items()}
+    else:
+        if not rays.is_contiguous():
+            raise ValueError(f"{what}: with out= the rays must be C-contiguous (nothing is allocated)")
+        rays = rays.detach()
+        if not isinstance(out, dict) or set(out) != set(shapes):
+            raise ValueError(f"{what}: out must be a dict with the keys {CLIP_BATCH_KEYS}")
+        for k, (shape, dtype) in shapes.items():
+            t = out[k]
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev \
+                    or not t.is_contiguous():
+                raise ValueError(f"{what}: out['{k}'] must be a C-contiguous {shape} {dtype} tensor on {dev}")
+        if n and out['rays'].data_ptr() == rays.data_ptr():
+            raise ValueError(f"{what}: out['rays'] must not be the input rays")
+    if n == 0:
+        out['hit_count'].zero_()
+        return out
+    L.load()
+    with torch.cuda.device(dev):
+        L.launch("hn_occ_clip_batch", L.ptr(rays), n, ld, id_col, L.ptr(stack.bits), stack.n_slots, cells[0], cells[1],
+                 cells[2], L.ptr(stack.slot_of_id), stack.slot_of_id.numel(), (C.c_float * 6)(*bounds), near, far,
+                 1 if clip_far else 0, min_span, L.ptr(out['rays']), L.ptr(out['viewdirs']), L.ptr(out['affine']),
+                 L.ptr(out['hit']), L.ptr(out['hit_count']), L.stream_handle())
+    return out

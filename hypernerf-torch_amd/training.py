@@ -19,6 +19,9 @@ with the MSE in ONE traversal (functional.backward_all); without it the step is 
 `clip_grad_norm=` / `clip_grad_value=` clip the gradient buffer in two HIP launches right before every optimizer launch
 (optim.GradClip: by value, then by global norm; Lightning's gradient_clip_val / gradient_clip_algorithm) and
 `clip_grad_norm` adds 'train/grad_norm' (the norm before clipping) to the log; without them nothing is allocated or launched.
+`occupancy=TrainOccupancy(...)` clips the step's rays to per-frame occupancy grids inside the captured step (one
+hn_occ_clip_batch launch at its head; 'train/occupancy_hit' and 'train/occupancy_span' in the log) and keeps the grids
+current between replays; without it the step is launch for launch the one above.  One GPU only.
 """
 from __future__ import annotations
 
@@ -40,13 +43,150 @@ from .optim import OPTIMIZERS, ArenaAdam, GradClip, MultiStepLR, check_clip_args
 _EXTRA = {'nerf_alpha': None, 'warp_alpha': None, 'hyper_alpha': None, 'hyper_sheet_alpha': None}
 
 
+def _count(value, name: str, least: int, what: str) -> int:
+    if isinstance(value, bool) or not isinstance(value, int) or value < least:
+        raise ValueError(f"{what}: {name} must be an int >= {least}, got {value!r}")
+    return value
+
+
+class TrainOccupancy:
+    """Occupancy grids for the training step: `TrainStep(..., occupancy=TrainOccupancy(...))` clips every
+    ray of a step to the occupied cells of ITS frame's grid — ONE hn_occ_clip_batch launch at the head of the captured
+    step — and renders the clipped rows with the original directions as view directions, so the model spends its samples
+    where the field is; the grids are rebuilt from the field between replays, on a schedule.
+
+    The grids live in an ops.occupancy.OccupancyStack over the cells of a lattice of `resolution` points over `bounds`;
+    `ids` are the frame ids that get one (shared=True: ONE grid for all of them, the union over the frames).  A ray of
+    any other id is not clipped.  builder(frame_id) -> occupancy dict is, by default,
+    occupancy_grid(model, bounds, resolution, frame_id, sigma_min, dilate, level, chunk).
+    clip_far=None means `not model.use_sample_at_infinity`: a model trained with the sample at infinity needs its far end
+    (DESIGN.md 3.18), and the front-only clip ends each ray's walk at the first occupied cell.
+
+    Schedule, with k the number of steps begun so far: before step k the grids are refreshed iff k >= warmup_steps and
+    (k - warmup_steps) % refresh_every == 0.  A refresh builds the next `frames_per_refresh` ids in ascending order,
+    round robin.  Per frame: stack.set(id, builder(id)); a frame not yet visited stays all-occupied.  Shared: every
+    fresh grid is ORed into a pending grid, and when the round wraps the pending grid becomes the live one and is
+    cleared; until the first wrap the live grid is all-occupied.  An all-occupied grid whose box holds a ray's
+    [near, far] segment leaves the row's bits as they are, so the warm-up trains exactly as without the keyword."""
+
+    def __init__(self, model, bounds, resolution, ids, sigma_min: float, dilate: int = 1, shared: bool = False,
+                 warmup_steps: int = 256, refresh_every: int = 16, frames_per_refresh: int = 1,
+                 clip_far: Optional[bool] = None, min_span: Optional[float] = None, level: str = 'fine',
+                 chunk: int = 1 << 20, builder=None, device=None):
+        from .ops import occupancy as occ_ops
+        from .ops.mesh import check_lattice
+        what = "TrainOccupancy"
+        shape, bounds = check_lattice(occ_ops._resolution(resolution), bounds, what)
+        cells = occ_ops._check_cells(tuple(n - 1 for n in shape), what)
+        bounds = occ_ops._check_bounds(cells, bounds, what)
+        ids = occ_ops._check_ids(ids, what)
+        self.sigma_min = occ_ops._check_sigma_min(sigma_min, what)
+        self.dilate = occ_ops._check_dilate(dilate, what)
+        self.warmup_steps = _count(warmup_steps, "warmup_steps", 0, what)
+        self.refresh_every = _count(refresh_every, "refresh_every", 1, what)
+        self.frames_per_refresh = _count(frames_per_refresh, "frames_per_refresh", 1, what)
+        if level not in ('coarse', 'fine'):
+            raise ValueError(f"{what}: level must be 'coarse' or 'fine', got {level!r}")
+        if int(chunk) < 1:
+            raise ValueError(f"{what}: chunk must be positive, got {chunk}")
+        if min_span is not None and not (isinstance(min_span, (int, float)) and 0.0 <= float(min_span) < float("inf")):
+            raise ValueError(f"{what}: min_span must be None or finite and not negative, got {min_span!r}")
+        if builder is not None and not callable(builder):
+            raise ValueError(f"{what}: builder must be callable, got {builder!r}")
+        self.model, self.resolution, self.level, self.chunk = model, shape, level, int(chunk)
+        self.clip_far = (not getattr(model, 'use_sample_at_infinity', True)) if clip_far is None else bool(clip_far)
+        self.min_span = None if min_span is None else float(min_span)
+        self.builder = builder if builder is not None else self._build
+        if device is None:
+            device = next(model.parameters()).device
+        self.stack = occ_ops.OccupancyStack(cells, bounds, ids, shared=shared, device=device)
+        # shared mode: the union of the round in progress; it replaces the live grid (slot 0) when the round wraps
+        self.pending = torch.zeros_like(self.stack.bits[0]) if self.stack.shared else None
+        self.steps_begun = 0      # k
+        self.cursor = 0           # the next id of the round robin, an index into stack.ids
+        self.refreshes = 0
+        self._out: Dict[tuple, Dict[str, torch.Tensor]] = {}     # clip_batch's buffers per (rows, columns): fixed under a graph
+
+    def _build(self, frame_id: int):
+        from .ops.occupancy import occupancy_grid
+        return occupancy_grid(self.model, self.stack.bounds, self.resolution, frame_id, self.sigma_min, self.dilate,
+                              level=self.level, chunk=self.chunk)
+
+    def due(self) -> bool:
+        k = self.steps_begun - self.warmup_steps
+        return k >= 0 and k % self.refresh_every == 0
+
+    def before_step(self) -> None:
+        """What TrainStep.step() calls ahead of the step's launches or replay: the refresh that is due, then k += 1."""
+        if self.due():
+            self.refresh()
+        self.steps_begun += 1
+
+    @torch.no_grad()
+    def refresh(self) -> None:
+        """Rebuild the grids of the next `frames_per_refresh` ids.  Host-side, outside any graph; the model's
+        train / eval state is put back (a captured step froze it)."""
+        from .ops.occupancy import check_occupancy
+        stack = self.stack
+        training = getattr(self.model, 'training', None)
+        try:
+            for _ in range(self.frames_per_refresh):
+                frame_id = stack.ids[self.cursor]
+                occ = self.builder(frame_id)
+                if stack.shared:
+                    bits, cells, bounds = check_occupancy(occ, "TrainOccupancy.refresh")
+                    if cells != stack.cells or bounds != stack.bounds:
+                        raise ValueError(f"TrainOccupancy.refresh: the builder's occupancy has cells {cells} over {bounds}, "
+                                         f"the stack {stack.cells} over {stack.bounds}")
+                    self.pending.bitwise_or_(bits)
+                else:
+                    stack.set(frame_id, occ)
+                self.cursor += 1
+                if self.cursor == len(stack.ids):
+                    self.cursor = 0
+                    if stack.shared:
+                        stack.bits[0].copy_(self.pending)
+                        self.pending.zero_()
+        finally:
+            if training is not None and getattr(self.model, 'training', None) != training:
+                self.model.train(training)
+        self.refreshes += 1
+
+    def clip(self, rays: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """ops.occupancy.clip_batch of a step's rays over [model.near, model.far], into buffers kept per batch shape."""
+        from .ops.occupancy import CLIP_BATCH_KEYS, clip_batch
+        key = tuple(rays.shape)
+        out = self._out.get(key)
+        if out is None:
+            n, ld = key
+            sizes = {'rays': ((n, ld), torch.float32), 'viewdirs': ((n, 3), torch.float32),
+                     'affine': ((n, 2), torch.float32), 'hit': ((n,), torch.uint8), 'hit_count': ((), torch.int64)}
+            out = self._out[key] = {k: torch.zeros(sizes[k][0], dtype=sizes[k][1], device=rays.device)
+                                    for k in CLIP_BATCH_KEYS}
+        return clip_batch(rays, self.stack, self.model.near, self.model.far, clip_far=self.clip_far,
+                          min_span=self.min_span, out=out)
+
+    def state_dict(self) -> Dict:
+        return {'stack': self.stack.state_dict(), 'pending': None if self.pending is None else self.pending.clone(),
+                'steps_begun': self.steps_begun, 'cursor': self.cursor, 'refreshes': self.refreshes}
+
+    def load_state_dict(self, state: Dict) -> None:
+        self.stack.load_state_dict(state['stack'])
+        if (self.pending is None) != (state['pending'] is None):
+            raise ValueError("TrainOccupancy.load_state_dict: the state is that of another mode (shared differs)")
+        if self.pending is not None:
+            with torch.no_grad():
+                self.pending.copy_(state['pending'])
+        self.steps_begun, self.cursor, self.refreshes = int(state['steps_begun']), int(state['cursor']), int(state['refreshes'])
+
+
 class TrainStep:
     def __init__(self, model: torch.nn.Module, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, use_graph: bool = True, group=None, chunk: int = 32 * 1024,
                  decay_step: Optional[Sequence[int]] = None, decay_gamma: float = 0.1, overlap_grad_sync: bool = False,
                  hparams=None, force_dp: bool = False, capture_collective: bool = True, optimizer: str = "adam",
                  momentum: float = 0.9, batcher=None, background_loss=None, clip_grad_norm: Optional[float] = None,
-                 clip_grad_value: Optional[float] = None, distortion_loss=None):
+                 clip_grad_value: Optional[float] = None, distortion_loss=None, occupancy=None):
         # the optimizer of the reference's get_optimizer (utils/__init__.py:23-41): hparams.optimizer (and
         # hparams.momentum for 'sgd') when hparams carries one, the keywords otherwise; lr / eps / weight_decay always
         # from the keywords.  Checked before any device work.
@@ -58,9 +198,18 @@ class TrainStep:
         clipping = clip_grad_norm is not None or clip_grad_value is not None
         if clipping:
             check_clip_args(clip_grad_norm, clip_grad_value, "TrainStep(clip_grad_norm=, clip_grad_value=)")
+        self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+        if occupancy is not None:
+            if not isinstance(occupancy, TrainOccupancy):
+                raise ValueError(f"TrainStep(occupancy=): expected a TrainOccupancy, got {type(occupancy).__name__}")
+            if self.world > 1 or (bool(force_dp) and dist.is_available() and dist.is_initialized()):
+                # sized, not built: the replicas are bit-identical, so every rank could refresh on its own and get the
+                # same grids — but nothing of it has run on two GPUs
+                raise ValueError("TrainStep(occupancy=): not available under data parallelism")
+            if occupancy.model is not model:
+                raise ValueError("TrainStep(occupancy=): the TrainOccupancy was built for another model")
         self.model = model
         self.arena = ParamArena(model.parameters())
-        self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.group = group
         self.use_graph = use_graph
         self.chunk = int(chunk)          # rays per model call (train.py:108-111); the default exceeds any batch size
@@ -109,6 +258,9 @@ class TrainStep:
         self._bg_rng: Optional[Dict[str, torch.Tensor]] = None   # its injected draws, split off `rng` (_split_rng)
         # losses.DistortionLoss or None: a term on every ray chunk's compositing weights (_forward_backward_body)
         self.distortion_loss = distortion_loss
+        # TrainOccupancy or None: one clip launch at the head of the step body; its schedule runs in step(), ahead of the
+        # replay.  With it the distortion loss normalises depth over each ray's CLIPPED interval (the model's z).
+        self.occupancy = occupancy
         self._graph: Optional[GraphedStep] = None
         self._rays = self._rgbs = None
         self._rng: Optional[Dict[str, torch.Tensor]] = None    # fixed buffers of injected random draws (tests)
@@ -129,6 +281,12 @@ class TrainStep:
     def _forward_backward_body(self):
         b = self._rays.shape[0]
         loss_sum, dist_sum, psnr_in = None, None, []
+        # rows the model renders: the step's rays, or (occupancy=) each clipped to its frame's occupied cells, then
+        # rendered with the original directions as view directions, as inference.render_image does
+        rows, clip = self._rays, None
+        if self.occupancy is not None:
+            clip = self.occupancy.clip(self._rays)
+            rows = clip['rays']
         dl = self.distortion_loss
         bg = None
         if self.background_loss is not None:
@@ -143,9 +301,12 @@ class TrainStep:
         # (train.py:108-114); mean((rgb-gt)^2) over the batch = sum over chunks of (rays in chunk / B) x chunk mean,
         # so every chunk is back-propagated on its own (its activations are freed before the next chunk runs)
         for i in range(0, b, self.chunk):
-            rays, rgbs = self._rays[i:i + self.chunk], self._rgbs[i:i + self.chunk]
+            rays, rgbs = rows[i:i + self.chunk], self._rgbs[i:i + self.chunk]
             kw = {} if self._rng is None else {'rng': {k: v[i:i + self.chunk] for k, v in self._rng.items()}}
-            results = self.model(model_utils.prepare_ray_dict(rays), dict(_EXTRA), **kw)
+            ray_dict = model_utils.prepare_ray_dict(rays)
+            if clip is not None:
+                ray_dict['viewdirs'] = clip['viewdirs'][i:i + self.chunk]
+            results = self.model(ray_dict, dict(_EXTRA), **kw)
             w = rays.shape[0] / b
             # the term's forward launches (one per level, right behind the compositing launches) write the gradient for
             # the root they are about to get
@@ -177,6 +338,9 @@ class TrainStep:
                 self._log['train/background_loss'] = bg          # unweighted
             if dist_sum is not None:
                 self._log['train/distortion_loss'] = dist_sum    # unweighted
+            if clip is not None:
+                self._log['train/occupancy_hit'] = clip['hit_count'].to(torch.float32) / b      # the share of rays clipped to cells
+                self._log['train/occupancy_span'] = clip['affine'][:, 1].mean()                 # the mean share of [near, far] kept
 
     def _optimizer_step(self):
         if self.clip is not None:
@@ -315,6 +479,8 @@ class TrainStep:
             self._graph_state = state
             self._graph = None
         self.optimizer.sync_hyper()      # a replayed Adam launch reads lr & co. from device memory
+        if self.occupancy is not None:
+            self.occupancy.before_step()     # the refresh that is due, on the host side of the graph
         if not self.use_graph:
             self._forward_backward()
             if self.dp:
@@ -416,6 +582,8 @@ class TrainStep:
             self._batched_state = state
             self._batched = {}
         self.optimizer.sync_hyper()
+        if self.occupancy is not None:
+            self.occupancy.before_step()
         key = (rows, rng is not None) if bg_rng is None else (rows, rng is not None, True)
         if not self.use_graph:
             b.launch(rows)

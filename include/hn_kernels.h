@@ -857,16 +857,33 @@ int hn_tsdf_face_keep(const int32_t* faces_dev, long long n_faces, const float* 
  *                     so that a model sampling z in [t_near, t_far] along the new row is at distance a + b z along the
  *                     old one.  A miss gives t = (t_near, t_far), hit 0, affine (0, 1) and the input row bit for bit, and so
  *                     does every row with t0 == t_near and t1 == t_far.
+ *   hn_occ_clip_batch the same clip for a training batch that mixes frames, one launch, graph-capturable:
+ *                     bits (n_slots, cx, cy, words) is a stack of grids that share cells and bounds_host; the id v of a ray
+ *                     is column id_col of its row (id_col < 0: every ray has id 0; else 6 <= id_col < ray_ld); when v is
+ *                     finite and 0 <= (int)v < n_ids its slot is slot_of_id[(int)v] (int32, on the device).  A slot
+ *                     outside [0, n_slots), and any other v (NaN included), means "no grid": the row is copied, hit = 0,
+ *                     affine = (0, 1).  With a slot, hit, affine and the output row are bit for bit those of
+ *                     hn_occ_clip_rays on that slot's grid; with clip_far == 0 the walk ends at the first occupied cell
+ *                     (t1 = t_far whatever lies behind it).  Every pointer read is fixed: a replayed graph sees what the
+ *                     host wrote into bits and slot_of_id since.  Outputs, each may be NULL: rays_out (n, ray_ld), not
+ *                     rays; viewdirs_out (n, 3) = the INPUT rows' d; affine (n, 2); hit (n) uint8; hit_count (int64, on the
+ *                     device) = the number of hits, zeroed by a one-lane launch on the stream, then one integer atomic
+ *                     per wave: the same number on every run.
  * Status, before any launch: -2 for a size out of range (no cell or more than 2048 along an axis, a lattice hn_grid_points
  * refuses, hi <= lo or a bound that is not finite, a NaN sigma_min, n or n_words outside 1 .. 2^31 - 1, ray_ld outside
- * 6 .. 64, t_far <= t_near or not finite, min_span negative or not finite, bounds_host NULL, out == in), -3 for a NULL device
- * pointer that must not be. */
+ * 6 .. 64, t_far <= t_near or not finite, min_span negative or not finite, bounds_host NULL, out == in, id_col in 0 .. 5 or
+ * >= ray_ld, n_slots or n_ids < 1), -3 for a NULL device pointer that must not be. */
 int hn_occ_mark(const float* grid_dev, int nx, int ny, int nz, float sigma_min, uint64_t* bits_dev, hnStream_t stream);
 int hn_occ_dilate(const uint64_t* in_dev, uint64_t* out_dev, int cx, int cy, int cz, hnStream_t stream);
 int hn_occ_count(const uint64_t* bits_dev, long long n_words, int64_t* count_dev, hnStream_t stream);
 int hn_occ_clip_rays(const float* rays_dev, long long n, int ray_ld, const uint64_t* bits_dev, int cx, int cy, int cz,
                      const float* bounds_host, float t_near, float t_far, int clip_far, float min_span, float* t_dev,
                      uint8_t* hit_dev, float* rays_out_dev, float* affine_dev, hnStream_t stream);
+int hn_occ_clip_batch(const float* rays_dev, long long n, int ray_ld, int id_col, const uint64_t* bits_dev, int n_slots,
+                      int cx, int cy, int cz, const int32_t* slot_of_id_dev, int n_ids, const float* bounds_host,
+                      float t_near, float t_far, int clip_far, float min_span, float* rays_out_dev,
+                      float* viewdirs_out_dev, float* affine_dev, uint8_t* hit_dev, int64_t* hit_count_dev,
+                      hnStream_t stream);
 
 /* Mesh-to-mesh distance (csrc/hn_mesh_distance.hip; DESIGN.md 3.13 holds the definition, tests/mesh_distance_restated.py
  * restates it in NumPy float32).  Vertices (V, 3) fp32, faces (F, 3) int32; every fp32 operation that decides a result is
