@@ -1,7 +1,8 @@
 """Empty-space skipping for the render path (csrc/hn_occupancy.hip): a density lattice as one bit per
 lattice cell, its dilation and population count, rays clipped to the occupied part of [near, far], and the map of a
 clipped ray's results back to true distances.  For the training step: OccupancyStack, grids of several
-frames in one fixed buffer, and clip_batch, one graph-capturable launch that clips every ray against its frame's grid.
+frames in one fixed buffer, and clip_batch, one graph-capturable launch that clips every ray against its frame's grid;
+train.py holds TrainOccupancy, which keeps such a stack current for training.TrainStep.
 
 An occupancy is a dict {'bits': (cx, cy, words) int64 on the GPU, 'cells': (cx, cy, cz), 'bounds': six floats}: the
 lattice of (cx + 1, cy + 1, cz + 1) points over `bounds` has cx * cy * cz cells, words = ceil(cz / 64), and bit b of word w

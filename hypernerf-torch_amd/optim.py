@@ -20,7 +20,8 @@ from . import _lib as L
 from .arena import ParamArena
 
 
-# A/B switch of the fused reduce + Adam launch for the callers that turn it on (TrainStep, bench.py): HN_FUSE_REDUCE=0
+# The fused reduce + Adam launch is opt-in, off by default: HN_FUSE_REDUCE=1 turns it on for the callers that pass this on
+# as `fuse_reduce` (TrainStep, bench.py); measured slower than reduce, then Adam (NOTES.md, profiles/r06_reduce_adam_ab.log)
 FUSE_REDUCE = __import__("os").environ.get("HN_FUSE_REDUCE", "0") != "0"
 
 
@@ -32,7 +33,7 @@ class ArenaAdam:
         # fuse_reduce: consume the reduce launch of the batched weight gradient (machine.PendingReduce) — `step()` then
         # completes the gradient and applies the update in ONE launch (hn_mlp_wgrad_reduce_adam).  Between backward() and
         # step() the gradient buffer is then INCOMPLETE; `finish_gradients()` (or any ParamArena collective / zero_grad)
-        # completes it with the plain reduce.  Single-GPU training steps: training.TrainStep and bench.py switch it on.
+        # completes it with the plain reduce.  Single-GPU training steps only: training.TrainStep and bench.py switch it on under HN_FUSE_REDUCE=1.
         self.fuse_reduce = bool(fuse_reduce)
         if self.fuse_reduce:
             import weakref

@@ -26,158 +26,32 @@ current between replays; without it the step is launch for laun
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence, Union
 
 import torch
 import torch.distributed as dist
 
 from . import functional as F
 from . import machine
+from . import optim as _optim          # FUSE_REDUCE is read where a TrainStep is built: tests rebind it on the module
 from .arena import ParamArena
 from .dist import GradSync, collective_capturable
 from .graphs import GraphedStep
 from .hypernerf import model_utils
 from .losses import MSELoss, psnr
+from .ops.occupancy.train import TrainOccupancy
 from .optim import OPTIMIZERS, ArenaAdam, GradClip, MultiStepLR, check_clip_args, get_scheduler, make_optimizer
 
 _EXTRA = {'nerf_alpha': None, 'warp_alpha': None, 'hyper_alpha': None, 'hyper_sheet_alpha': None}
 
 
-def _count(value, name: str, least: int, what: str) -> int:
-    if isinstance(value, bool) or not isinstance(value, int) or value < least:
-        raise ValueError(f"{what}: {name} must be an int >= {least}, got {value!r}")
-    return value
-
-
-class TrainOccupancy:
-    """Occupancy grids for the training step: `TrainStep(..., occupancy=TrainOccupancy(...))` clips every
-    ray of a step to the occupied cells of ITS frame's grid — ONE hn_occ_clip_batch launch at the head of the captured
-    step — and renders the clipped rows with the original directions as view directions, so the model spends its samples
-    where the field is; the grids are rebuilt from the field between replays, on a schedule.
-
-    The grids live in an ops.occupancy.OccupancyStack over the cells of a lattice of `resolution` points over `bounds`;
-    `ids` are the frame ids that get one (shared=True: ONE grid for all of them, the union over the frames).  A ray of
-    any other id is not clipped.  builder(frame_id) -> occupancy dict is, by default,
-    occupancy_grid(model, bounds, resolution, frame_id, sigma_min, dilate, level, chunk).
-    clip_far=None means `not model.use_sample_at_infinity`: a model trained with the sample at infinity needs its far end
-    (DESIGN.md 3.18), and the front-only clip ends each ray's walk at the first occupied cell.
-
-    Schedule, with k the number of steps begun so far: before step k the grids are refreshed iff k >= warmup_steps and
-    (k - warmup_steps) % refresh_every == 0.  A refresh builds the next `frames_per_refresh` ids in ascending order,
-    round robin.  Per frame: stack.set(id, builder(id)); a frame not yet visited stays all-occupied.  Shared: every
-    fresh grid is ORed into a pending grid, and when the round wraps the pending grid becomes the live one and is
-    cleared; until the first wrap the live grid is all-occupied.  An all-occupied grid whose box holds a ray's
-    [near, far] segment leaves the row's bits as they are, so the warm-up trains exactly as without the keyword."""
-
-    def __init__(self, model, bounds, resolution, ids, sigma_min: float, dilate: int = 1, shared: bool = False,
-                 warmup_steps: int = 256, refresh_every: int = 16, frames_per_refresh: int = 1,
-                 clip_far: Optional[bool] = None, min_span: Optional[float] = None, level: str = 'fine',
-                 chunk: int = 1 << 20, builder=None, device=None):
-        from .ops import occupancy as occ_ops
-        from .ops.mesh import check_lattice
-        what = "TrainOccupancy"
-        shape, bounds = check_lattice(occ_ops._resolution(resolution), bounds, what)
-        cells = occ_ops._check_cells(tuple(n - 1 for n in shape), what)
-        bounds = occ_ops._check_bounds(cells, bounds, what)
-        ids = occ_ops._check_ids(ids, what)
-        self.sigma_min = occ_ops._check_sigma_min(sigma_min, what)
-        self.dilate = occ_ops._check_dilate(dilate, what)
-        self.warmup_steps = _count(warmup_steps, "warmup_steps", 0, what)
-        self.refresh_every = _count(refresh_every, "refresh_every", 1, what)
-        self.frames_per_refresh = _count(frames_per_refresh, "frames_per_refresh", 1, what)
-        if level not in ('coarse', 'fine'):
-            raise ValueError(f"{what}: level must be 'coarse' or 'fine', got {level!r}")
-        if int(chunk) < 1:
-            raise ValueError(f"{what}: chunk must be positive, got {chunk}")
-        if min_span is not None and not (isinstance(min_span, (int, float)) and 0.0 <= float(min_span) < float("inf")):
-            raise ValueError(f"{what}: min_span must be None or finite and not negative, got {min_span!r}")
-        if builder is not None and not callable(builder):
-            raise ValueError(f"{what}: builder must be callable, got {builder!r}")
-        self.model, self.resolution, self.level, self.chunk = model, shape, level, int(chunk)
-        self.clip_far = (not getattr(model, 'use_sample_at_infinity', True)) if clip_far is None else bool(clip_far)
-        self.min_span = None if min_span is None else float(min_span)
-        self.builder = builder if builder is not None else self._build
-        if device is None:
-            device = next(model.parameters()).device
-        self.stack = occ_ops.OccupancyStack(cells, bounds, ids, shared=shared, device=device)
-        # shared mode: the union of the round in progress; it replaces the live grid (slot 0) when the round wraps
-        self.pending = torch.zeros_like(self.stack.bits[0]) if self.stack.shared else None
-        self.steps_begun = 0      # k
-        self.cursor = 0           # the next id of the round robin, an index into stack.ids
-        self.refreshes = 0
-        self._out: Dict[tuple, Dict[str, torch.Tensor]] = {}     # clip_batch's buffers per (rows, columns): fixed under a graph
-
-    def _build(self, frame_id: int):
-        from .ops.occupancy import occupancy_grid
-        return occupancy_grid(self.model, self.stack.bounds, self.resolution, frame_id, self.sigma_min, self.dilate,
-                              level=self.level, chunk=self.chunk)
-
-    def due(self) -> bool:
-        k = self.steps_begun - self.warmup_steps
-        return k >= 0 and k % self.refresh_every == 0
-
-    def before_step(self) -> None:
-        """What TrainStep.step() calls ahead of the step's launches or replay: the refresh that is due, then k += 1."""
-        if self.due():
-            self.refresh()
-        self.steps_begun += 1
-
-    @torch.no_grad()
-    def refresh(self) -> None:
-        """Rebuild the grids of the next `frames_per_refresh` ids.  Host-side, outside any graph; the model's
-        train / eval state is put back (a captured step froze it)."""
-        from .ops.occupancy import check_occupancy
-        stack = self.stack
-        training = getattr(self.model, 'training', None)
-        try:
-            for _ in range(self.frames_per_refresh):
-                frame_id = stack.ids[self.cursor]
-                occ = self.builder(frame_id)
-                if stack.shared:
-                    bits, cells, bounds = check_occupancy(occ, "TrainOccupancy.refresh")
-                    if cells != stack.cells or bounds != stack.bounds:
-                        raise ValueError(f"TrainOccupancy.refresh: the builder's occupancy has cells {cells} over {bounds}, "
-                                         f"the stack {stack.cells} over {stack.bounds}")
-                    self.pending.bitwise_or_(bits)
-                else:
-                    stack.set(frame_id, occ)
-                self.cursor += 1
-                if self.cursor == len(stack.ids):
-                    self.cursor = 0
-                    if stack.shared:
-                        stack.bits[0].copy_(self.pending)
-                        self.pending.zero_()
-        finally:
-            if training is not None and getattr(self.model, 'training', None) != training:
-                self.model.train(training)
-        self.refreshes += 1
-
-    def clip(self, rays: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """ops.occupancy.clip_batch of a step's rays over [model.near, model.far], into buffers kept per batch shape."""
-        from .ops.occupancy import CLIP_BATCH_KEYS, clip_batch
-        key = tuple(rays.shape)
-        out = self._out.get(key)
-        if out is None:
-            n, ld = key
-            sizes = {'rays': ((n, ld), torch.float32), 'viewdirs': ((n, 3), torch.float32),
-                     'affine': ((n, 2), torch.float32), 'hit': ((n,), torch.uint8), 'hit_count': ((), torch.int64)}
-            out = self._out[key] = {k: torch.zeros(sizes[k][0], dtype=sizes[k][1], device=rays.device)
-                                    for k in CLIP_BATCH_KEYS}
-        return clip_batch(rays, self.stack, self.model.near, self.model.far, clip_far=self.clip_far,
-                          min_span=self.min_span, out=out)
-
-    def state_dict(self) -> Dict:
-        return {'stack': self.stack.state_dict(), 'pending': None if self.pending is None else self.pending.clone(),
-                'steps_begun': self.steps_begun, 'cursor': self.cursor, 'refreshes': self.refreshes}
-
-    def load_state_dict(self, state: Dict) -> None:
-        self.stack.load_state_dict(state['stack'])
-        if (self.pending is None) != (state['pending'] is None):
-            raise ValueError("TrainOccupancy.load_state_dict: the state is that of another mode (shared differs)")
-        if self.pending is not None:
-            with torch.no_grad():
-                self.pending.copy_(state['pending'])
-        self.steps_begun, self.cursor, self.refreshes = int(state['steps_begun']), int(state['cursor']), int(state['refreshes'])
+class _Program(NamedTuple):
+    """A captured step.  `run`: the whole step as ONE GraphedStep, or the data-parallel step in three pieces as
+    (fwd_bwd, held) — a graph up to the first weight-gradient bucket and the graph of the held bucket (or None), with an
+    eager all-reduce and the optimizer behind them (TrainStep._run).  `log`: the log tensors that capture wrote, which
+    every replay overwrites."""
+    run: Union[GraphedStep, tuple]
+    log: Dict[str, torch.Tensor]
 
 
 class TrainStep:
@@ -229,9 +103,9 @@ class TrainStep:
         # hn_adam_step: one launch for all parameters, clears the gradient buffer on the way out, graph-capturable
         # (on one GPU it is part of the captured step; with N>1 it follows the gradient all-reduce and scales the
         # summed gradient by 1/world itself)
-        # Without a collective between backward and the optimizer (one GPU) the launch that completes the gradient also
-        # applies the update (hn_mlp_wgrad_reduce_adam: no gradient write-back, no second pass over the arena)
-        from . import optim as _optim
+        # Opt-in, off by default (HN_FUSE_REDUCE=1, optim.FUSE_REDUCE): without a collective between backward and the
+        # optimizer (one GPU) and without clipping, the launch that completes the gradient also applies the update
+        # (hn_mlp_wgrad_reduce_adam: no gradient write-back, no second pass over the arena)
         if optimizer == "adam":
             self.optimizer = ArenaAdam(self.arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, zero_grad=True,
                                        grad_scale=1.0 / self.world,
@@ -261,17 +135,19 @@ class TrainStep:
         # TrainOccupancy or None: one clip launch at the head of the step body; its schedule runs in step(), ahead of the
         # replay.  With it the distortion loss normalises depth over each ray's CLIPPED interval (the model's z).
         self.occupancy = occupancy
-        self._graph: Optional[GraphedStep] = None
-        self._rays = self._rgbs = None
-        self._rng: Optional[Dict[str, torch.Tensor]] = None    # fixed buffers of injected random draws (tests)
-        self._log: Dict[str, torch.Tensor] = {}
         # batcher (datasets.RayBatcher): step() takes no tensors; the batch is gathered on the device by the first
-        # launch of the step's graph.  One cached program per batch size (the full one and the epoch's short last one)
+        # launch of the step's graph (eager and data-parallel steps: by a launch of its own ahead of the step)
         self.batcher = batcher
-        self._batched: Dict[tuple, tuple] = {}
-        self._batched_state = None
-        self._batched_rng: Dict[int, Dict[str, torch.Tensor]] = {}
-        self._batched_bg_rng: Optional[Dict[str, torch.Tensor]] = None
+        self._rays = self._rgbs = None                         # the fixed buffers the step body reads (_bind_*)
+        self._rng: Optional[Dict[str, torch.Tensor]] = None    # ... of injected random draws (tests)
+        self._log: Dict[str, torch.Tensor] = {}                # ... and writes: the log of the step that ran last
+        # the captured programs by key (step()).  The tensor-fed step keeps ONE (its binder drops it together with the
+        # buffers it was captured on); a batcher one per key: the full batch and the epoch's short last one
+        self._batched: Dict[tuple, _Program] = {}
+        self._graph = None          # _Program.run of the step that ran last, None once that program was dropped
+        self._graph_state = None    # (precision, model.training) the programs were captured under
+        self._batched_rng: Dict[int, Dict[str, torch.Tensor]] = {}       # the batcher's rng buffers per row count
+        self._batched_bg_rng: Optional[Dict[str, torch.Tensor]] = None   # ... and its background draws, for all row counts
 
     # ---- the step body (what gets captured) ---------------------------------------------------
     def _forward_backward(self):
@@ -442,96 +318,6 @@ class TrainStep:
         self.dp_graph = f"three pieces: graph | eager all-reduce | Adam ({why})"
         return self._capture_data_parallel()
 
-    # ---- public -----------------------------------------------------------------------------------
-    def step(self, rays: Optional[torch.Tensor] = None, rgbs: Optional[torch.Tensor] = None,
-             rng: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-        """rays (B, 8|9), rgbs (B, 3) on the GPU; B must stay the same from call to call when graphs are on.
-        `rng` optionally supplies the random draws of NerfModel.forward ('t_rand', 'u', 'noise_coarse', 'noise_fine',
-        one row per ray) instead of torch's generator: parity runs against the CPU oracle share the draws this way.
-        With a background loss, `rng` may also carry its draws 'bg_u' (batch_size, 2) and 'bg_n' (batch_size, 3).
-        With a batcher, step() takes no rays / rgbs: the next batch of the batcher's epoch is gathered on the device
-        (an epoch that ran out starts the next one); `rng` rows then match that batch's size."""
-        if self.batcher is not None:
-            if rays is not None or rgbs is not None:
-                raise ValueError("TrainStep(batcher=...): step() takes no rays / rgbs")
-            return self._step_batched(rng)
-        if rays is None or rgbs is None:
-            raise ValueError("step() needs rays and rgbs (or a TrainStep built with batcher=...)")
-        rng, bg_rng = self._split_rng(rng)
-        if (self._rays is None or self._rays.shape != rays.shape or (rng is None) != (self._rng is None)
-                or (bg_rng is None) != (self._bg_rng is None)):
-            self._rays, self._rgbs = rays.clone(), rgbs.clone()
-            self._rng = None if rng is None else {k: v.clone() for k, v in rng.items()}
-            self._bg_rng = None if bg_rng is None else {k: v.clone() for k, v in bg_rng.items()}
-            self._graph = None
-        else:
-            self._rays.copy_(rays)
-            self._rgbs.copy_(rgbs)
-            if rng is not None:
-                for k, v in rng.items():
-                    self._rng[k].copy_(v)
-            if bg_rng is not None:
-                for k, v in bg_rng.items():
-                    self._bg_rng[k].copy_(v)
-        # what a captured graph froze besides the shapes: the precision mode and whether the model trains / evaluates
-        state = (F.get_precision(), self.model.training)
-        if getattr(self, "_graph_state", None) != state:
-            self._graph_state = state
-            self._graph = None
-        self.optimizer.sync_hyper()      # a replayed Adam launch reads lr & co. from device memory
-        if self.occupancy is not None:
-            self.occupancy.before_step()     # the refresh that is due, on the host side of the graph
-        if not self.use_graph:
-            self._forward_backward()
-            if self.dp:
-                self.sync.reduce(F.flush_held_wgrads, force=True)
-            self._optimizer_step()
-        elif not self.dp:
-            if self._graph is None:
-                self._graph = self._capture(self._whole)
-            self._graph()
-        else:
-            if self._graph is None:
-                self._graph = self._capture_dp()
-            if isinstance(self._graph, GraphedStep):
-                self._graph()               # forward + backward + all-reduce + Adam: ONE replay
-            else:
-                fwd_bwd, held = self._graph
-                fwd_bwd()
-                self.sync.reduce(held, force=True)   # all-reduce(bucket 0) || held weight gradients, then all-reduce(bucket 1)
-                self._optimizer_step()
-        # a replay updates the parameters without running any Python: tell the weight packers (an eval forward
-        # after this must repack — see machine.MlpRunner.pack)
-        self.arena.bump()
-        machine.note_parameters_changed()
-        log = self._with_grad_norm({k: v.clone() for k, v in self._log.items()})     # graph outputs are overwritten by the next replay
-        log['lr'] = self.optimizer.param_groups[0]['lr']
-        return log
-
-    _BG_KEYS = ('bg_u', 'bg_n')
-
-    def _split_rng(self, rng):
-        """`rng` of step() -> (the per-ray draws of NerfModel.forward or None, the background loss's draws or None): the
-        second never reaches the model and is never sliced per chunk."""
-        if rng is None or not any(k in rng for k in self._BG_KEYS):
-            return rng, None
-        if self.background_loss is None:
-            raise ValueError("step(rng=...): 'bg_u' / 'bg_n' given to a TrainStep without background_loss")
-        if not all(k in rng for k in self._BG_KEYS):
-            raise ValueError("step(rng=...): 'bg_u' and 'bg_n' come together")
-        rest = {k: v for k, v in rng.items() if k not in self._BG_KEYS}
-        return (rest or None), {k: rng[k] for k in self._BG_KEYS}
-
-    def epoch_end(self):
-        """Advance the LR schedule by one epoch (Lightning steps the scheduler of configure_optimizers per epoch); with
-        a batcher, end its epoch too: the next step() draws a new order (for the epoch a set_epoch() call in between
-        names, else the next one)."""
-        if self.scheduler is not None:
-            self.scheduler.step()
-        if self.batcher is not None:
-            self.batcher.end_epoch()
-
-    # ---- the batched step (batcher=...) ---------------------------------------------------------------
     def _whole_batched(self, rows: int):
         self.batcher.launch(rows)
         self._whole()
@@ -551,72 +337,142 @@ class TrainStep:
         finally:
             b.state.copy_(state)
 
-    def _step_batched(self, rng: Optional[Dict[str, torch.Tensor]]) -> Dict[str, torch.Tensor]:
-        b = self.batcher
-        rows = b.next_rows()              # host bookkeeping only; the cursor itself lives on the device
-        self._rays, self._rgbs = b.views(rows)
+    def _capture_step(self, rows: int) -> _Program:
+        """The step on the buffers bound now, captured in the form this TrainStep runs."""
+        if self.dp:
+            run = self._capture_dp()
+        elif self.batcher is not None:
+            run = self._capture_batched(rows)
+        else:
+            run = self._capture(self._whole)
+        return _Program(run, self._log)
+
+    def _run(self, run):
+        """One step: ONE replay of a whole-step graph, or `run` = (fwd_bwd, held) in three pieces — a captured program's
+        two graphs, or the eager step's uncaptured functions."""
+        if isinstance(run, GraphedStep):
+            return run()
+        fwd_bwd, held = run
+        fwd_bwd()
+        if self.dp:
+            self.sync.reduce(held, force=True)   # all-reduce(bucket 0) || held weight gradients, then all-reduce(bucket 1)
+        self._optimizer_step()
+
+    # ---- binding the step's inputs ----------------------------------------------------------------
+    _BG_KEYS = ('bg_u', 'bg_n')
+
+    def _split_rng(self, rng):
+        """`rng` of step() -> (the per-ray draws of NerfModel.forward or None, the background loss's draws or None): the
+        second never reaches the model and is never sliced per chunk."""
+        if rng is None or not any(k in rng for k in self._BG_KEYS):
+            return rng, None
+        if self.background_loss is None:
+            raise ValueError("step(rng=...): 'bg_u' / 'bg_n' given to a TrainStep without background_loss")
+        if not all(k in rng for k in self._BG_KEYS):
+            raise ValueError("step(rng=...): 'bg_u' and 'bg_n' come together")
+        rest = {k: v for k, v in rng.items() if k not in self._BG_KEYS}
+        return (rest or None), {k: rng[k] for k in self._BG_KEYS}
+
+    @staticmethod
+    def _fill(bufs, draws):
+        """`draws` copied into the fixed buffers `bufs` in place; without buffers (None), owned clones become them."""
+        if bufs is None:
+            return {k: v.clone() for k, v in draws.items()}
+        for k, v in draws.items():
+            bufs[k].copy_(v)
+        return bufs
+
+    def _drop_programs(self, rng_rows: Optional[int] = None):
+        """Forget the captured programs: all of them, or only those of `rng_rows` rows that read per-ray draws."""
+        self._batched = {} if rng_rows is None else {key: prog for key, prog in self._batched.items()
+                                                     if not (key[0] == rng_rows and key[1])}
+        self._graph = None
+
+    def _bind_tensors(self, rays, rgbs, rng):
+        """The caller's tensors into owned buffers: copied in place while the shape of `rays` stays and `rng` / the
+        background draws stay given or not given; otherwise cloned anew, and the program captured on the old ones goes."""
         rng, bg_rng = self._split_rng(rng)
-        if bg_rng is None:
-            self._bg_rng = None
+        if (self._rays is None or self._rays.shape != rays.shape or (rng is None) != (self._rng is None)
+                or (bg_rng is None) != (self._bg_rng is None)):
+            self._rays, self._rgbs = rays.clone(), rgbs.clone()
+            self._rng = self._bg_rng = None
+            self._drop_programs()
         else:
-            if self._batched_bg_rng is None:      # one pair of buffers for every batch size (batch_size rows)
-                self._batched_bg_rng = {k: v.clone() for k, v in bg_rng.items()}
-            else:
-                for k, v in bg_rng.items():
-                    self._batched_bg_rng[k].copy_(v)
-            self._bg_rng = self._batched_bg_rng
-        if rng is None:
-            self._rng = None
-        else:
+            self._rays.copy_(rays)
+            self._rgbs.copy_(rgbs)
+        self._rng = None if rng is None else self._fill(self._rng, rng)
+        self._bg_rng = None if bg_rng is None else self._fill(self._bg_rng, bg_rng)
+
+    def _bind_batch(self, rng):
+        """The batcher's next batch: views of its buffers, one set of rng buffers per row count — replaced, with that row
+        count's programs that read it, when the key set of `rng` changes — and one pair of background buffers for all."""
+        rows = self.batcher.next_rows()              # host bookkeeping only; the cursor itself lives on the device
+        self._rays, self._rgbs = self.batcher.views(rows)
+        rng, bg_rng = self._split_rng(rng)
+        if bg_rng is not None:
+            self._batched_bg_rng = self._fill(self._batched_bg_rng, bg_rng)
+        self._bg_rng = None if bg_rng is None else self._batched_bg_rng
+        if rng is not None:
             bufs = self._batched_rng.get(rows)
             if bufs is None or set(bufs) != set(rng):
-                bufs = self._batched_rng[rows] = {k: v.clone() for k, v in rng.items()}
-                self._batched.pop((rows, True), None)
-                self._batched.pop((rows, True, True), None)
-            else:
-                for k, v in rng.items():
-                    bufs[k].copy_(v)
-            self._rng = bufs
-        state = (F.get_precision(), self.model.training)
-        if self._batched_state != state:
-            self._batched_state = state
-            self._batched = {}
-        self.optimizer.sync_hyper()
-        if self.occupancy is not None:
-            self.occupancy.before_step()
-        key = (rows, rng is not None) if bg_rng is None else (rows, rng is not None, True)
-        if not self.use_graph:
-            b.launch(rows)
-            self._forward_backward()
-            if self.dp:
-                self.sync.reduce(F.flush_held_wgrads, force=True)
-            self._optimizer_step()
-            log = self._log
-        elif not self.dp:
-            prog = self._batched.get(key)
-            if prog is None:
-                g = self._capture_batched(rows)
-                prog = self._batched[key] = (g, self._log)
-            prog[0]()
-            log = prog[1]
+                bufs = None
+                self._drop_programs(rng_rows=rows)
+            self._batched_rng[rows] = self._fill(bufs, rng)
+        self._rng = None if rng is None else self._batched_rng[rows]
+
+    # ---- public -----------------------------------------------------------------------------------
+    def step(self, rays: Optional[torch.Tensor] = None, rgbs: Optional[torch.Tensor] = None,
+             rng: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """rays (B, 8|9), rgbs (B, 3) on the GPU; B must stay the same from call to call when graphs are on.
+        `rng` optionally supplies the random draws of NerfModel.forward ('t_rand', 'u', 'noise_coarse', 'noise_fine',
+        one row per ray) instead of torch's generator: parity runs against the CPU oracle share the draws this way.
+        With a background loss, `rng` may also carry its draws 'bg_u' (batch_size, 2) and 'bg_n' (batch_size, 3).
+        With a batcher, step() takes no rays / rgbs: the next batch of the batcher's epoch is gathered on the device
+        (an epoch that ran out starts the next one); `rng` rows then match that batch's size."""
+        if self.batcher is not None:
+            if rays is not None or rgbs is not None:
+                raise ValueError("TrainStep(batcher=...): step() takes no rays / rgbs")
+            self._bind_batch(rng)
+        elif rays is None or rgbs is None:
+            raise ValueError("step() needs rays and rgbs (or a TrainStep built with batcher=...)")
         else:
-            # data-parallel: the gather runs on its own ahead of the step's program(s), cached per batch size
-            b.launch(rows)
+            self._bind_tensors(rays, rgbs, rng)
+        # what a captured graph froze besides the shapes: the precision mode and whether the model trains / evaluates
+        state = (F.get_precision(), self.model.training)
+        if self._graph_state != state:
+            self._graph_state = state
+            self._drop_programs()
+        self.optimizer.sync_hyper()      # a replayed Adam launch reads lr & co. from device memory
+        if self.occupancy is not None:
+            self.occupancy.before_step()     # the refresh that is due, on the host side of the graph
+        rows = self._rays.shape[0]
+        if self.batcher is not None and (self.dp or not self.use_graph):
+            # only the one-GPU graph holds the gather (_capture_batched); otherwise it runs on its own, ahead of the step
+            self.batcher.launch(rows)
+        if not self.use_graph:
+            self._run((self._forward_backward, F.flush_held_wgrads))
+        else:
+            # what names a program: the rows and whether per-ray / background draws are injected, of the buffers bound above
+            key = (rows, self._rng is not None, self._bg_rng is not None)
             prog = self._batched.get(key)
             if prog is None:
-                self._graph = None
-                prog = self._batched[key] = (self._capture_dp(), self._log)
-            g = prog[0]
-            if isinstance(g, GraphedStep):
-                g()
-            else:
-                fwd_bwd, held = g
-                fwd_bwd()
-                self.sync.reduce(held, force=True)
-                self._optimizer_step()
-            log = prog[1]
+                prog = self._batched[key] = self._capture_step(rows)
+            self._graph, self._log = prog.run, prog.log
+            self._run(prog.run)
+        # a replay updates the parameters without running any Python: tell the weight packers (an eval forward
+        # after this must repack — see machine.MlpRunner.pack)
         self.arena.bump()
         machine.note_parameters_changed()
-        out = self._with_grad_norm({k: v.clone() for k, v in log.items()})
-        out['lr'] = self.optimizer.param_groups[0]['lr']
-        return out
+        log = self._with_grad_norm({k: v.clone() for k, v in self._log.items()})     # graph outputs are overwritten by the next replay
+        log['lr'] = self.optimizer.param_groups[0]['lr']
+        return log
+
+    def epoch_end(self):
+        """Advance the LR schedule by one epoch (Lightning steps the scheduler of configure_optimizers per epoch); with
+        a batcher, end its epoch too: the next step() draws a new order (for the epoch a set_epoch() call in between
+        names, else the next one)."""
+        if self.scheduler is not None:
+            self.scheduler.step()
+        if self.batcher is not None:
+            self.batcher.end_epoch()
+

@@ -1109,3 +1109,59 @@ def test_reduce_fused_with_adam_equals_reduce_then_adam(precision, use_graph, ch
         grads[fuse] = arena.grad.clone()
         opt.step()
     assert torch.equal(grads[False], grads[True]) and bool(grads[True].any())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# what a captured step keeps from call to call: one program for the tensor-fed step, one per batch size for a batcher
+# ------------------------------------------------------------------------------------------------------------------
+def _model_64(seed):
+    HN.set_precision("bf16")
+    m = models.NerfModel(EMB, n_samples_coarse=64, n_samples_fine=64, noise_std=None, **KW)
+    load_hash(m, seed)
+    return m.to(DEV)
+
+
+def test_tensor_fed_step_keeps_one_program_and_recaptures_on_a_new_shape():
+    """Steps of 64, 64, 96, 64 rays through one captured TrainStep: the second replays the first's program, every change
+    of shape captures a new one (the old one is not kept), and the capture's warm-up runs are undone each time — the
+    device step counter reads exactly one update per step()."""
+    ts = TrainStep(_model_64(81), lr=1e-3, use_graph=True)
+    assert ts._graph is None
+    seen = []
+    for k, b in enumerate((64, 64, 96, 64)):
+        _, _, _, rays = ray_rows(81 + k, b)
+        log = ts.step(rays.to(DEV), H.uniform(81 + k, "rgbs", (b, 3), 0.1, 0.9).to(DEV))
+        assert ts._graph is not None and ts._rays.shape == (b, 9)
+        assert math.isfinite(float(log["train/loss"]))
+        seen.append(ts._graph)
+    assert float(ts.optimizer.step_count) == 4.0
+    assert seen[1] is seen[0] and seen[2] is not seen[1] and seen[3] is not seen[2] and seen[3] is not seen[0]
+
+
+def test_batcher_fed_step_replaces_its_programs_when_the_draws_change(golden_dir, tmp_path):
+    """TrainStep(batcher=...) over two epochs of the g22 scene at 40 x 30, B = 2048 (6000 rays: two full batches and a
+    short one): an epoch with rng = {t_rand}, then one with rng = {t_rand, u}.  Every step() is exactly one update, and
+    the two programs of the first epoch (full batch, short batch) are REPLACED by the second epoch's, not kept beside them."""
+    from hypernerf_torch_amd.datasets import LLFFDataset, RayBatcher
+    from llff_scene import write_scene
+    g22 = np.load(os.path.join(golden_dir, "g22_llff.npz"))
+    root = write_scene(str(tmp_path / "g22"), g22["scene_pixels"], g22["scene_poses_bounds"])
+    ds = LLFFDataset(root, split="train", img_wh=(40, 30), include_idx=True)
+    ts = TrainStep(_model_64(82), lr=1e-3, batcher=RayBatcher(ds, 2048, generator=torch.Generator().manual_seed(6)))
+    per_epoch = ts.batcher.steps_per_epoch
+    assert per_epoch == 3 and 0 < ts.batcher.short_rows < 2048
+    gen = torch.Generator().manual_seed(2)
+    n_steps = 0
+    for keys in (("t_rand",), ("t_rand", "u")):
+        sizes = []
+        for k in range(per_epoch):
+            rows = 2048 if k < per_epoch - 1 else ts.batcher.short_rows
+            log = ts.step(rng={name: torch.rand((rows, 64), generator=gen).to(DEV) for name in keys})
+            assert ts._rays.shape[0] == rows and set(ts._rng) == set(keys)
+            assert math.isfinite(float(log["train/loss"]))
+            sizes.append(rows)
+            n_steps += 1
+        ts.epoch_end()
+        assert len(set(sizes)) == 2 and len(ts._batched) == 2, (keys, sizes, len(ts._batched))
+    assert n_steps == 6 and float(ts.optimizer.step_count) == float(n_steps)
+    ts.batcher.check()
