@@ -199,7 +199,7 @@ def vertex_colors(model, vertices: torch.Tensor, normals: Optional[torch.Tensor]
     as in density_grid.  `chunk` vertices at a time, as rows of ONE point with their own direction (hn_vertex_viewdirs
     writes a chunk of directions; the full direction tensor never exists); the values do not depend on `chunk`.
     dtype float32: that rgb; uint8: (rgb * 255) truncated on the device, the convention of inference.evaluate_images.
-    A model with use_viewdirs=False ignores the direction.  Inference only; model._level_state is left as found."""
+    A model with use_viewdirs=False ignores the direction.  Inference only; no state is left on the model."""
     if dtype not in (torch.uint8, torch.float32):
         raise ValueError(f"vertex_colors: dtype must be torch.uint8 or torch.float32, got {dtype}")
     if int(chunk) < 1:
@@ -1238,7 +1238,7 @@ def bake_field_texture(model, mesh: Dict[str, torch.Tensor], atlas: Dict, frame_
                        render_opts=None, dtype=torch.uint8) -> torch.Tensor:
     """bake_texture with the field's colour at frame `frame_id`: vertex_colors(model, points, normals, frame_id, view=...) at
     every owned texel's point, seen along -normal or from the camera position `view`.  The mesh lives on the model's
-    device.  The values do not depend on `chunk`; model._level_state is left as found."""
+    device.  The values do not depend on `chunk`; no state is left on the model."""
     if int(chunk) < 1:
         raise ValueError(f"bake_field_texture: chunk must be positive, got {chunk}")
 

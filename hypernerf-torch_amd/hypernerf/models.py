@@ -9,13 +9,14 @@ from __future__ import annotations
 
 import functools
 import os
-from typing import Any, Callable, Dict, Mapping, Optional, Sequence
+from typing import Any, Callable, Dict, Mapping, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
 from .. import _lib as L
 from .. import functional as F
+from .. import machine
 from ..machine import AuxSpec, GradIn, OutSpec, Program, copy_features, posenc_features
 from . import model_utils, modules, warping
 
@@ -33,6 +34,22 @@ def filter_sigma(points, sigma, render_opts):
              & (points[..., 1] <= ymax) & (points[..., 2] >= zmin) & (points[..., 2] <= zmax))
         sigma = m * sigma
     return sigma
+
+
+class _Pass(NamedTuple):
+    """What one pass over the model (forward, render_samples, query_points) is called with, and the path its levels
+    take: 'fused' = the level as ONE program, 'gather' = the warp outside a template that gathers from the GLO table,
+    'networks' = network by network.  `tab` = (GLOEmbed module, metadata key) of the table the programs of the first
+    two gather from.  Lives as long as the call that made it."""
+    use_warp: bool
+    metadata_encoded: bool
+    metadata: Any
+    extra_params: Any
+    return_warp_jacobian: bool
+    viewdirs: Optional[torch.Tensor]
+    directions: Optional[torch.Tensor]
+    path: str
+    tab: Optional[tuple]
 
 
 class NerfModel(nn.Module):
@@ -140,6 +157,7 @@ class NerfModel(nn.Module):
         self.nerf_mlps_coarse = nerf_mlps_coarse
         self.nerf_mlps_fine = nerf_mlps_fine
         self._template_calls: Dict[Any, F.ProgramCall] = {}
+        self._no_fit: set = set()       # "fuse" / "gather": this configuration does not fit ONE level / gathered program
         self._det_u: Dict[Any, torch.Tensor] = {}
         self.precision: Optional[str] = None   # None = package default (functional.set_precision)
         # the constructor's own public attributes shape the compiled programs (hyper_slice_method, use_viewdirs,
@@ -153,8 +171,12 @@ class NerfModel(nn.Module):
         # use_alpha_condition, the frequencies, ...): the cached programs were compiled for the old value
         if "_template_calls" in self.__dict__ and (isinstance(value, nn.Module) or
                                                    name in self.__dict__.get("_structural", ())):
-            self._template_calls.clear()
+            self._drop_programs()
         super().__setattr__(name, value)
+
+    def _drop_programs(self):
+        self._template_calls.clear()
+        self._no_fit.clear()
 
     def _live_call(self, key):
         """Cached program for `key`, unless a parameter it was compiled over is no longer a parameter of this model
@@ -165,7 +187,7 @@ class NerfModel(nn.Module):
             return None
         ids = {id(p) for p in self.parameters()}
         if any(id(p) not in ids for p in call.program.params):
-            self._template_calls.clear()
+            self._drop_programs()
             return None
         return call
 
@@ -223,33 +245,40 @@ class NerfModel(nn.Module):
         return self.warp_field(points, self.warp_embed(warp_embed), extra_params)
 
     # ---- template program ----------------------------------------------------------------------
+    def _cached_call(self, key, build: Callable[[], F.ProgramCall]) -> F.ProgramCall:
+        call = self._live_call(key)
+        if call is None:
+            call = self._template_calls[key] = build()
+        return call
+
+    def _template_layers(self, level: str, point_feats, dst_rgb: int = 0, dst_alpha: int = 1):
+        """The layers of query_template (models.py:447-493) behind the encoded point features `point_feats`: view
+        directions from source 1, the alpha / rgb conditions (models.py:425-436) from the GLO source 2."""
+        m = self.nerf_mlps_fine if level == 'fine' else self.nerf_mlps_coarse
+        if len(point_feats) != m.in_ch:
+            raise RuntimeError(f"template input has {len(point_feats)} channels, the MLP expects {m.in_ch} "
+                               "(the reference shape-errors the same way, e.g. axis_aligned_plane needs "
+                               "hyper_slice_out_dim == GLO_dim)")
+        rgb_feats = posenc_features(1, range(3), self.dir_freq, False) if self.use_viewdirs else []
+        alpha_aux = None
+        if self.use_nerf_embed:
+            if self.use_alpha_condition:
+                alpha_aux = AuxSpec(copy_features(2, range(self.GLO_dim), True))
+            if self.use_rgb_condition:
+                rgb_feats += copy_features(2, range(self.GLO_dim), True)
+        return modules.nerf_mlp_layers(m, f"nerf_mlps_{level}", AuxSpec(point_feats), alpha_aux,
+                                       AuxSpec(rgb_feats) if rgb_feats else None, dst_rgb=dst_rgb, dst_alpha=dst_alpha)
+
     def _template_call(self, level: str, n_point_ch: int, xyz_grad: bool, hyper_grad: bool) -> F.ProgramCall:
         """Program of query_template (models.py:447-493): sources 0 = (warped) points (P, 3+H),
         1 = viewdirs (B,3), 2 = template GLO embedding (B,G)."""
-        key = (level, n_point_ch, xyz_grad, hyper_grad)
-        call = self._live_call(key)
-        if call is None:
-            m = self.nerf_mlps_fine if level == 'fine' else self.nerf_mlps_coarse
+        def build():
             feats = posenc_features(0, range(3), self.xyz_freq, xyz_grad)
             if n_point_ch > 3:
                 feats += posenc_features(0, range(3, n_point_ch), self.hyper_freq, hyper_grad)
-            if len(feats) != m.in_ch:
-                raise RuntimeError(f"template input has {len(feats)} channels, the MLP expects {m.in_ch} "
-                                   "(the reference shape-errors the same way, e.g. axis_aligned_plane needs "
-                                   "hyper_slice_out_dim == GLO_dim)")
-            rgb_feats = posenc_features(1, range(3), self.dir_freq, False) if self.use_viewdirs else []
-            alpha_aux = None
-            if self.use_nerf_embed:
-                if self.use_alpha_condition:
-                    alpha_aux = AuxSpec(copy_features(2, range(self.GLO_dim), True))
-                if self.use_rgb_condition:
-                    rgb_feats += copy_features(2, range(self.GLO_dim), True)
-            layers = modules.nerf_mlp_layers(m, f"nerf_mlps_{level}", AuxSpec(feats), alpha_aux,
-                                             AuxSpec(rgb_feats) if rgb_feats else None)
-            call = F.ProgramCall(Program(layers, name=f"template_{level}"), [False, True, True], [3, 1],
-                                 [("g", 0), ("g", 1), ("y", 0)])
-            self._template_calls[key] = call
-        return call
+            return F.ProgramCall(Program(self._template_layers(level, feats), name=f"template_{level}"),
+                                 [False, True, True], [3, 1], [("g", 0), ("g", 1), ("y", 0)])
+        return self._cached_call((level, n_point_ch, xyz_grad, hyper_grad), build)
 
     def _gather_table(self, use_warp: bool):
         """(GLOEmbed module, metadata key) when every embedding the TEMPLATE stage of a level consumes — the alpha /
@@ -271,31 +300,13 @@ class NerfModel(nn.Module):
         all): sources 0 = spatial points (P,3), 1 = viewdirs (B,3), 2 = the GLO table, gathered with the ray's index
         by the kernels — conditions and, for the axis-aligned slice, the hyper coordinates are read from the row, and
         the row's gradient is reduced and scattered by the backward machine."""
-        key = ("tgather", level, hyper_from_table, xyz_grad)
-        call = self._live_call(key)
-        if call is None:
-            m = self.nerf_mlps_fine if level == 'fine' else self.nerf_mlps_coarse
-            G = self.GLO_dim
+        def build():
             feats = posenc_features(0, range(3), self.xyz_freq, xyz_grad)
             if hyper_from_table:
-                feats += posenc_features(2, range(G), self.hyper_freq, True)
-            if len(feats) != m.in_ch:
-                raise RuntimeError(f"template input has {len(feats)} channels, the MLP expects {m.in_ch} "
-                                   "(the reference shape-errors the same way, e.g. axis_aligned_plane needs "
-                                   "hyper_slice_out_dim == GLO_dim)")
-            rgb_feats = posenc_features(1, range(3), self.dir_freq, False) if self.use_viewdirs else []
-            alpha_aux = None
-            if self.use_nerf_embed:
-                if self.use_alpha_condition:
-                    alpha_aux = AuxSpec(copy_features(2, range(G), True))
-                if self.use_rgb_condition:
-                    rgb_feats += copy_features(2, range(G), True)
-            layers = modules.nerf_mlp_layers(m, f"nerf_mlps_{level}", AuxSpec(feats), alpha_aux,
-                                             AuxSpec(rgb_feats) if rgb_feats else None)
-            call = F.ProgramCall(Program(layers, name=f"template_{level}", no_direct=(2,)), [False, True, True], [3, 1],
-                                 [("g", 0), ("g", 1), ("y", 0)], gather_src=2)
-            self._template_calls[key] = call
-        return call
+                feats += posenc_features(2, range(self.GLO_dim), self.hyper_freq, True)
+            return F.ProgramCall(Program(self._template_layers(level, feats), name=f"template_{level}", no_direct=(2,)),
+                                 [False, True, True], [3, 1], [("g", 0), ("g", 1), ("y", 0)], gather_src=2)
+        return self._cached_call(("tgather", level, hyper_from_table, xyz_grad), build)
 
     def _template_reuse_call(self, level: str, n_hyper_pts: int, hyper_from_table: bool, warped_grad: bool) -> F.ProgramCall:
         """query_template (models.py:447-493) over warped points that ALREADY exist — the fine level's pass over the
@@ -303,31 +314,16 @@ class NerfModel(nn.Module):
         wrote them (xyz in columns 0-2; bendy sheet: the sheet's H outputs behind them), 1 = viewdirs (B,3), 2 = the
         GLO table gathered by ray (conditions; the axis-aligned slice's hyper coordinates).  The gradient w.r.t. source 0
         is what the coarse level program takes as the external gradient on its `warped_points` output."""
-        key = ("treuse", level, n_hyper_pts, hyper_from_table, warped_grad)
-        call = self._live_call(key)
-        if call is None:
-            m = self.nerf_mlps_fine if level == 'fine' else self.nerf_mlps_coarse
-            G = self.GLO_dim
+        def build():
             feats = posenc_features(0, range(3), self.xyz_freq, warped_grad)
             if n_hyper_pts:
                 feats += posenc_features(0, range(3, 3 + n_hyper_pts), self.hyper_freq, warped_grad)
             elif hyper_from_table:
-                feats += posenc_features(2, range(G), self.hyper_freq, True)
-            if len(feats) != m.in_ch:
-                raise RuntimeError(f"template input has {len(feats)} channels, the MLP expects {m.in_ch}")
-            rgb_feats = posenc_features(1, range(3), self.dir_freq, False) if self.use_viewdirs else []
-            alpha_aux = None
-            if self.use_nerf_embed:
-                if self.use_alpha_condition:
-                    alpha_aux = AuxSpec(copy_features(2, range(G), True))
-                if self.use_rgb_condition:
-                    rgb_feats += copy_features(2, range(G), True)
-            layers = modules.nerf_mlp_layers(m, f"nerf_mlps_{level}", AuxSpec(feats), alpha_aux,
-                                             AuxSpec(rgb_feats) if rgb_feats else None)
-            call = F.ProgramCall(Program(layers, name=f"template_{level}_reuse", no_direct=(2,)), [False, True, True],
-                                 [3, 1], [("g", 0), ("g", 1), ("y", 0)], gather_src=2)
-            self._template_calls[key] = call
-        return call
+                feats += posenc_features(2, range(self.GLO_dim), self.hyper_freq, True)
+            return F.ProgramCall(Program(self._template_layers(level, feats), name=f"template_{level}_reuse",
+                                         no_direct=(2,)),
+                                 [False, True, True], [3, 1], [("g", 0), ("g", 1), ("y", 0)], gather_src=2)
+        return self._cached_call(("treuse", level, n_hyper_pts, hyper_from_table, warped_grad), build)
 
     # ---- fused level program -------------------------------------------------------------------
     FUSE_LEVELS = True      # warp field -> hyper sheet -> template as ONE launch per level where the model allows it
@@ -340,7 +336,7 @@ class NerfModel(nn.Module):
     # the fine loss reaches the warp field through the coarse level program's external `warped_points` gradient.
     # At config 2: 1/3 of all warp + sheet forward, backward and weight-gradient work and ~10 % of the stash bytes.
     REUSE_COARSE = os.environ.get("HN_REUSE_COARSE", "1") != "0"
-    PREPACK = os.environ.get("HN_PREPACK", "1") != "0"      # one pack launch for the programs of a step (_prepack)
+    PREPACK = os.environ.get("HN_PREPACK", "1") != "0"      # one pack launch for the programs of a step (_prepack_calls)
 
     def _can_fuse_level(self, use_warp: bool, metadata_encoded: bool, metadata) -> bool:
         """One launch per level needs: a TranslationField warp, hyper coordinates from the sheet MLP (or none), and
@@ -363,12 +359,12 @@ class NerfModel(nn.Module):
         # warp, sheet and template share ONE budget of staged source components / source-gradient rows in a fused
         # program (32 each): a configuration that compiles network by network (a large GLO_dim) may not fit — then the
         # level runs unfused instead of raising
-        if ("nofuse",) in self._template_calls:
+        if "fuse" in self._no_fit:
             return False
         try:
             self._level_call('coarse')
         except NotImplementedError:
-            self._template_calls[("nofuse",)] = None
+            self._no_fit.add("fuse")
             return False
         return True
 
@@ -378,11 +374,7 @@ class NerfModel(nn.Module):
         (gathered with the ray's index), 3 = the warped points — published by the warp / sheet heads in the forward
         launch (they never leave the workgroup), read back from the output tensor in the backward launch.
         Outputs: 0 = warped points (P, 3+H), 1 = rgb (P,3), 2 = alpha (P,1)."""
-        key = ("level", level)
-        call = self._live_call(key)
-        if call is None:
-            m = self.nerf_mlps_fine if level == 'fine' else self.nerf_mlps_coarse
-            G = self.GLO_dim
+        def build():
             wf = self.warp_field
             layers = modules.mlp_layers(wf.mlp, "warp_field.mlp", wf.input_aux(0, 2, False, True), None,
                                         OutSpec(0, 0, "none", residual=(0, 0), publish=(3, 0)),
@@ -400,28 +392,15 @@ class NerfModel(nn.Module):
             elif self.hyper_slice_method == 'axis_aligned_plane':
                 # hyper coordinates = the ray's GLO row itself (models.py:533-534): encoded from the gathered source;
                 # the kernel does not copy them into `warped_points`, run_program fills those columns
-                h = G
-                feats += posenc_features(2, range(G), self.hyper_freq, True)
+                h = self.GLO_dim
+                feats += posenc_features(2, range(h), self.hyper_freq, True)
                 fill = (0, 3)
-            if len(feats) != m.in_ch:
-                raise RuntimeError(f"template input has {len(feats)} channels, the MLP expects {m.in_ch} (the "
-                                   "reference shape-errors the same way, e.g. axis_aligned_plane needs "
-                                   "hyper_slice_out_dim == GLO_dim)")
-            rgb_feats = posenc_features(1, range(3), self.dir_freq, False) if self.use_viewdirs else []
-            alpha_aux = None
-            if self.use_nerf_embed:
-                if self.use_alpha_condition:
-                    alpha_aux = AuxSpec(copy_features(2, range(G), True))
-                if self.use_rgb_condition:
-                    rgb_feats += copy_features(2, range(G), True)
-            layers += modules.nerf_mlp_layers(m, f"nerf_mlps_{level}", AuxSpec(feats), alpha_aux,
-                                              AuxSpec(rgb_feats) if rgb_feats else None, dst_rgb=1, dst_alpha=2)
-            call = F.ProgramCall(Program(layers, name=f"level_{level}", no_direct=(2,)), [False, True, True, False],
+            layers += self._template_layers(level, feats, dst_rgb=1, dst_alpha=2)
+            return F.ProgramCall(Program(layers, name=f"level_{level}", no_direct=(2,)), [False, True, True, False],
                                  [3 + h, 3, 1],
                                  [("g", 1), ("g", 2), ("y", 1), ("go", 0)], gather_src=2, bwd_src_from_out={3: 0},
                                  fill_from_gather=fill)
-            self._template_calls[key] = call
-        return call
+        return self._cached_call(("level", level), build)
 
     def compiled_programs(self, n_rays: int, reference: bool = False):
         """[(name, machine.Program, points evaluated per forward pass of `n_rays` rays)] of the programs this model has
@@ -433,8 +412,6 @@ class NerfModel(nn.Module):
         fused = False
         reuse = None if reference else getattr(self, "_reused_coarse", None)
         for key, call in self._template_calls.items():
-            if call is None:            # the ("nofuse",) marker
-                continue
             if key[0] == "level":
                 n_fine = nf if reuse else nc + nf       # with REUSE_COARSE the fine level program sees the new samples only
                 out.append((f"level_{key[1]}", call.program, n_rays * (nc if key[1] == 'coarse' else n_fine)))
@@ -484,14 +461,38 @@ class NerfModel(nn.Module):
         warped = spatial if hyper is None else torch.cat([spatial, hyper], dim=-1)
         return warped, None
 
-    def render_samples(self, level, points, z_vals, directions, viewdirs, metadata, extra_params, use_warp=True,
-                       metadata_encoded=False, return_warp_jacobian=False, use_sample_at_infinity=False,
-                       render_opts=None, noise=None, then_pdf=None):
-        """One level of the render (reference: models.py:587-671).  `then_pdf` (forward() for the coarse level): the fine
-        level's inverse-CDF sampling rides on this level's compositing launch; its results land in out['_pdf']."""
-        self._then_pdf = then_pdf
-        # filter_sigma (reference models.py:35-63, call site :650) runs inside the compositing kernel: the dust
-        # threshold as a scalar, the bounding box as a 0/1 mask over the sample points
+    # ---- one level ------------------------------------------------------------------------------
+    def _begin_pass(self, level, use_warp, metadata_encoded, metadata, extra_params, return_warp_jacobian, viewdirs,
+                    directions) -> _Pass:
+        """What a pass is called with, and the path its levels take, decided once (see _Pass); `level`: the first
+        level it runs."""
+        path, tab = 'networks', None
+        if self._can_fuse_level(use_warp, metadata_encoded, metadata):
+            path, tab = 'fused', (self.warp_embed, self.warp_embed_key)
+        elif (self.FUSE_LEVELS and not metadata_encoded and metadata.get('hyper_point') is None
+                and not return_warp_jacobian and not (use_warp and self.hyper_slice_method == 'bendy_sheet')):
+            tab = self._gather_table(use_warp)
+            if tab is not None and "gather" not in self._no_fit:
+                # a GLO table too wide for the staging / source-gradient budget of ONE program: the levels run network
+                # by network (embedding rows looked up first, surplus copies read directly) instead of raising
+                try:
+                    self._template_gather_call(level, use_warp and self.hyper_slice_method == 'axis_aligned_plane',
+                                               torch.is_grad_enabled() and use_warp)
+                    path = 'gather'
+                except NotImplementedError:
+                    self._no_fit.add("gather")
+        return _Pass(use_warp, metadata_encoded, metadata, extra_params, return_warp_jacobian, viewdirs, directions,
+                     path, tab if path != 'networks' else None)
+
+    @staticmethod
+    def _ray_index(idx):
+        """Ids given per ray as (B,) or (B,1) -> (B,)."""
+        return idx.squeeze(-1) if idx.shape[-1] == 1 and idx.dim() > 1 else idx
+
+    @staticmethod
+    def _dust_keep(points, render_opts):
+        """filter_sigma (reference models.py:35-63, call site :650) runs inside the compositing kernel: the dust
+        threshold as a scalar, the bounding box as a 0/1 mask over the sample points."""
         dust, keep = None, None
         if render_opts is not None:
             if 'dust_threshold' in render_opts:
@@ -500,71 +501,52 @@ class NerfModel(nn.Module):
                 xmin, xmax, ymin, ymax, zmin, zmax = render_opts['bounding_box']
                 keep = ((points[..., 0] >= xmin) & (points[..., 0] <= xmax) & (points[..., 1] >= ymin)
                         & (points[..., 1] <= ymax) & (points[..., 2] >= zmin) & (points[..., 2] <= zmax)).float()
-        b, s = points.shape[0], points.shape[1]
-        out = {'points': points}
-        warped, rgb, alpha = self._level_fields(level, points, viewdirs, metadata, extra_params, use_warp,
-                                                metadata_encoded, return_warp_jacobian)
-        return self._composite_level(out, warped, rgb, alpha, z_vals, directions, noise, use_sample_at_infinity,
-                                     dust, keep, b, s, points.device, level)
+        return dust, keep
 
-    def _level_fields(self, level, points, viewdirs, metadata, extra_params, use_warp, metadata_encoded,
-                      return_warp_jacobian):
-        """The networks of one level on `points` (B,S,3), everything render_samples computes before it composites:
-        (warped points (B,S,3+H), rgb (B*S,3), raw density (B*S,1)) on whichever path the model takes — the fused level
-        program, a gathered template with the warp outside, or network by network."""
+    def _density_noise(self, noise, drawn, shape, device):
+        """(noise, scale) of noise_regularize (models.py:485-489): the caller's `noise` as it is; otherwise, where the
+        model asks for noise, the N(0,1) tensor forward() `drawn` for this level (or one drawn here), scaled by noise_std
+        inside the compositing kernel."""
+        if noise is not None or self.noise_std is None or not (self.noise_std > 0.0 and self.use_stratified_sampling):
+            return noise, 1.0
+        if drawn is None or tuple(drawn.shape) != shape:
+            drawn = torch.randn(shape, device=device, dtype=torch.float32)
+        return drawn, float(self.noise_std)
+
+    def _level_fields(self, p: _Pass, level, points):
+        """The networks of one level on `points` (B,S,3), everything a level computes before it composites, on the path
+        the pass takes: (warped points (B,S,3+H), rgb (B*S,3), raw density (B*S,1), the warped xyz (B,S,3) a fine level
+        re-using these samples needs next to a gathered template (REUSE_COARSE) | None)."""
         b, s = points.shape[0], points.shape[1]
-        if self._can_fuse_level(use_warp, metadata_encoded, metadata):
-            if return_warp_jacobian:
+        vd = p.viewdirs if self.use_viewdirs else None
+        metadata = p.metadata
+        if p.path == 'fused':
+            if p.return_warp_jacobian:
                 raise NotImplementedError
-            idx = metadata[self.warp_embed_key]
-            if idx.shape[-1] == 1 and idx.dim() > 1:
-                idx = idx.squeeze(-1)
-            call = self._level_call(level)
-            warped, rgb, alpha = F.run_program(call, [points.reshape(b * s, 3), viewdirs if self.use_viewdirs else None,
-                                                      self.warp_embed.embed.weight, None], s, self.precision,
-                                               gather_idx=idx)
-            warped = warped.view(b, s, -1)
-            return warped, rgb, alpha
-        tab = None
-        if (self.FUSE_LEVELS and not metadata_encoded and metadata.get('hyper_point') is None
-                and not return_warp_jacobian and not (use_warp and self.hyper_slice_method == 'bendy_sheet')):
-            tab = self._gather_table(use_warp)
-        if tab is not None:
-            # a GLO table too wide for the staging / source-gradient budget of ONE program: the generic path below
-            # (embedding rows looked up first, surplus copies read directly) takes over instead of raising
-            if ("nogather",) in self._template_calls:
-                tab = None
-            else:
-                try:
-                    self._template_gather_call(level, use_warp and self.hyper_slice_method == 'axis_aligned_plane',
-                                               torch.is_grad_enabled() and use_warp)
-                except NotImplementedError:
-                    self._template_calls[("nogather",)] = None
-                    tab = None
-        if tab is not None:
+            emb_mod, key = p.tab
+            warped, rgb, alpha = F.run_program(self._level_call(level), [points.reshape(b * s, 3), vd,
+                                                                        emb_mod.embed.weight, None], s, self.precision,
+                                               gather_idx=self._ray_index(metadata[key]))
+            return warped.view(b, s, -1), rgb, alpha, None
+        if p.path == 'gather':
             # the warp (if any) runs as its own program; the template reads conditions / axis-aligned hyper
             # coordinates straight from the GLO table (no gather kernel, no (B,S,H) expand + cat in front of it, the
             # row gradient reduced in the backward machine)
-            emb_mod, key = tab
-            idx = metadata[key]
-            if idx.shape[-1] == 1 and idx.dim() > 1:
-                idx = idx.squeeze(-1)
-            from_table = use_warp and self.hyper_slice_method == 'axis_aligned_plane'
-            xyz, warped_rows = self._warp_outside(points, metadata, idx, emb_mod, from_table, use_warp, extra_params)
+            emb_mod, key = p.tab
+            idx = self._ray_index(metadata[key])
+            from_table = p.use_warp and self.hyper_slice_method == 'axis_aligned_plane'
+            xyz, warped_rows = self._warp_outside(points, metadata, idx, emb_mod, from_table, p.use_warp, p.extra_params)
             ge = torch.is_grad_enabled() and xyz.requires_grad
-            call = self._template_gather_call(level, from_table, ge)
-            rgb, alpha = F.run_program(call, [xyz.reshape(b * s, 3), viewdirs if self.use_viewdirs else None,
-                                              emb_mod.embed.weight], s, self.precision, gather_idx=idx)
+            rgb, alpha = F.run_program(self._template_gather_call(level, from_table, ge),
+                                       [xyz.reshape(b * s, 3), vd, emb_mod.embed.weight], s, self.precision, gather_idx=idx)
             warped = self._warped_of(xyz, warped_rows, from_table, emb_mod, idx, b, s)
-            if use_warp:        # what a fine level re-using these samples needs (REUSE_COARSE)
-                self._level_state = {'level': level, 'xyz': xyz, 'rows': warped_rows is not None, 'tab': tab}
-            return warped, rgb, alpha
-        if use_warp:
-            warp_embed = metadata['encoded_warp'] if metadata_encoded else self.warp_embed(metadata[self.warp_embed_key])
+            return warped, rgb, alpha, xyz if p.use_warp else None
+        if p.use_warp:
+            warp_embed = metadata['encoded_warp'] if p.metadata_encoded else self.warp_embed(metadata[self.warp_embed_key])
         else:
             warp_embed = None
         if self.has_hyper_embed:
-            if metadata_encoded:
+            if p.metadata_encoded:
                 hyper_embed = metadata['encoded_hyper']
             elif self.hyper_use_warp_embed:
                 hyper_embed = warp_embed
@@ -572,16 +554,58 @@ class NerfModel(nn.Module):
                 hyper_embed = self.hyper_embed(metadata[self.hyper_embed_key])
         else:
             hyper_embed = None
-        warped, _ = self.map_points(points, warp_embed, hyper_embed, extra_params, use_warp=use_warp,
-                                    return_warp_jacobian=return_warp_jacobian,
+        warped, _ = self.map_points(points, warp_embed, hyper_embed, p.extra_params, use_warp=p.use_warp,
+                                    return_warp_jacobian=p.return_warp_jacobian,
                                     hyper_point_override=metadata.get('hyper_point'))
-        nerf_embed = self.get_condition_inputs(viewdirs, metadata, metadata_encoded)
+        nerf_embed = self.get_condition_inputs(p.viewdirs, metadata, p.metadata_encoded)
         n_ch = warped.shape[-1]
         ge = torch.is_grad_enabled() and warped.requires_grad
         call = self._template_call(level, n_ch, ge, ge and n_ch > 3)
-        rgb, alpha = F.run_program(call, [warped.reshape(b * s, n_ch), viewdirs if self.use_viewdirs else None,
-                                          nerf_embed], s, self.precision)
-        return warped, rgb, alpha
+        rgb, alpha = F.run_program(call, [warped.reshape(b * s, n_ch), vd, nerf_embed], s, self.precision)
+        return warped, rgb, alpha, None
+
+    def _composite_level(self, p: _Pass, points, warped, rgb, alpha, z_vals, noise, drawn, use_sample_at_infinity,
+                         dust, keep, then_pdf=None, new=None):
+        """noise_regularize + Softplus + filter_sigma + volumetric_rendering + median-depth gather
+        (models.py:485-489, 650-669) in the compositing kernel.  `then_pdf`: the next level's inverse-CDF sampling rides
+        on this launch.  `new` = (rgb, raw density, warped points, merge permutation): the level comes in two parts,
+        (warped, rgb, alpha) of the first samples and those of the `new` ones (_render_fine_reusing_coarse).
+        Returns (the level's result dict, sample_pdf's results | None)."""
+        b, s = z_vals.shape
+        noise, scale = self._density_noise(noise, drawn, (b, s, 1), z_vals.device)
+        parts = {}
+        if new is not None:
+            n_new = s - alpha.numel() // b
+            parts = dict(rgb1=new[0].view(b, n_new, 3), raw1=new[1].view(b, n_new), warped1=new[2].view(b, n_new, -1),
+                         perm=new[3])
+        res = F.composite(rgb.view(b, -1, 3), alpha.view(b, -1), noise, z_vals, p.directions, warped, variant=0,
+                          white_bg=self.use_white_background, sample_at_infinity=use_sample_at_infinity,
+                          want_median=True, dust_threshold=dust, keep=keep, noise_scale=scale, then_pdf=then_pdf, **parts)
+        out = {'points': points, 'warped_points': warped if new is None else res[6], 'rgb': res[0], 'depth': res[1],
+               'acc': res[2], 'weights': res[3], 'med_depth': res[4], 'med_points': res[5].view(b, 1, 1)}
+        return out, None if then_pdf is None else res[-(6 if then_pdf.get('split') else 4):]
+
+    def _render_level(self, p: _Pass, level, points, z_vals, noise, drawn, use_sample_at_infinity, render_opts,
+                      then_pdf=None):
+        """One level (reference: models.py:587-671): (result dict, sample_pdf's results | None, _level_fields' xyz)."""
+        dust, keep = self._dust_keep(points, render_opts)
+        warped, rgb, alpha, xyz = self._level_fields(p, level, points)
+        out, pdf = self._composite_level(p, points, warped, rgb, alpha, z_vals, noise, drawn, use_sample_at_infinity,
+                                         dust, keep, then_pdf)
+        return out, pdf, xyz
+
+    def render_samples(self, level, points, z_vals, directions, viewdirs, metadata, extra_params, use_warp=True,
+                       metadata_encoded=False, return_warp_jacobian=False, use_sample_at_infinity=False,
+                       render_opts=None, noise=None, then_pdf=None):
+        """One level of the render (reference: models.py:587-671).  `then_pdf`: the next level's inverse-CDF sampling
+        rides on this level's compositing launch; its results land in out['_pdf']."""
+        p = self._begin_pass(level, use_warp, metadata_encoded, metadata, extra_params, return_warp_jacobian, viewdirs,
+                             directions)
+        out, pdf, _ = self._render_level(p, level, points, z_vals, noise, None, use_sample_at_infinity, render_opts,
+                                         then_pdf)
+        if pdf is not None:
+            out['_pdf'] = pdf
+        return out
 
     def query_points(self, points, metadata, level='fine', viewdirs=None, use_warp=True, extra_params=None,
                      render_opts=None):
@@ -607,12 +631,8 @@ class NerfModel(nn.Module):
                         'sigma': points.new_zeros((b, s))}
             if viewdirs is None:
                 viewdirs = points.new_tensor([0.0, 0.0, 1.0]).expand(b, 3).contiguous()
-            state = getattr(self, '_level_state', None)     # (a forward pass in flight keeps its coarse level's state)
-            try:
-                warped, rgb, alpha = self._level_fields(level, points, viewdirs, metadata, extra_params or {}, use_warp,
-                                                        False, False)
-            finally:
-                self._level_state = state
+            p = self._begin_pass(level, use_warp, False, metadata, extra_params or {}, False, viewdirs, None)
+            warped, rgb, alpha, _ = self._level_fields(p, level, points)
             sigma = F.density_activate(alpha.view(b, s), points, render_opts)
             return {'warped_points': warped.reshape(b, s, -1), 'rgb': rgb.view(b, s, 3), 'sigma': sigma}
 
@@ -642,115 +662,6 @@ class NerfModel(nn.Module):
             rows.masked_fill_((safe != flat)[:, None], float("nan"))   # as the kernels' own gather poisons it
         return torch.cat([xyz, rows[:, None, :].expand(b, s, rows.shape[-1])], dim=-1)
 
-    def _can_reuse_coarse(self, use_warp, metadata_encoded, metadata, return_warp_jacobian) -> Optional[str]:
-        """'fused' / 'outside' when the fine level may take the warp of the coarse level's samples from the coarse
-        level (REUSE_COARSE), else None: the coarse level ran as one fused program, or with its warp field as a program
-        of its own in front of a gathered template (SE3Field: BASELINE config 5)."""
-        if not (self.REUSE_COARSE and use_warp) or return_warp_jacobian:
-            return None
-        if self._can_fuse_level(use_warp, metadata_encoded, metadata):
-            return 'fused'
-        st = getattr(self, '_level_state', None)
-        if st is not None and st['level'] == 'coarse' and st['xyz'].shape[1] == self.num_coarse_samples:
-            return 'outside'
-        return None
-
-    def _prepack(self, use_warp, metadata_encoded, metadata, return_warp_jacobian, device, collect=False):
-        """The weight streams of every program this forward pass is about to launch, packed by ONE launch
-        (machine.pack_many) where more than one of them is stale — after an optimizer step that is all three of a
-        training step's (coarse level, fine level over the new samples, fine template over the coarse samples): three
-        dispatches of ~9 us for ~4 us of work each.  A prediction only: a program it misses packs itself as before.
-        `collect`: return the pack groups (machine.collect_pack_jobs) instead of launching them — the step head
-        (functional.render_prologue) packs them in its own launch."""
-        if not self.PREPACK or not self._can_fuse_level(use_warp, metadata_encoded, metadata):
-            return []
-        from .. import machine
-        calls = [self._level_call('coarse')]
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in calls[0].program.params)
-        if self.num_fine_samples > 0:
-            calls.append(self._level_call('fine'))
-            if self.REUSE_COARSE and not return_warp_jacobian:
-                n_hyper = self.hyper_sheet_out_dim if self.hyper_slice_method == 'bendy_sheet' else 0
-                calls.append(self._template_reuse_call('fine', n_hyper, self.hyper_slice_method == 'axis_aligned_plane', grad))
-        if collect:
-            groups = machine.collect_pack_jobs([c.runner for c in calls], device, F.mode_of(self.precision), force=grad,
-                                               min_jobs=1)
-            if len(groups) <= 1:
-                return groups
-            for m, arr, grp in groups:           # two numeric modes in one model: not the step head's business
-                L.launch("hn_pack_units_multi", m, arr, len(grp), L.stream_handle())
-                machine.mark_packed(grp)
-            return []
-        machine.pack_many([c.runner for c in calls], device, F.mode_of(self.precision), force=grad)
-        return []
-
-    def _render_fine_reusing_coarse(self, coarse, points, z_vals, pts_new, perm, directions, viewdirs, metadata,
-                                    use_sample_at_infinity, render_opts, noise, extra_params=None, how='fused'):
-        """The fine level (models.py:752-768 -> render_samples 587-671) without re-evaluating the shared networks on the
-        coarse level's samples (REUSE_COARSE).  `points` / `z_vals` (B, Nc+Nf, .) sorted, `pts_new` (B, Nf, 3) the new
-        samples in draw order, `perm` (B, Nc+Nf) the merge permutation.  Returns the same dict as render_samples."""
-        b, s = z_vals.shape
-        nc = self.num_coarse_samples
-        nf = s - nc
-        dust, keep = None, None
-        if render_opts is not None:
-            if 'dust_threshold' in render_opts:
-                dust = float(render_opts.get('dust_threshold', 0.0))
-            if 'bounding_box' in render_opts:
-                xmin, xmax, ymin, ymax, zmin, zmax = render_opts['bounding_box']
-                keep = ((points[..., 0] >= xmin) & (points[..., 0] <= xmax) & (points[..., 1] >= ymin)
-                        & (points[..., 1] <= ymax) & (points[..., 2] >= zmin) & (points[..., 2] <= zmax)).float()
-        vd = viewdirs if self.use_viewdirs else None
-        from_table = self.hyper_slice_method == 'axis_aligned_plane'
-        w_old = coarse['warped_points']                                   # (B, Nc, 3 + H)
-        if how == 'fused':
-            idx = metadata[self.warp_embed_key]
-            if idx.shape[-1] == 1 and idx.dim() > 1:
-                idx = idx.squeeze(-1)
-            table = self.warp_embed.embed.weight
-            # (i) the coarse level's samples: their warped points exist (output of the coarse program) — the fine
-            # template alone
-            n_hyper = w_old.shape[-1] - 3 if self.hyper_slice_method == 'bendy_sheet' else 0
-            ge = torch.is_grad_enabled() and w_old.requires_grad
-            call_old = self._template_reuse_call('fine', n_hyper, from_table, ge)
-            rgb_old, alpha_old = F.run_program(call_old, [w_old.reshape(b * nc, w_old.shape[-1]), vd, table], nc,
-                                               self.precision, gather_idx=idx)
-            # (ii) the new samples: warp field -> hyper sheet -> fine template, one launch
-            call_new = self._level_call('fine')
-            w_new, rgb_new, alpha_new = F.run_program(call_new, [pts_new.reshape(b * nf, 3), vd, table, None], nf,
-                                                      self.precision, gather_idx=idx)
-        else:
-            # the warp field is a program of its own (SE3Field + exp-map launch): the fine template over the coarse
-            # level's warped xyz, then field + template over the new samples
-            st = self._level_state
-            emb_mod, key = st['tab']
-            idx = metadata[key]
-            if idx.shape[-1] == 1 and idx.dim() > 1:
-                idx = idx.squeeze(-1)
-            table = emb_mod.embed.weight
-            xyz_old = st['xyz']
-            ge = torch.is_grad_enabled() and xyz_old.requires_grad
-            rgb_old, alpha_old = F.run_program(self._template_gather_call('fine', from_table, ge),
-                                               [xyz_old.reshape(b * nc, 3), vd, table], nc, self.precision, gather_idx=idx)
-            xyz_new, rows_new = self._warp_outside(pts_new, metadata, idx, emb_mod, from_table, True, extra_params)
-            ge = torch.is_grad_enabled() and xyz_new.requires_grad
-            rgb_new, alpha_new = F.run_program(self._template_gather_call('fine', from_table, ge),
-                                               [xyz_new.reshape(b * nf, 3), vd, table], nf, self.precision, gather_idx=idx)
-            w_new = self._warped_of(xyz_new, rows_new, from_table, emb_mod, idx, b, nf)
-            self._level_state = None
-        scale = 1.0
-        if noise is None and (self.noise_std is not None) and self.noise_std > 0.0 and self.use_stratified_sampling:
-            noise = getattr(self, '_auto_noise', {}).pop('fine', None)
-            if noise is None or tuple(noise.shape) != (b, s, 1):
-                noise = torch.randn((b, s, 1), device=z_vals.device, dtype=torch.float32)
-            scale = float(self.noise_std)
-        res = F.composite(rgb_old.view(b, nc, 3), alpha_old.view(b, nc), noise, z_vals, directions, w_old, variant=0,
-                          white_bg=self.use_white_background, sample_at_infinity=use_sample_at_infinity,
-                          want_median=True, dust_threshold=dust, keep=keep, noise_scale=scale,
-                          rgb1=rgb_new.view(b, nf, 3), raw1=alpha_new.view(b, nf), warped1=w_new.view(b, nf, -1), perm=perm)
-        return {'points': points, 'warped_points': res[6], 'rgb': res[0], 'depth': res[1], 'acc': res[2],
-                'weights': res[3], 'med_depth': res[4], 'med_points': res[5].view(b, 1, 1)}
-
     def _empty_result(self, like: torch.Tensor, use_warp: bool):
         """Zero rays in, zero rays out (the reference's ATen ops all accept empty batches): no kernel is launched."""
         e = lambda *shape: like.new_zeros(shape)
@@ -767,52 +678,39 @@ class NerfModel(nn.Module):
                           'acc': e(0), 'weights': e(0, s), 'med_depth': e(0), 'med_points': e(0, 1, 1)}
         return out
 
-    def _composite_level(self, out, warped, rgb, alpha, z_vals, directions, noise, use_sample_at_infinity, dust, keep,
-                         b, s, device, level=None):
-        """noise_regularize + Softplus + filter_sigma + volumetric_rendering + median-depth gather
-        (models.py:485-489, 650-669) in the compositing kernel."""
-        scale = 1.0
-        if noise is None and (self.noise_std is not None) and self.noise_std > 0.0 and self.use_stratified_sampling:
-            noise = getattr(self, '_auto_noise', {}).pop(level, None) if level is not None else None   # drawn by forward()
-            if noise is None or tuple(noise.shape) != (b, s, 1):
-                noise = torch.randn((b, s, 1), device=device, dtype=torch.float32)
-            scale = float(self.noise_std)                                              # scaled inside the kernel
-        then_pdf = getattr(self, '_then_pdf', None)
-        self._then_pdf = None
-        res = F.composite(rgb.view(b, s, 3), alpha.view(b, s), noise, z_vals, directions, warped, variant=0,
-                          white_bg=self.use_white_background, sample_at_infinity=use_sample_at_infinity,
-                          want_median=True, dust_threshold=dust, keep=keep, noise_scale=scale, then_pdf=then_pdf)
-        if then_pdf is not None:
-            out['_pdf'] = res[-(6 if then_pdf.get('split') else 4):]
-        out['warped_points'] = warped
-        out['rgb'], out['depth'], out['acc'], out['weights'], out['med_depth'] = res[0], res[1], res[2], res[3], res[4]
-        out['med_points'] = res[5].view(b, 1, 1)
-        return out
+    # ---- forward -------------------------------------------------------------------------------
+    def _reuse_coarse(self, p: _Pass) -> Optional[str]:
+        """'fused' / 'outside' when the fine level takes the warp of the coarse level's samples from the coarse level
+        (REUSE_COARSE), else None: the coarse level runs as one fused program, or with its warp field as a program of
+        its own in front of a gathered template (SE3Field: BASELINE config 5)."""
+        if not (self.REUSE_COARSE and p.use_warp) or p.return_warp_jacobian:
+            return None
+        return {'fused': 'fused', 'gather': 'outside'}.get(p.path)
 
-    def forward(self, rays_dict: Dict[str, Any], extra_params: Dict[str, Any], metadata_encoded=False,
-                use_warp=True, return_points=False, return_weights=False, return_warp_jacobian=False, near=None,
-                far=None, use_sample_at_infinity=None, render_opts=None, deterministic=False,
-                rng: Optional[Dict[str, torch.Tensor]] = None):
-        """Returns {'coarse': {...}, 'fine': {...}} with keys points, warped_points, rgb, depth, med_depth, acc,
-        weights, med_points (reference: models.py:673-780).  `rng` optionally supplies the random draws
-        ('t_rand' (B,Nc), 'u' (B,Nf), 'noise_coarse' (B,Nc,1), 'noise_fine' (B,Nc+Nf,1), noise already scaled);
-        otherwise they are drawn from torch's generator in the reference's order."""
-        rng = rng or {}
-        use_warp = self.use_warp and use_warp
-        origins, directions, metadata = rays_dict['origins'], rays_dict['directions'], rays_dict['metadata']
-        L.require_gpu(origins, directions)
-        viewdirs = rays_dict['viewdirs'] if rays_dict.get('viewdirs') is not None else directions
-        near = self.near if near is None else near
-        far = self.far if far is None else far
-        if use_sample_at_infinity is None:
-            use_sample_at_infinity = self.use_sample_at_infinity
-        b = origins.shape[0]
-        if b == 0:
-            return self._empty_result(origins, use_warp)
-        # every draw the caller did not supply, in ONE launch (F.random_draws) instead of the reference's four ATen
-        # calls (model_utils.py:31 t_rand, :226 u, :300-317 the density noise of each level); the noise stays N(0,1)
-        # and is scaled by noise_std inside the compositing kernel
-        self._auto_noise = {}
+    def _prepack_calls(self, p: _Pass):
+        """(programs, force) of the weight streams a forward pass of fused levels is about to use, for ONE pack launch
+        (machine.pack_many, or the step head's own) where more than one of them is stale — after an optimizer step that
+        is all three of a training step's (coarse level, fine level over the new samples, fine template over the coarse
+        samples): three dispatches of ~9 us for ~4 us of work each.  A prediction only: a program it misses packs
+        itself."""
+        if not self.PREPACK or p.path != 'fused':
+            return [], False
+        calls = [self._level_call('coarse')]
+        grad = torch.is_grad_enabled() and any(q.requires_grad for q in calls[0].program.params)
+        if self.num_fine_samples > 0:
+            calls.append(self._level_call('fine'))
+            if self.REUSE_COARSE and not p.return_warp_jacobian:
+                n_hyper = self.hyper_sheet_out_dim if self.hyper_slice_method == 'bendy_sheet' else 0
+                calls.append(self._template_reuse_call('fine', n_hyper, self.hyper_slice_method == 'axis_aligned_plane', grad))
+        return calls, grad
+
+    def _step_head(self, p: _Pass, origins, near, far, rng):
+        """Every draw the caller did not supply, in ONE launch instead of the reference's four ATen calls
+        (model_utils.py:31 t_rand, :226 u, :300-317 the density noise of each level), and the stale weight streams of
+        the pass.  Returns (`rng` with the drawn 't_rand' / 'u' added, {level: drawn N(0,1) density noise — scaled by
+        noise_std inside the compositing kernel}, z_vals and points of the coarse samples where the launch placed them,
+        else None, None)."""
+        b, device, metadata = origins.shape[0], origins.device, p.metadata
         want = []
         if self.use_stratified_sampling and F.FAST_DRAWS:
             nc, nf = self.num_coarse_samples, self.num_fine_samples
@@ -825,92 +723,139 @@ class NerfModel(nn.Module):
                 want.append(('u', (b, nf), 'uniform'))
             if nf > 0 and noisy and 'noise_fine' not in rng:
                 want.append(('noise_fine', (b, nc + nf, 1), 'normal'))
-        self._level_state = None
+        specs = [(shape, kind) for _, shape, kind in want]
+        calls, force = self._prepack_calls(p)
+        runners, mode = [c.runner for c in calls], F.mode_of(self.precision)
         lazy_ids = isinstance(metadata, model_utils.RayMetadata) and not metadata.converted()
         z_vals = points = None
         if F.PROLOGUE and (want or lazy_ids):
-            # the step head as ONE launch (hn_render_prologue): the draws, the stale weight streams of the programs this
-            # pass will run, the coarse samples placed from the t_rand draw, the int64 image ids of the ray rows — four
-            # launches of 5-13 us (each ~5 us of dispatch floor) otherwise
+            # the step head as ONE launch (hn_render_prologue): the draws, the stale weight streams, the coarse samples
+            # placed from the t_rand draw, the int64 image ids of the ray rows — four launches of 5-13 us (each ~5 us
+            # of dispatch floor) otherwise
             ids = None
             if lazy_ids:
-                ids = (metadata.raw, torch.empty(b, dtype=torch.int64, device=origins.device))
+                ids = (metadata.raw, torch.empty(b, dtype=torch.int64, device=device))
             sample = None
             if want and want[0][0] == 't_rand':
                 lower, upper, _ = model_utils.stratified_bounds(self.num_coarse_samples, near, far,
-                                                                self.use_linear_disparity, origins.device)
-                sample = dict(draw=0, origins=origins, directions=directions, lower=lower, upper=upper)
+                                                                self.use_linear_disparity, device)
+                sample = dict(draw=0, origins=origins, directions=p.directions, lower=lower, upper=upper)
             if ids is not None:
                 metadata.set_converted(ids[1])       # (the launch below fills it; nothing reads it before)
-            groups = self._prepack(use_warp, metadata_encoded, metadata, return_warp_jacobian, origins.device, collect=True)
-            got, z_vals, points = F.render_prologue(origins.device, F.mode_of(self.precision), groups,
-                                                    [(shape, kind) for _, shape, kind in want], sample, ids)
+            groups = machine.collect_pack_jobs(runners, device, mode, force=force, min_jobs=1) if calls else []
+            if len(groups) > 1:                      # two numeric modes in one model: not the step head's business
+                for m, arr, grp in groups:
+                    L.launch("hn_pack_units_multi", m, arr, len(grp), L.stream_handle())
+                    machine.mark_packed(grp)
+                groups = []
+            got, z_vals, points = F.render_prologue(device, mode, groups, specs, sample, ids)
         else:
-            got = F.random_draws([(shape, kind) for _, shape, kind in want], origins.device) if want else []
-            self._prepack(use_warp, metadata_encoded, metadata, return_warp_jacobian, origins.device)
-        if want:
-            rng = dict(rng)
-            for (name, _, _), t in zip(want, got):
-                if name.startswith('noise_'):
-                    self._auto_noise[name[6:]] = t
-                else:
-                    rng[name] = t
+            got = F.random_draws(specs, device) if want else []
+            if calls:
+                machine.pack_many(runners, device, mode, force=force)
+        rng, drawn = dict(rng), {}
+        for (name, _, _), t in zip(want, got):
+            if name.startswith('noise_'):
+                drawn[name[6:]] = t
+            else:
+                rng[name] = t
+        return rng, drawn, z_vals, points
+
+    def _fine_draws(self, p: _Pass, origins, rng):
+        """(u (B,Nf) of the fine level's inverse-CDF sampling, the `then_pdf` that lets it ride on the coarse level's
+        compositing launch | None)."""
+        b, nc, nf = origins.shape[0], self.num_coarse_samples, self.num_fine_samples
+        u = rng.get('u')
+        if u is None:
+            if self.use_stratified_sampling:
+                u = torch.rand(b, nf, device=origins.device)
+            else:
+                # the reference's deterministic draws (model_utils.py:226-227): built on the host with the same
+                # ATen CPU op, uploaded once per (batch, device) — never inside a stream capture
+                key = (b, nf, str(origins.device))
+                u = self._det_u.get(key)
+                if u is None:
+                    u = self._det_u[key] = torch.linspace(0, 1, nf).to(origins.device).expand(b, -1).contiguous()
+        then_pdf = None
+        if F.COMPOSITE_PDF and 3 <= nc <= 256 and nc + nf <= 512:
+            # the split outputs — merge permutation, new points — are produced whenever REUSE_COARSE could apply
+            then_pdf = dict(u=u, origins=origins, directions=p.directions,
+                            split=bool(self.REUSE_COARSE and p.use_warp and not p.return_warp_jacobian))
+        return u, then_pdf
+
+    def _render_fine_reusing_coarse(self, p: _Pass, w_old, xyz_old, points, z_vals, pts_new, perm, noise, drawn,
+                                    use_sample_at_infinity, render_opts):
+        """The fine level (models.py:752-768 -> render_samples 587-671) without re-evaluating the shared networks on the
+        coarse level's samples (REUSE_COARSE): the fine template alone over their warped points — `w_old` (B,Nc,3+H),
+        the coarse level program's output, or `xyz_old` (B,Nc,3) behind a warp field that is a program of its own — and
+        the whole level over the new samples.  `points` / `z_vals` (B, Nc+Nf, .) sorted, `pts_new` (B, Nf, 3) the new
+        samples in draw order, `perm` (B, Nc+Nf) the merge permutation.  Returns the result dict of a level."""
+        b, nc = w_old.shape[0], w_old.shape[1]
+        dust, keep = self._dust_keep(points, render_opts)
+        vd = p.viewdirs if self.use_viewdirs else None
+        from_table = self.hyper_slice_method == 'axis_aligned_plane'
+        emb_mod, key = p.tab
+        idx = self._ray_index(p.metadata[key])
+        if p.path == 'fused':
+            n_hyper = w_old.shape[-1] - 3 if self.hyper_slice_method == 'bendy_sheet' else 0
+            call, old = self._template_reuse_call('fine', n_hyper, from_table,
+                                                  torch.is_grad_enabled() and w_old.requires_grad), w_old
+        else:
+            call, old = self._template_gather_call('fine', from_table,
+                                                   torch.is_grad_enabled() and xyz_old.requires_grad), xyz_old
+        rgb_old, alpha_old = F.run_program(call, [old.reshape(b * nc, old.shape[-1]), vd, emb_mod.embed.weight], nc,
+                                           self.precision, gather_idx=idx)
+        w_new, rgb_new, alpha_new, _ = self._level_fields(p, 'fine', pts_new)
+        return self._composite_level(p, points, w_old, rgb_old, alpha_old, z_vals, noise, drawn, use_sample_at_infinity,
+                                     dust, keep, new=(rgb_new, alpha_new, w_new, perm))[0]
+
+    def _fine_level(self, p: _Pass, coarse, xyz_coarse, pdf, z_vals, u, origins, noise, drawn, use_sample_at_infinity,
+                    render_opts):
+        how = self._reuse_coarse(p)
+        self._reused_coarse = how
+        if pdf is None:
+            pdf = F.sample_pdf(coarse['weights'], z_vals, u, origins, p.directions, split=how is not None)
+        z_fine, pts_fine, inds = pdf[0], pdf[1], pdf[2]
+        if how is None:
+            fine = self._render_level(p, 'fine', pts_fine, z_fine, noise, drawn, use_sample_at_infinity, render_opts)[0]
+        else:
+            fine = self._render_fine_reusing_coarse(p, coarse['warped_points'], xyz_coarse, pts_fine, z_fine, pdf[5],
+                                                    pdf[4], noise, drawn, use_sample_at_infinity, render_opts)
+        # not part of the reference's return value: kept for tests / debugging
+        self.last_sampling = {'z_coarse': z_vals, 'z_fine': z_fine, 'inds': inds, 'u': u}
+        return fine
+
+    def forward(self, rays_dict: Dict[str, Any], extra_params: Dict[str, Any], metadata_encoded=False,
+                use_warp=True, return_points=False, return_weights=False, return_warp_jacobian=False, near=None,
+                far=None, use_sample_at_infinity=None, render_opts=None, deterministic=False,
+                rng: Optional[Dict[str, torch.Tensor]] = None):
+        """Returns {'coarse': {...}, 'fine': {...}} with keys points, warped_points, rgb, depth, med_depth, acc,
+        weights, med_points (reference: models.py:673-780).  `rng` optionally supplies the random draws
+        ('t_rand' (B,Nc), 'u' (B,Nf), 'noise_coarse' (B,Nc,1), 'noise_fine' (B,Nc+Nf,1), noise already scaled);
+        otherwise they are drawn from torch's generator in the reference's order."""
+        use_warp = self.use_warp and use_warp
+        origins, directions, metadata = rays_dict['origins'], rays_dict['directions'], rays_dict['metadata']
+        L.require_gpu(origins, directions)
+        viewdirs = rays_dict['viewdirs'] if rays_dict.get('viewdirs') is not None else directions
+        near = self.near if near is None else near
+        far = self.far if far is None else far
+        if use_sample_at_infinity is None:
+            use_sample_at_infinity = self.use_sample_at_infinity
+        if origins.shape[0] == 0:
+            return self._empty_result(origins, use_warp)
+        p = self._begin_pass('coarse', use_warp, metadata_encoded, metadata, extra_params, return_warp_jacobian,
+                             viewdirs, directions)
+        rng, drawn, z_vals, points = self._step_head(p, origins, near, far, rng or {})
         if z_vals is None:
             z_vals, points = model_utils.sample_along_rays(origins, directions, self.num_coarse_samples, near, far,
                                                            self.use_stratified_sampling, self.use_linear_disparity,
                                                            t_rand=rng.get('t_rand'))
-        u = then_pdf = None
-        if self.num_fine_samples > 0:
-            u = rng.get('u')
-            if u is None:
-                if self.use_stratified_sampling:
-                    u = torch.rand(b, self.num_fine_samples, device=origins.device)
-                else:
-                    # the reference's deterministic draws (model_utils.py:226-227): built on the host with the same
-                    # ATen CPU op, uploaded once per (batch, device) — never inside a stream capture
-                    key = (b, self.num_fine_samples, str(origins.device))
-                    u = self._det_u.get(key)
-                    if u is None:
-                        u = torch.linspace(0, 1, self.num_fine_samples).to(origins.device).expand(b, -1).contiguous()
-                        self._det_u[key] = u
-            if F.COMPOSITE_PDF and 3 <= self.num_coarse_samples <= 256 and self.num_coarse_samples + self.num_fine_samples <= 512:
-                # the fine level's inverse-CDF sampling rides on the coarse level's compositing launch (whether the fine
-                # level will re-use the coarse warp is only known after the coarse level ran: the split outputs — merge
-                # permutation, new points — are produced whenever REUSE_COARSE could apply)
-                then_pdf = dict(u=u, origins=origins, directions=directions,
-                                split=bool(self.REUSE_COARSE and use_warp and not return_warp_jacobian))
-        coarse = self.render_samples('coarse', points, z_vals, directions, viewdirs, metadata, extra_params,
-                                     use_warp=use_warp, metadata_encoded=metadata_encoded,
-                                     return_warp_jacobian=return_warp_jacobian,
-                                     use_sample_at_infinity=self.use_sample_at_infinity,
-                                     noise=rng.get('noise_coarse'), then_pdf=then_pdf)
-        pdf = coarse.pop('_pdf', None)
-        self._then_pdf = None
+        fine = self.num_fine_samples > 0
+        u, then_pdf = self._fine_draws(p, origins, rng) if fine else (None, None)
+        coarse, pdf, xyz = self._render_level(p, 'coarse', points, z_vals, rng.get('noise_coarse'), drawn.get('coarse'),
+                                              self.use_sample_at_infinity, None, then_pdf)
         out = {'coarse': coarse}
-        if self.num_fine_samples > 0:
-            how = self._can_reuse_coarse(use_warp, metadata_encoded, metadata, return_warp_jacobian)
-            self._reused_coarse = how
-            if how is not None and (pdf is None or len(pdf) == 6):
-                if pdf is not None:
-                    z_fine, pts_fine, inds, _, perm, pts_new = pdf
-                else:
-                    z_fine, pts_fine, inds, _, perm, pts_new = F.sample_pdf(coarse['weights'], z_vals, u, origins,
-                                                                            directions, split=True)
-                fine = self._render_fine_reusing_coarse(coarse, pts_fine, z_fine, pts_new, perm, directions, viewdirs,
-                                                        metadata, use_sample_at_infinity, render_opts,
-                                                        rng.get('noise_fine'), extra_params, how)
-            else:
-                if pdf is not None:
-                    z_fine, pts_fine, inds = pdf[0], pdf[1], pdf[2]
-                else:
-                    z_fine, pts_fine, inds, _ = F.sample_pdf(coarse['weights'], z_vals, u, origins, directions)
-                fine = self.render_samples('fine', pts_fine, z_fine, directions, viewdirs, metadata, extra_params,
-                                           use_warp=use_warp, metadata_encoded=metadata_encoded,
-                                           return_warp_jacobian=return_warp_jacobian,
-                                           use_sample_at_infinity=use_sample_at_infinity, render_opts=render_opts,
-                                           noise=rng.get('noise_fine'))
-            out['fine'] = fine
-            # not part of the reference's return value: kept for tests / debugging
-            self.last_sampling = {'z_coarse': z_vals, 'z_fine': z_fine, 'inds': inds, 'u': u}
-        self._level_state = None        # (holds the coarse level's warped xyz, i.e. its autograd graph)
+        if fine:
+            out['fine'] = self._fine_level(p, coarse, xyz, pdf, z_vals, u, origins, rng.get('noise_fine'),
+                                           drawn.get('fine'), use_sample_at_infinity, render_opts)
         return out

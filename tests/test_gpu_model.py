@@ -512,9 +512,9 @@ def test_model_option_matrix_vs_oracle(case):
         if case == "glo24":
             # 37 source components for the fused level program, 5 more than the LDS staging holds, and the surplus
             # belongs to the GATHERED table, which the direct global read does not gather: per-network launches
-            assert ("nofuse",) in m._template_calls and not any(k[0] == "level" for k in m._template_calls)
+            assert "fuse" in m._no_fit and not any(k[0] == "level" for k in m._template_calls)
         if case == "glo25":
-            assert ("nofuse",) in m._template_calls and not any(k[0] == "level" for k in m._template_calls)
+            assert "fuse" in m._no_fit and not any(k[0] == "level" for k in m._template_calls)
         if case == "viewdirs":
             # the same forward with the embeddings looked up by the caller (metadata_encoded, models.py:609-622, 425-436)
             with torch.no_grad():

@@ -39,6 +39,13 @@ def words(prog):
     return out
 
 
+def words_or_error(build):
+    try:
+        return words(build().program)
+    except Exception as e:
+        return f"error: {type(e).__name__}"
+
+
 def model_programs(name, kw):
     torch.manual_seed(0)
     m = NerfModel(EMB, n_samples_coarse=8, n_samples_fine=8, view_fourier_dim=6, **kw)
@@ -46,10 +53,7 @@ def model_programs(name, kw):
         m.warp_field = warping.SE3Field(in_ch=3)
     out = {}
     for level in ("coarse", "fine"):
-        try:
-            out[f"level_{level}"] = words(m._level_call(level).program)
-        except Exception as e:          # not fusable (SE3Field): the template program alone below
-            out[f"level_{level}"] = f"error: {type(e).__name__}"
+        out[f"level_{level}"] = words_or_error(lambda: m._level_call(level))    # SE3Field: not fusable
         for n_ch in range(3, 12):       # the template's point channels: 3 + hyper dimensions
             for xyz_grad in (False, True):
                 try:
@@ -57,6 +61,15 @@ def model_programs(name, kw):
                 except RuntimeError:
                     continue
                 out[f"template_{level}_{n_ch}_{xyz_grad}"] = words(call.program)
+        # the templates that gather their conditions (and axis-aligned hyper coordinates) from the GLO table: every
+        # argument combination, those that do not compile recorded by what they raise
+        for from_table in (False, True):
+            for grad in (False, True):
+                out[f"gather_{level}_{from_table}_{grad}"] = words_or_error(
+                    lambda: m._template_gather_call(level, from_table, grad))
+                for n_hyper in (0, 2, 4, 8):
+                    out[f"reuse_{level}_{n_hyper}_{from_table}_{grad}"] = words_or_error(
+                        lambda: m._template_reuse_call(level, n_hyper, from_table, grad))
     return out
 
 
